@@ -3,11 +3,19 @@
 One step = forward + A3C loss + backward + per-tensor clip + (RCCL gradient mean for N>1) +
 Adam, on a synthetic 84x84x4 uint8 frame batch already resident in HBM.  Default workload:
 configs[2]/[3] — B=2048 per GPU, fc_neurons=512, fc_splits=1, A=4 (Breakout), Adam with the
-README's best hyper-parameters.  The B=32 / F=128 / S=4 parity configuration (configs[1]) is
-timed beside it.  Rank 0 prints ONE JSON line.
+README's best hyper-parameters.  Rank 0 prints ONE JSON line.
 
     python bench.py --gpus N --steps K --warmup W     (N > 1: starts N rank processes itself)
     torchrun --nproc-per-node N ... bench.py --gpus N   (one process per GPU, RCCL)
+
+A plain run sets up, warms up (CLOCK_WARM_STEPS untimed steps while the clock ramps, then W),
+times the K steps and prints the line (`value`, `ms_per_step`).
+`--full` adds everything else the line can carry: the per-kernel probes with `roofline` and
+`ceiling`, the per-step median, the exchange report (N > 1 or --sync-path), the predictor
+overlap (configs[4]), the B=32 / F=128 / S=4 parity configuration (configs[1]) and the CPU
+baseline.  `--dump-outputs DIR` writes what the last timed step left — parameters, optimizer
+slots and the step's scalars — as DIR/<name>.npy; inputs and weights are seeded, so two
+builds run with the same arguments can be compared array for array.
 
 Without WORLD_SIZE in the environment and --gpus N > 1, this process is only a launcher: it
 makes no GPU call, starts N children (`python bench.py ...` with RANK / LOCAL_RANK /
@@ -224,14 +232,17 @@ def sync_all(world):
         torch.cuda.synchronize()
 
 
-def time_steps(tr, batch, steps, warmup, world, probe=None, probe_every=1):
+def time_steps(tr, batch, steps, warmup, world, probe=None, probe_every=1, median=True,
+               after_timed=None):
     """Time exactly `steps` steps bracketed by barrier + synchronize (max over ranks): the
     wall clock, and HIP events around the whole run on the learner stream.  Then, outside the
-    timed region, `steps` more steps with an event after each (every event recorded on the
-    learner stream leaves a 5-6 us gap between its kernels, r06c trace) for the per-step
-    median.  `probe`: the kernel whose launches the HIP-event probe brackets inside the timed
-    steps, the first of every `probe_every` (each bracket's two events leave ~10 us of gaps in
-    the stream, so a throughput run samples them; ba3c_probe_every)."""
+    timed region and only with `median`, `steps` more steps with an event after each (every
+    event recorded on the learner stream leaves a 5-6 us gap between its kernels, r06c trace)
+    for the per-step median (None without).  `probe`: the kernel whose launches the HIP-event
+    probe brackets inside the timed steps, the first of every `probe_every` (each bracket's two
+    events leave ~10 us of gaps in the stream, so a throughput run samples them;
+    ba3c_probe_every).  `after_timed()` is called once the timed steps have completed, before
+    any further step runs (--dump-outputs takes its snapshot there)."""
     for _ in range(warmup):
         tr.train_step(*batch)
     sync_all(world)
@@ -250,18 +261,21 @@ def time_steps(tr, batch, steps, warmup, world, probe=None, probe_every=1):
     if probe is not None:
         probe_ms, launches = tr.engine.probe_read()   # the probe covers the timed steps only
         tr.engine.probe_enable(None)
-    evs = [hipevent.timing_event() for _ in range(steps + 1)]
-    evs[0].record()
-    for i in range(steps):
-        tr.train_step(*batch)
-        evs[i + 1].record()
-    sync_all(world)
-    per_step = [evs[i].elapsed_time(evs[i + 1]) for i in range(steps)]
-    el = torch.tensor([max(wall, gpu_s), float(np.median(per_step))], dtype=torch.float64,
-                      device="cuda")
+    if after_timed is not None:
+        after_timed()
+    med = 0.0
+    if median:
+        evs = [hipevent.timing_event() for _ in range(steps + 1)]
+        evs[0].record()
+        for i in range(steps):
+            tr.train_step(*batch)
+            evs[i + 1].record()
+        sync_all(world)
+        med = float(np.median([evs[i].elapsed_time(evs[i + 1]) for i in range(steps)]))
+    el = torch.tensor([max(wall, gpu_s), med], dtype=torch.float64, device="cuda")
     if world > 1:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
-    return float(el[0].item()), float(el[1].item()), probe_ms, launches
+    return float(el[0].item()), float(el[1].item()) if median else None, probe_ms, launches
 
 
 def time_graph_steps(tr, batch, steps, warmup):
@@ -595,6 +609,45 @@ def health(out, flags, identical=None):
     return 1 if flags or identical is False else 0
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000     # --dump-outputs writes at most this much in all
+NPY_HEADER_BYTES = 256                  # allowance per file for the .npy header (128 today)
+# Untimed steps a plain run takes before --warmup, as many as the --full run's per-kernel pass
+# (find_dominant_kernel: 20 + 5 per kernel id): the clock is still ramping over the first
+# steps after start, and 20 timed steps after 2 + 5 untimed ones read 3 % slower (1.72 against
+# 1.67 ms) than the same steps after this many, about 0.2 s at the default size.
+CLOCK_WARM_STEPS = 120
+
+
+def snapshot_outputs(tr):
+    """--dump-outputs: device copies of what the timed path leaves its caller after a step —
+    the flat parameter vector, the optimizer's slots (Adam's m and v) and the step's eight
+    scalars (_lib.SCALAR_NAMES: cost, the loss terms, ..., active_relus).  train_step()
+    itself returns nothing; these are the tensors run_step() and a checkpoint read."""
+    opt = tr.optimizer
+    inner = opt._opt if hasattr(opt, "_opt") else opt
+    snap = {"params": tr.engine.params.clone(), "scalars": tr.engine.scalars.clone()}
+    for i, t in enumerate(inner.slots or []):
+        snap["slot%d" % i] = t.clone()
+    return snap
+
+
+def write_outputs(path, snap, limit=DUMP_LIMIT_BYTES):
+    """Write each tensor of `snap` as `path`/<name>.npy (float32 as it is, everything else as
+    float64).  An array over its share of `limit` is cut to a fixed sample of its flattened
+    elements (sorted indices from numpy's RandomState(0), the same in every run)."""
+    os.makedirs(path, exist_ok=True)
+    share = limit // max(len(snap), 1) - NPY_HEADER_BYTES
+    for name, t in sorted(snap.items()):
+        a = t.detach().cpu().numpy()
+        if a.dtype != np.float32:
+            a = a.astype(np.float64)
+        if a.nbytes > share:
+            keep = np.sort(np.random.RandomState(0).choice(a.size, share // a.itemsize,
+                                                           replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 ARITH = ("fp32-class products on 16-bit MFMA with fp32 accumulation: conv0 u8 x fp16 hi/lo "
          "(2 products), conv0..conv3 power-of-two-scaled fp16 hi/lo (3 products: hi*hi + hi*lo "
          "+ lo*hi), fc1 / heads weight gradient bf16 hi/mid/lo (6 products); per product ~2^-20 "
@@ -602,11 +655,19 @@ ARITH = ("fp32-class products on 16-bit MFMA with fp32 accumulation: conv0 u8 x 
          "image's / tensor's max |x| lose fp16 bits (DESIGN.md §3.1)")
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: per-kernel probes, roofline and ceiling, "
+                         "the per-step median, the exchange report (N>1 / --sync-path), the "
+                         "predictor overlap, the B=32 configuration and the CPU baseline "
+                         "(each can be left out again with its --no-... option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them left (parameters, "
+                         "optimizer slots, the step's scalars) as DIR/<name>.npy")
     # the roofline probe brackets the dominant launch of one timed step in this many (1: every
     # step; one in 5 measured the same step time, r06s)
     ap.add_argument("--probe-every", type=int, default=1)
@@ -632,7 +693,14 @@ def main():
     ap.add_argument("--occupy-us", type=float, default=50.0,
                     help="the short occupancy window (microseconds) of --occupy")
     ap.add_argument("--exchange-selftest", action="store_true", help=argparse.SUPPRESS)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.occupy and not args.full:
+        ap.error("--occupy fills the exchange report, which needs --full")
+    return args
+
+
+def main():
+    args = parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # launcher only: no GPU call in this process (the children set their devices)
@@ -668,24 +736,38 @@ def run_rank(args, world, rank, local):
     for _ in range(2):
         tr.train_step(*batch)
     sync_all(world)
-    dom, per_kernel = find_dominant_kernel(tr, batch)
-    ceiling = step_ceiling(tr.engine, per_kernel, B, C, F)
+    # a plain run times the steps and nothing else: no per-kernel pass, and no probe inside the
+    # timed steps unless BA3C_BENCH_PROBE names a kernel
+    dom, per_kernel, ceiling = None, None, None
+    if args.full:
+        dom, per_kernel = find_dominant_kernel(tr, batch)
+        ceiling = step_ceiling(tr.engine, per_kernel, B, C, F)
+    else:
+        for _ in range(CLOCK_WARM_STEPS):
+            tr.train_step(*batch)
     # A/B runs: time a named kernel over the timed steps instead of the dominant one
     dom = os.environ.get("BA3C_BENCH_PROBE", dom)
     sync_all(world)
+    before_warmup = tr.global_step    # untimed steps so far (the line's steps_before_warmup)
 
+    snap = {}
+    take = (lambda: snap.update(snapshot_outputs(tr))) if args.dump_outputs else None
     elapsed, med_ms, probe_ms, launches = time_steps(tr, batch, args.steps, args.warmup, world,
-                                                     probe=dom, probe_every=args.probe_every)
+                                                     probe=dom, probe_every=args.probe_every,
+                                                     median=args.full, after_timed=take)
     flags = tr.engine.device_errors()     # synchronises; after the timed region
     identical = None
     if world > 1:
         inner = tr.optimizer._opt if hasattr(tr.optimizer, "_opt") else tr.optimizer
         identical = replicas_identical([tr.engine.params] + list(inner.slots or []))
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, snap)
 
     value = world * B * args.steps / elapsed
     ms_step = elapsed / args.steps * 1000.0
     macs = layer_macs(C, F)
-    dom_flops, dom_jobs = probe_flops(dom, tr.engine.kernel_merged(dom), macs, B)
+    dom_flops, dom_jobs = (probe_flops(dom, tr.engine.kernel_merged(dom), macs, B)
+                           if dom is not None else (None, []))
     # a multi-job launch's ceiling: its total FLOPs over the time every job would take at the
     # peak of its own arithmetic path
     job_peak_s = sum(2.0 * macs[KERNEL_LAYER[k]] * B / (kernel_peak(tr.engine.kernel_split(k)) * 1e12)
@@ -715,12 +797,10 @@ def run_rank(args, world, rank, local):
                     "2516.6 TF dense 16-bit MFMA / %d split products" % split if len(dom_jobs) == 1 else
                     "total FLOPs / sum over jobs of (job FLOPs / 2516.6 TF x its split products)")}
     step_tflops = train_step_flops(B, C, F, A) / (ms_step / 1000.0) / 1e12
-    ceiling["step_frac_of_mixed_path_ceiling"] = round(ceiling["ideal_ms"] / ms_step, 4)
 
     out = {"metric": METRIC, "value": round(value, 1), "unit": "samples/s", "n_gpus": world,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 4),
-           "ms_per_step_median": round(med_ms, 4),
-           "value_median": round(world * B / (med_ms / 1000.0), 1),
+           "steps_before_warmup": before_warmup, "full": bool(args.full),
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
            "arith": ARITH,
            "data": "synthetic uint8 84x84x4 frames, random actions/returns, weights from the "
@@ -733,21 +813,28 @@ def run_rank(args, world, rank, local):
                       "step_path": "bucketed sync (phase-split backward, per-bucket clip, "
                                    "unfused update)" if sync else "fused single replica",
                       "backup_workers": 0},
-           "step_tflops_algorithmic": round(step_tflops, 2),
-           "ceiling": ceiling,
-           "roofline": roof,
-           "probe": {"kernel": dom, "avg_launch_ms": round(avg_ms, 4), "launches": launches,
-                     "every": args.probe_every},
-           "kernel_ms_per_step": {k: round(v, 4) for k, v in per_kernel.items()}}
+           "step_tflops_algorithmic": round(step_tflops, 2)}
+    if dom is not None:
+        out["roofline"] = roof
+        out["probe"] = {"kernel": dom, "avg_launch_ms": round(avg_ms, 4), "launches": launches,
+                        "every": args.probe_every}
+    if args.full:
+        ceiling["step_frac_of_mixed_path_ceiling"] = round(ceiling["ideal_ms"] / ms_step, 4)
+        out.update({"ms_per_step_median": round(med_ms, 4),
+                    "value_median": round(world * B / (med_ms / 1000.0), 1),
+                    "ceiling": ceiling,
+                    "kernel_ms_per_step": {k: round(v, 4) for k, v in per_kernel.items()}})
+    if args.dump_outputs:
+        out["dumped_outputs"] = sorted(snap)
 
     rc = health(out, flags, identical)
-    if sync:
+    if args.full and sync:
         ks = [int(k) for k in args.occupy.split(",") if k.strip()]
         out["exchange"] = exchange_report(tr, batch, max(args.steps // 3, 5), world, ks,
                                           args.occupy_us)
-    if not args.no_overlap:
+    if args.full and not args.no_overlap:
         out["overlap"] = overlap_bench(tr, batch, args.predict_batch, 10, world)
-    if not args.no_b32:
+    if args.full and not args.no_b32:
         close_exchange(tr)
         del tr
         tr = None
@@ -767,7 +854,7 @@ def run_rank(args, world, rank, local):
             out["b32"]["device_errors"] = int(f32)
             rc = 1
         tr = tr32
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(F, S, A, args.cpu_seconds)
         out["gpu_vs_cpu"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
     if rank == 0:

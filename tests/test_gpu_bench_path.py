@@ -292,3 +292,96 @@ def test_probe_every_brackets_one_launch_in_n():
 def _lib_check_every(eng, n):
     from ba3c_amd import _lib
     _lib.check(eng.lib.ba3c_probe_every(eng.h, n))
+
+
+def _bench_line(capsys, argv):
+    import json
+    import bench
+    capsys.readouterr()
+    assert bench.run_rank(bench.parse_args(argv), 1, 0, 0) == 0
+    lines = [l for l in capsys.readouterr().out.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, lines
+    return json.loads(lines[0])
+
+
+def test_plain_bench_run_times_the_steps_and_dumps_the_last_one(capsys, tmp_path):
+    """A plain bench.py run (no --full) at configs[1]: the line carries the headline figure
+    and none of the extra legs, --steps is the number of timed steps, and --dump-outputs writes
+    the state the last timed step left — bit-identical between two runs with the same
+    arguments, and equal to the run's untimed steps (2 at start-up, bench.CLOCK_WARM_STEPS,
+    the warmup) + `steps` steps of the same trainer."""
+    import bench
+    cfg = ["--gpus", "1", "--batch", "32", "--fc_neurons", "128", "--fc_splits", "4"]
+    argv = cfg + ["--steps", "3", "--warmup", "1"]
+    d = _bench_line(capsys, argv + ["--dump-outputs", str(tmp_path / "a")])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["full"] is False
+    assert d["steps_before_warmup"] == 2 + bench.CLOCK_WARM_STEPS
+    assert d["unit"] == "samples/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["metric"] == bench.METRIC and d["device_errors"] == 0
+    assert d["ms_per_step"] > 0
+    assert abs(d["value"] - 32 / (d["ms_per_step"] / 1000.0)) <= 1e-3 * d["value"]
+    for k in ("b32", "cpu_baseline", "overlap", "exchange", "kernel_ms_per_step", "ceiling",
+              "roofline", "probe", "ms_per_step_median"):
+        assert k not in d, k
+    assert d["dumped_outputs"] == ["params", "scalars", "slot0", "slot1"]
+    _bench_line(capsys, argv + ["--dump-outputs", str(tmp_path / "b")])
+    got = {}
+    for name in d["dumped_outputs"]:
+        a = np.load(str(tmp_path / "a" / (name + ".npy")))
+        assert a.dtype == (np.float64 if name == "scalars" else np.float32), (name, a.dtype)
+        assert np.isfinite(a).all(), name
+        assert np.array_equal(a, np.load(str(tmp_path / "b" / (name + ".npy")))), name
+        got[name] = a
+    tr, batch = bench.build_trainer(32, 128, 4, 4, 1, seed=0)
+    for _ in range(2 + bench.CLOCK_WARM_STEPS + 1 + 3):
+        tr.train_step(*batch)
+    torch.cuda.synchronize()
+    assert np.array_equal(got["params"], tr.engine.params.cpu().numpy())
+    assert np.array_equal(got["scalars"], tr.engine.scalars.cpu().numpy())
+    assert np.array_equal(got["slot0"], tr.optimizer.slots[0].cpu().numpy())
+    assert got["params"].size == tr.engine.params.numel() and got["scalars"].shape == (8,)
+
+
+def test_full_bench_run_keeps_every_leg_and_dumps_before_its_extra_steps(capsys, tmp_path,
+                                                                        monkeypatch):
+    """--full at configs[1] (CPU baseline left out: it times B=2048 on the host): the legs a
+    plain run drops are all in the line, and the dump is the state right after the last timed
+    step — the steps the trainer had run when the snapshot was taken, replayed on a fresh
+    trainer, give the same arrays, although the per-step-median pass and the other legs step
+    the model further before the files are written."""
+    import bench
+    from ba3c_amd.trainer import Ba3cTrainer
+    count = {"steps": 0, "at_snapshot": None}
+    step, snapshot = Ba3cTrainer.train_step, bench.snapshot_outputs
+
+    def counted_step(self, *a):
+        count["steps"] += 1
+        return step(self, *a)
+
+    def counted_snapshot(tr):
+        count["at_snapshot"] = count["steps"]
+        return snapshot(tr)
+
+    monkeypatch.setattr(Ba3cTrainer, "train_step", counted_step)
+    monkeypatch.setattr(bench, "snapshot_outputs", counted_snapshot)
+    argv = ["--gpus", "1", "--batch", "32", "--fc_neurons", "128", "--fc_splits", "4",
+            "--steps", "3", "--warmup", "1", "--predict_batch", "64", "--no-cpu-baseline",
+            "--full", "--dump-outputs", str(tmp_path / "f")]
+    d = _bench_line(capsys, argv)
+    monkeypatch.undo()
+    assert d["full"] is True and d["steps"] == 3
+    for k in ("b32", "overlap", "kernel_ms_per_step", "ceiling", "roofline", "probe",
+              "ms_per_step_median", "value_median"):
+        assert k in d, k
+    assert d["b32"]["ms_per_step"] > 0 and d["b32"]["ms_per_step_graph"] > 0
+    assert d["probe"]["launches"] > 0 and d["probe"]["launches"] % 3 == 0
+    n = count["at_snapshot"]
+    assert n is not None and n == d["steps_before_warmup"] + 1 + 3 and n < count["steps"]
+    tr, batch = bench.build_trainer(32, 128, 4, 4, 1, seed=0)
+    for _ in range(n):
+        tr.train_step(*batch)
+    torch.cuda.synchronize()
+    for name, want in (("params", tr.engine.params), ("scalars", tr.engine.scalars),
+                       ("slot0", tr.optimizer.slots[0]), ("slot1", tr.optimizer.slots[1])):
+        got = np.load(str(tmp_path / "f" / (name + ".npy")))
+        assert np.array_equal(got, want.cpu().numpy()), name

@@ -389,3 +389,40 @@ def test_bench_health_flags_make_the_run_fail():
     assert out["replicas_identical"] is True
     out = {}
     assert bench.health(out, 0, False) == 1 and out["replicas_identical"] is False
+
+
+def test_bench_write_outputs_formats_and_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: float32 tensors are written as they are, everything else as
+    float64; an array over its share of the size limit is cut to the same sorted sample of its
+    elements in every run, and the whole dump stays within the limit."""
+    import bench
+    snap = {"params": torch.arange(5000, dtype=torch.float32) * 0.5,
+            "scalars": torch.arange(8, dtype=torch.float64) - 3.0,
+            "count": torch.arange(7, dtype=torch.int64)}
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    bench.write_outputs(a, snap)
+    got = {f[:-4]: np.load(os.path.join(a, f)) for f in sorted(os.listdir(a))}
+    assert sorted(got) == ["count", "params", "scalars"]
+    assert got["params"].dtype == np.float32 and got["scalars"].dtype == np.float64
+    assert got["count"].dtype == np.float64
+    for k, t in snap.items():
+        np.testing.assert_array_equal(got[k], t.numpy())
+    limit = 3 * 1200         # a share of 1200 bytes less the header allowance: 236 floats
+    keep = (1200 - bench.NPY_HEADER_BYTES) // 4
+    bench.write_outputs(a, snap, limit=limit)
+    bench.write_outputs(b, snap, limit=limit)
+    pa, pb = np.load(os.path.join(a, "params.npy")), np.load(os.path.join(b, "params.npy"))
+    assert pa.shape == (keep,) and np.array_equal(pa, pb)
+    assert np.all(np.diff(pa) > 0) and np.all(np.isin(pa, snap["params"].numpy()))
+    np.testing.assert_array_equal(np.load(os.path.join(a, "scalars.npy")), snap["scalars"].numpy())
+    assert sum(os.path.getsize(os.path.join(a, f)) for f in os.listdir(a)) <= limit   # headers too
+
+
+def test_bench_occupy_needs_full():
+    """--occupy fills the exchange report, which only a --full run produces: refused without."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--sync-path",
+                        "--occupy", "16"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--full" in r.stderr
