@@ -100,6 +100,8 @@ def load():
         "ba3c_nstep_returns": (i32, [P, P, P, P, P, P, i32, i32, ctypes.c_double, P, P, P, P, P]),
         "ba3c_gather_rows": (i32, [P, P, P, i32, i64, P]),
         "ba3c_history_push": (i32, [P, P, P, P, i32, i32, i32, i32]),
+        "ba3c_breakout_step": (i32, [P, P, P, i32, i32, P, P, P, P, P]),
+        "ba3c_breakout_render": (i32, [P, P, i32, P, P]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("BA3C_LIB") and name in AB_OPTIONAL and not hasattr(lib, name):

@@ -61,15 +61,22 @@ class ActorLearner(object):
     predictor: the reference's towerp0 reads the same variables, train.py:355-362)."""
 
     def __init__(self, trainer, n_envs, batch_size, seed=0, rs=None, on_train_step=None,
-                 dummy_predictor=False):
-        """on_train_step(trainer): called after every learner step (callbacks / metrics);
+                 dummy_predictor=False, env=None):
+        """env: the vector of simulators (None: SyntheticAtari, as before); an env with
+        `step_into(actions, hist)` (ba3c_amd.breakout.BreakoutVec) is stepped through it, the
+        frame-history push fused into the env's launch.
+        on_train_step(trainer): called after every learner step (callbacks / metrics);
         dummy_predictor: --dummy_predictor 1 (predict/base.py:94-105) — uniform policy and
         U(0,1) values instead of the network forward."""
         eng = trainer.engine
         assert eng.channels == 4, "synthetic loop is grayscale x FRAME_HISTORY=4"
         self.trainer = trainer
         self.engine = eng
-        self.env = SyntheticAtari(n_envs, eng.num_actions, seed=seed, device=eng.device)
+        if env is None:
+            env = SyntheticAtari(n_envs, eng.num_actions, seed=seed, device=eng.device)
+        assert env.E == n_envs and env.A <= eng.num_actions
+        self.env = env
+        self._fused = hasattr(env, "step_into")
         self.hist = FrameHistory(n_envs, hist_len=4, channels=1, device=eng.device)
         self.buf = RolloutBuffer(n_envs, channels=4, device=eng.device)
         self.queue = BatchQueue(batch_size)
@@ -98,8 +105,11 @@ class ActorLearner(object):
         u = torch.from_numpy(self.rs.random_sample(self.env.E)).to(eng.device)
         actions, flag = eng.sample(probsT, u)
         self.buf.on_state(state, actions, value)
-        frames, reward, over = self.env.step(actions)
-        self.hist.push(frames, over)
+        if self._fused:
+            reward, over = self.env.step_into(actions, self.hist)
+        else:
+            frames, reward, over = self.env.step(actions)
+            self.hist.push(frames, over)
         self.queue.put(self.buf.on_reward(reward, over))
         while True:
             b = self.queue.get()

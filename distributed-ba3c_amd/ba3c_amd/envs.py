@@ -243,11 +243,139 @@ class SyntheticAtariPlayer(RLEnvironment):
         return self.space
 
 
+class BreakoutPlayer(RLEnvironment):
+    """GridBreakout (ba3c_amd.breakout holds the rules and constants) as one host player, for
+    the simulator processes: the same integer rules as scalar Python ints.  Auto-restarts like
+    GymEnv and records the episode 'score' stat in finish_episode.  `limit` (None: none) ends
+    an episode after that many steps; get_player leaves that to LimitLengthPlayer.
+    `last_events` names what the last action() met, from: wall, ceiling, brick7, brick4,
+    brick1, paddle, lost, over_lives, over_clear, over_limit."""
+
+    def __init__(self, idx=0, num_actions=4, seed=0, limit=None):
+        super(BreakoutPlayer, self).__init__()
+        from . import breakout as K
+        self.K = K
+        self.idx = int(idx)
+        self.limit = limit
+        self.rng = (int(seed) * 1000 + self.idx) % (1 << 32)
+        self.space = DiscreteActionSpace(int(num_actions), seed=seed + 1)
+        self.last_events = set()
+        self.last_ep_score = None
+        self.restart_episode()
+
+    def restart_episode(self):
+        K = self.K
+        self.px = K.PX_START
+        self.bx = self.by = self.vx = self.vy = self.in_play = 0
+        self.lives = K.LIVES
+        self.score = 0
+        self.t = 0
+        self.bricks = [K.FULL_ROW] * K.ROWS
+
+    def finish_episode(self):
+        self.stats["score"].append(self.score)
+
+    def game_row(self):
+        """The episode state as the device's int32 row (breakout.py layout)."""
+        rng = self.rng - (1 << 32) if self.rng >= (1 << 31) else self.rng
+        return [self.px, self.bx, self.by, self.vx, self.vy, self.in_play, self.lives, self.score,
+                self.t, rng] + list(self.bricks)
+
+    def current_state(self):
+        K = self.K
+        f = np.zeros((K.H, K.W), np.uint8)
+        for i in range(self.lives):
+            f[K.LIVES_Y:K.LIVES_Y + 2, 4 * i:4 * i + 2] = K.LIVES_SHADE
+        for r in range(K.ROWS):
+            y0 = K.BRICK_Y0 + K.BRICK_H * r
+            for c in range(K.COLS):
+                if (self.bricks[r] >> c) & 1:
+                    f[y0:y0 + K.BRICK_H, K.BRICK_W * c:K.BRICK_W * (c + 1)] = K.SHADE[r]
+        f[K.PADDLE_Y:K.PADDLE_Y + K.PADDLE_H, self.px:self.px + K.PADDLE_W] = 255
+        if self.in_play:
+            f[self.by:self.by + K.BALL, self.bx:self.bx + K.BALL] = 255
+        return f
+
+    def action(self, act):
+        K = self.K
+        ev = set()
+        act = int(act)
+        reward = 0
+        if act == K.RIGHT:
+            self.px = min(self.px + K.PADDLE_STEP, K.PX_MAX)
+        elif act == K.LEFT:
+            self.px = max(self.px - K.PADDLE_STEP, 0)
+        if not self.in_play:
+            if act == K.FIRE:
+                self.rng = (self.rng * K.LCG_A + K.LCG_C) % (1 << 32)
+                self.bx = 8 + ((self.rng >> 16) % 68)
+                self.by = 40
+                self.vx = 1 if (self.rng >> 8) & 1 else -1
+                self.vy = 2
+                self.in_play = 1
+        else:
+            nx, ny = self.bx + self.vx, self.by + self.vy
+            if nx < 0:
+                nx, self.vx = -nx, -self.vx
+                ev.add("wall")
+            elif nx > 82:
+                nx, self.vx = 164 - nx, -self.vx
+                ev.add("wall")
+            if ny < 0:
+                ny, self.vy = -ny, -self.vy
+                ev.add("ceiling")
+            for cx, cy in ((nx, ny), (nx + 1, ny), (nx, ny + 1), (nx + 1, ny + 1)):
+                if 18 <= cy < 36:
+                    r, c = (cy - 18) // 3, cx // 6
+                    if (self.bricks[r] >> c) & 1:
+                        self.bricks[r] &= ~(1 << c)
+                        reward += K.VAL[r]
+                        self.vy = -self.vy
+                        ny = self.by
+                        ev.add("brick%d" % K.VAL[r])
+                        break
+            if (self.vy > 0 and self.by + 1 < 78 and ny + 1 >= 78 and nx + 1 >= self.px
+                    and nx <= self.px + 11):
+                ny, self.vy = 76, -2
+                d = nx + 1 - (self.px + 6)
+                self.vx = -2 if d < -3 else -1 if d < 0 else 1 if d < 3 else 2
+                ev.add("paddle")
+            self.bx, self.by = nx, ny
+            if self.by > 82:
+                self.in_play = 0
+                self.lives -= 1
+                ev.add("lost")
+        self.score += reward
+        self.t += 1
+        if self.lives == 0:
+            ev.add("over_lives")
+        if not any(self.bricks):
+            ev.add("over_clear")
+        if self.limit is not None and self.t >= self.limit:
+            ev.add("over_limit")
+        over = bool(ev & {"over_lives", "over_clear", "over_limit"})
+        if over:
+            self.last_ep_score = self.score
+            self.finish_episode()
+            self.restart_episode()
+        self.last_events = ev
+        return float(reward), over
+
+    def get_action_space(self):
+        return self.space
+
+
 def get_player(idx=0, num_actions=4, seed=0, train=False, frame_history=FRAME_HISTORY,
-               limit=40000):
-    """OpenAIGym/train.py:113-128 with the synthetic game: history of `frame_history` frames,
-    PreventStuckPlayer(30, 1) for evaluation players, LimitLengthPlayer(40000)."""
-    pl = SyntheticAtariPlayer(idx, num_actions, seed)
+               limit=40000, game="synthetic"):
+    """OpenAIGym/train.py:113-128 with the synthetic game (or game="breakout": GridBreakout):
+    history of `frame_history` frames, PreventStuckPlayer(30, 1) for evaluation players,
+    LimitLengthPlayer(40000)."""
+    if game == "breakout":
+        pl = BreakoutPlayer(idx, num_actions, seed)
+    elif game == "synthetic":
+        pl = SyntheticAtariPlayer(idx, num_actions, seed)
+    else:
+        raise ValueError("unknown game %r (synthetic, breakout)" % (game,))
     pl = HistoryFramePlayer(pl, frame_history)
     if not train:
         pl = PreventStuckPlayer(pl, 30, 1)

@@ -5,6 +5,9 @@ flags are accepted and ignored."""
 import argparse
 
 
+GRID_BREAKOUT = "GridBreakout-v0"
+
+
 def string_to_bool(s):        # parse.py:5-6
     return str(s).lower() == "true"
 
@@ -27,7 +30,9 @@ def build_parser():
     p.add_argument("--beta1", type=float, default=0.9)
     p.add_argument("--beta2", type=float, default=0.999)
     p.add_argument("--adam_debug", action="store_true")
-    p.add_argument("--environment", "-e", "--env", dest="environment", default="Breakout-v0")
+    p.add_argument("--environment", "-e", "--env", dest="environment", default="Breakout-v0",
+                   help="GridBreakout-v0: the on-device Breakout (ba3c_amd.breakout); any other "
+                        "name: the synthetic environment")
     p.add_argument("--channels", type=int, default=1)
     p.add_argument("--num_actions", type=int, default=4)
     p.add_argument("--predict_batch_size", type=int, default=16)
@@ -41,6 +46,9 @@ def build_parser():
     p.add_argument("--steps_per_epoch", type=int, default=250)
     p.add_argument("--max_epoch", type=int, default=1000)
     p.add_argument("--send_debug_every", type=int, default=100)
+    p.add_argument("--nr_eval", type=int, default=0,
+                   help="episodes the Evaluator plays every --steps_per_epoch learner steps on "
+                        "rank 0 (0: off; needs -e GridBreakout-v0)")
     p.add_argument("--dummy", type=int, default=0)
     p.add_argument("--dummy_predictor", type=int, default=0)
     p.add_argument("--models_dir", default="models")
@@ -64,11 +72,18 @@ def build_parser():
 def resolve(args):
     """Apply the reference's implicit rules: --use_normal_fc disables replace_with_conv
     (run_job.py:131); --adam_debug sets beta2 := beta1 (train.py:460-461); --use_sync needs
-    --ngrads (run_job.py:55-57)."""
+    --ngrads (run_job.py:55-57).  -e GridBreakout-v0 needs --channels 1 and --num_actions >= 4."""
     if args.replace_with_conv is None:
         args.replace_with_conv = not args.use_normal_fc
     if args.adam_debug:
         args.beta2 = args.beta1
     if args.use_sync and args.ngrads is None:
         raise SystemExit("if using SyncReplicasOptimizer you have to specify --ngrads argument")
+    if args.environment == GRID_BREAKOUT:
+        if args.channels != 1:
+            raise SystemExit("-e %s renders grayscale frames: it requires --channels 1" % GRID_BREAKOUT)
+        if args.num_actions < 4:
+            raise SystemExit("-e %s has 4 actions: it requires --num_actions >= 4" % GRID_BREAKOUT)
+    elif args.nr_eval:
+        raise SystemExit("--nr_eval needs a game to evaluate: pass -e %s" % GRID_BREAKOUT)
     return args

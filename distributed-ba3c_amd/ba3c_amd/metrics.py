@@ -66,6 +66,11 @@ class CsvChannels(object):
         fd.write("{},{}\n".format(x, y))
         fd.flush()
 
+    def write_scalar(self, name, value):
+        """trainer.write_scalar_summary(name, value) (the Evaluator's mean_score / max_score,
+        common.py:131-132) as one more channel."""
+        self._send(name, (time.time() - self.start) / 3600.0, value)
+
     def send(self, message):
         _, content = message
         x = (time.time() - self.start) / 3600.0

@@ -271,16 +271,19 @@ SimulatorProcess = SimulatorProcessStateExchange     # simulator.py:111-112
 
 
 class SyntheticSimulatorWorker(SimulatorProcess):
-    """MySimulatorWorker (train.py:134-136) over the synthetic game."""
+    """MySimulatorWorker (train.py:134-136) over the synthetic game, or over GridBreakout's
+    host player with game="breakout"."""
 
-    def __init__(self, idx, pipe_c2s, pipe_s2c, num_actions=4, seed=0):
+    def __init__(self, idx, pipe_c2s, pipe_s2c, num_actions=4, seed=0, game="synthetic"):
         super(SyntheticSimulatorWorker, self).__init__(idx, pipe_c2s, pipe_s2c)
         self.num_actions = num_actions
         self.seed = seed
+        self.game = game
 
     def _build_player(self):
         from .envs import get_player
-        return get_player(self.idx, self.num_actions, self.seed + self.idx, train=True)
+        return get_player(self.idx, self.num_actions, self.seed + self.idx, train=True,
+                          game=self.game)
 
 
 def client_index(identity):

@@ -5,8 +5,10 @@ Replaces run_job.py:13-148 -> distributed_tensorpack_mkl.sh -> OpenAIGym/train.p
 (`-o`, :582-597), SyncReplicasOptimizer for `--use_sync -g N` (:598-606, here an RCCL
 all-reduce over the node's GPUs), the trainer and the actor-learner loop (simulator master +
 predictor + BatchData, :520-534 — with the synthetic on-device environment, gym/ALE being
-absent), plus the DebugLogCallback metrics channels and PeriodicPerStepCallback(ModelSaver)
-(:608-630) and `--load` (SaverRestore, :706-707).
+absent, or with `-e GridBreakout-v0` the on-device Breakout of ba3c_amd.breakout and, for
+`--nr_eval N`, the Evaluator callback every --steps_per_epoch steps), plus the
+DebugLogCallback metrics channels and PeriodicPerStepCallback(ModelSaver) (:608-630) and
+`--load` (SaverRestore, :706-707).
 
 One process per GPU: launch N > 1 with
     torchrun --nproc-per-node N --master-addr 127.0.0.1 -m ba3c_amd.train --use_sync -g N ...
@@ -24,7 +26,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .flags import build_parser, resolve
+from .flags import GRID_BREAKOUT, build_parser, resolve
 
 
 def _free_port():
@@ -153,10 +155,17 @@ def _run(args, rank, world):
     client = CsvChannels(args.experiment_dir) if rank == 0 else None
     metrics = _Metrics(trainer, args.batch_size, args.send_debug_every, client)
 
+    evaluator = None
+    if args.nr_eval and rank == 0:
+        from .evaluate import Evaluator
+        evaluator = Evaluator(trainer.engine, args.nr_eval, client, seed=1000 + rank)
+
     def on_step(tr):
         metrics(tr)
         for cb in savers:
             cb.trigger_step(tr)
+        if evaluator is not None and tr.global_step % args.steps_per_epoch == 0:
+            evaluator()                                       # Evaluator._trigger_epoch
 
     max_steps = args.max_steps or args.steps_per_epoch * args.max_epoch
     t0 = time.time()
@@ -172,9 +181,13 @@ def _run(args, rank, world):
             on_step(trainer)
         sim_steps = 0
     else:
+        env = None
+        if args.environment == GRID_BREAKOUT:
+            from .breakout import BreakoutVec
+            env = BreakoutVec(args.simulator_procs, seed=rank, device=trainer.engine.device)
         al = ActorLearner(trainer, n_envs=args.simulator_procs, batch_size=args.batch_size,
                           seed=rank, rs=np.random.RandomState(rank), on_train_step=on_step,
-                          dummy_predictor=bool(args.dummy_predictor))
+                          dummy_predictor=bool(args.dummy_predictor), env=env)
         while trainer.global_step < max_steps:
             al.iterate()
         sim_steps = al.steps
@@ -187,6 +200,8 @@ def _run(args, rank, world):
            "simulator_steps": sim_steps, "samples_per_s": round(
                trainer.global_step * args.batch_size * world / max(wall, 1e-9), 1),
            "last": metrics.last}
+    if evaluator is not None:
+        out["eval"] = evaluator.history
     if rank == 0:
         print(json.dumps(out), flush=True)
     return out

@@ -314,6 +314,39 @@ int ba3c_gather_rows(void* stream, const void* rows, const int32_t* idx, int32_t
 int ba3c_history_push(void* stream, const uint8_t* frame, uint8_t* state, const uint8_t* is_over,
                       int32_t n_envs, int32_t pixels, int32_t hist_len, int32_t channels);
 
+/* ---- GridBreakout: an on-device game (stands in for RL/gymenv.py + the 84x84 resize) ----- */
+
+/* A small integer-only Breakout for n_envs simulators; ba3c_amd/breakout.py states the rules
+ * (constants, step_numpy, render_numpy) and is the oracle of these entry points.  All game
+ * state is int32, one 64-byte (16-byte aligned) row per simulator:
+ *   game[e] = [px, bx, by, vx, vy, in_play, lives, score, t, rng, b0, b1, b2, b3, b4, b5]
+ * px: paddle left edge (0..72); (bx, by): the 2x2 ball's top-left; (vx, vy): its velocity;
+ * in_play: 0 until FIRE serves; lives: 5 per episode; score / t: reward sum and steps of the
+ * episode; rng: the serve LCG's uint32 bits; b_r: 14-bit mask of row r's live bricks.
+ *
+ * ba3c_breakout_step applies action[e] (0 NOOP, 1 FIRE, 2 RIGHT, 3 LEFT, anything else NOOP;
+ * the value is compared, never used as an index) to every simulator and writes reward[e]
+ * (float64, as gym returns it), over[e], and ep_score[e] ONLY where over[e] (the finished
+ * episode's score; the row is then already reset, GymEnv's auto-restart).  An episode ends
+ * when lives reach 0, no brick is left, or t >= limit (LimitLengthPlayer).  The frame after
+ * the step (on over: the new episode's first) is rendered to frame[e] ([84*84] uint8, may be
+ * NULL) and, when state is given ([84*84][4] uint8, may be NULL), pushed into the H=4, c=1
+ * frame history in the same launch: per pixel dword (old >> 8) | (pix << 24), old = 0 where
+ * over[e] — bit-identical to ba3c_history_push(frame, state, over).
+ *
+ * ba3c_breakout_render renders the current rows without stepping; with state it starts the
+ * history (zeros + frame).
+ *
+ * Both validate their arguments on the host (null game / action / outputs, n_envs < 1,
+ * limit < 1, misaligned game / state / frame -> BA3C_ERR_INVALID) before touching the
+ * device, never synchronise and never allocate.  One launch, one 256-thread workgroup per
+ * simulator. */
+int ba3c_breakout_step(void* stream, int32_t* game, const int64_t* action, int32_t n_envs,
+                       int32_t limit, double* reward, uint8_t* over, int32_t* ep_score,
+                       uint8_t* frame, uint8_t* state);
+int ba3c_breakout_render(void* stream, const int32_t* game, int32_t n_envs, uint8_t* frame,
+                         uint8_t* state);
+
 #ifdef __cplusplus
 }
 #endif
