@@ -192,8 +192,8 @@ class Ba3cEngine(object):
         _lib.check(self.lib.ba3c_launch_held(self.h, st))
 
     def set_phase2_event(self, event):
-        """Record `event` (a hipevent.HipEvent, or None) after conv3's gradient launches of every
-        later phase-2 pass."""
+        """Record `event` (a hipevent.HipEvent, or None) in every later phase-2 pass after conv3's
+        input-gradient launch, and its weight gradient's unless BA3C_C3W_RIDE is set."""
         _lib.check(self.lib.ba3c_set_phase2_event(self.h, event._ev if event is not None else None))
 
     def clip_grads(self, grads=None):

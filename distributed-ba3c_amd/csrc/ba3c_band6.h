@@ -16,8 +16,8 @@
 // bank-conflict search (affine, so every MFMA operand read is a ds_read_b128 at a
 // compile-time immediate offset from one per-m-block base).  K-step t = (tap, 32-channel
 // chunk); lane group q supplies channels 8q..8q+7, so a lane's A fragment of one split is
-// 16 contiguous bytes.  B (weights) comes from a per-step [split][N][K] bf16 copy (L2
-// resident) through a register ring.  Pooled epilogues are unchanged: rows are ordered
+// 16 contiguous bytes.  B (weights) comes from a per-step split copy in MFMA fragment order
+// (wprep6_body, L2 resident) through a register ring.  Pooled epilogues are unchanged: rows are ordered
 // (window, sub) so a lane's 4 accumulator rows are one 2x2 window (16x16 C layout).
 #pragma once
 #include "ba3c_split.h"
@@ -86,7 +86,8 @@ struct Band6 {
 struct Band6Args {
   const float* src;        // SRC 0: input map [B,HS,WS,CIN];  SRC 1: dP [B,UPH,UPW,CIN]
   const uint8_t* code;     // SRC 1: argmax codes of dP
-  const uint16_t* wt6;     // [NS][COUT][KH*KW*CIN] 16-bit splits (prepared per step)
+  const uint16_t* wt6;     // [NS] planes of COUT*KH*KW*CIN 16-bit splits in MFMA fragment order
+                           // (prepared per step, wprep6_body)
   float* out;              // POOL: pooled [B,HO/2,WO/2,COUT]; else [B,HO,WO,COUT]
   uint8_t* out_code;       // POOL: argmax codes (may be null: predictor)
   unsigned long long* relu_count;
@@ -191,15 +192,12 @@ struct Band6Ops {
 #pragma unroll
     for (int sp = 0; sp < L::NS; ++sp) *reinterpret_cast<uint2*>(p + sp * L::SPB) = make_uint2(s0[sp], s1[sp]);
   }
-#ifndef BA3C_UNPOOL_STAGE
-#define BA3C_UNPOOL_STAGE 1   // 0: A/B build with the per-pixel staging (store1) everywhere
-#endif
   // Whole-map input-gradient bands (conv2's): the zero-padded un-pooled dY staged from the
   // POOLED map, each (pooled pixel, 4 channels) loaded and split once and written to its 2x2
   // window with per-channel masks (mask16_eq0 on the codes as 16-bit halves); store1 instead
   // loads and splits every staged float4 (4 loads + 4 splits per pooled element, 3 of zeros).
   // The padding cells are zeroed in phase 0 and never written again.  Same LDS image bit for bit.
-  static constexpr bool UPSTAGE = BA3C_UNPOOL_STAGE && G::SRC == 1 && L::NS == 2 && G::NBANDS == 1 &&
+  static constexpr bool UPSTAGE = G::SRC == 1 && L::NS == 2 && G::NBANDS == 1 &&
                                   G::UHO == 2 * G::UPH && G::UWO == 2 * G::UPW &&
                                   G::UHO + 2 * G::PADY == G::HS && G::UWO + 2 * G::PADX == G::WS &&
                                   G::PADY % 2 == 0 && G::PADX % 2 == 0;
@@ -303,15 +301,12 @@ struct Band6Ops {
     // contiguous.  The offset goes through an empty asm so a persistent caller's band loop
     // cannot hoist the (band-invariant) weight loads of all k-steps out of the loop into
     // registers.
-#ifndef BA3C_WFRAG
-#define BA3C_WFRAG 1          // 0: A/B build with the plain [s][COUT][KDIM] weight order
-#endif
-    int woff = BA3C_WFRAG ? nb * 512 + lane * 8 : col * G::KDIM + 8 * lq;
+    int woff = nb * 512 + lane * 8;
     asm volatile("" : "+v"(woff));
     const uint16_t* wrow = a.wt6 + woff;
     constexpr size_t WSPLIT = (size_t)G::COUT * G::KDIM;
     // fragment offset (16-bit units) of K index k0 (a multiple of 32)
-    auto kfrag = [](int k0) { return BA3C_WFRAG ? (k0 / 32) * G::NB * 512 : k0; };
+    auto kfrag = [](int k0) { return (k0 / 32) * G::NB * 512; };
     // K index (tap, channel) of k-step t of a phase, relative to the phase's first channel
     auto koff = [&](int t) { return kfrag((t / L::K32) * G::CIN + (t % L::K32) * 32); };
 
@@ -345,13 +340,11 @@ struct Band6Ops {
 #pragma unroll
       for (int j = 0; j < MCH; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-#ifndef BA3C_B6_PRIO
-#define BA3C_B6_PRIO 1        // the MFMA main loop at wave priority 1, the staging at 0 (r05 A/B: conv1 fwd -1 %, dgrad -2 %)
-#endif
 #pragma unroll 1
       for (int ph = 0; ph < L::NPH; ++ph) {
         if constexpr (L::NPH > 1) stage_phase(ph);
-        if (BA3C_B6_PRIO) __builtin_amdgcn_s_setprio(1);
+        // the MFMA main loop at wave priority 1, the staging at 0 (r05 A/B: conv1 fwd -1 %, dgrad -2 %)
+        __builtin_amdgcn_s_setprio(1);
         const uint16_t* wph = wrow + kfrag(ph * L::KPH);
         constexpr int LA = 3;
         uint4 bring[LA + 1][L::NS];
@@ -378,10 +371,7 @@ struct Band6Ops {
         if constexpr (L::DBUF) read_a(0, avb[0]);
 #pragma unroll
         for (int t = 0; t < L::NT; ++t) {
-#ifndef BA3C_DIAG_NOB
-#define BA3C_DIAG_NOB 0       // diagnostics only: B fragments of the first k-steps reused
-#endif
-          if (!BA3C_DIAG_NOB && t + LA < L::NT) {
+          if (t + LA < L::NT) {
 #pragma unroll
             for (int s = 0; s < L::NS; ++s)
               bring[(t + LA) % (LA + 1)][s] = *reinterpret_cast<const uint4*>(wph + s * WSPLIT + koff(t + LA));
@@ -390,20 +380,17 @@ struct Band6Ops {
             if (t + 1 < L::NT) read_a(t + 1, avb[(t + 1) & 1]);
             __builtin_amdgcn_sched_barrier(0);                // keep those reads ahead of the MFMAs
           } else {
-#ifndef BA3C_B6_RINGFENCE
-#define BA3C_B6_RINGFENCE 1   // 0: A/B build without the fence below
-#endif
             // the weight-ring loads of k-step t + LA stay here: the scheduler otherwise sank them
             // next to their use, leaving one k-step of lookahead (a vmcnt(0) per k-step, r04 ISA).
             // Input-gradient layouts only: conv2's whole-map input gradient + weight gradient
             // 0.265 -> 0.221 ms with the branch-free staging; conv2's forward 0.093 -> 0.095 ms
-            if (BA3C_B6_RINGFENCE && !G::POOL) __builtin_amdgcn_sched_barrier(0);
+            if (!G::POOL) __builtin_amdgcn_sched_barrier(0);
             read_a(t, avb[0]);
           }
           u32x4 b[L::NS];
 #pragma unroll
           for (int s = 0; s < L::NS; ++s) {
-            const uint4 u = bring[BA3C_DIAG_NOB ? t % LA : t % (LA + 1)][s];
+            const uint4 u = bring[t % (LA + 1)][s];
             b[s] = u32x4{u.x, u.y, u.z, u.w};
           }
           // NS = 3: a1b1, a1b2, a2b1, a1b3, a2b2, a3b1;  NS = 2: a1b1, a1b2, a2b1 —
@@ -430,7 +417,7 @@ struct Band6Ops {
             mfmas();
           }
         }
-        if (BA3C_B6_PRIO) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
       }
 
       // ---- epilogue (16x16 C layout: lane holds column li, rows 4 lq + r) ----
@@ -536,10 +523,7 @@ __device__ __forceinline__ void band6r_body(const Band6Args& a, int bx, int gx, 
   }
   // PRE (input-gradient layouts, whose registers allow it): the next band's RB new rows are
   // loaded into registers before this band's MFMAs, so their global latency hides behind them
-#ifndef BA3C_RING_PRE
-#define BA3C_RING_PRE 1
-#endif
-  constexpr bool PRE = BA3C_RING_PRE && PRE_;
+  constexpr bool PRE = PRE_;
   constexpr unsigned FNEW = (unsigned)HALO * G::WS * O::Q;  // first float4 index of the new rows
   constexpr int NNEW = (G::RB * G::WS * O::Q + 255) / 256;
   float4 pv[PRE ? NNEW : 1];
@@ -562,15 +546,7 @@ __device__ __forceinline__ void band6r_body(const Band6Args& a, int bx, int gx, 
       __syncthreads();                                      // previous band's LDS reads are done
       if (dyn && tid == 0 && bi == 1) *tslot = (int)nt;     // (read after the image's last band)
       unsigned fbase = 0;
-#ifndef BA3C_DIAG_NOSTAGE
-#define BA3C_DIAG_NOSTAGE 0   // diagnostics only (A/B timing builds): skip the band staging
-#endif
-#ifndef BA3C_DIAG_NOCOMPUTE
-#define BA3C_DIAG_NOCOMPUTE 0 // diagnostics only: skip the MFMA main loop and epilogue
-#endif
-      if (BA3C_DIAG_NOSTAGE) {
-        __syncthreads();
-      } else if (bi > 0) {
+      if (bi > 0) {
         // carry the halo rows down: source rows RB .. SROWS-1 -> rows 0 .. HALO-1.  The new
         // rows then go to rows HALO .. SROWS-1, which overlap the source rows (RB >= HALO), and
         // a thread's copy elements are not the rows its stores write: every wave's copy must
@@ -583,8 +559,7 @@ __device__ __forceinline__ void band6r_body(const Band6Args& a, int bx, int gx, 
         fbase = FNEW;                                       // stage rows HALO .. SROWS-1 only
         __syncthreads();
       }
-      if (BA3C_DIAG_NOSTAGE) {
-      } else if (PRE && bi > 0) {
+      if (PRE && bi > 0) {
         // the new rows were prefetched during the previous band's MFMAs
 #pragma unroll
         for (int i = 0; i < NNEW; ++i) O::store1(lds, y0, rows_out, FNEW + tid + 256u * i, pv[i], pc[i], asc);
@@ -602,12 +577,12 @@ __device__ __forceinline__ void band6r_body(const Band6Args& a, int bx, int gx, 
         }
       }
       __syncthreads();
-      if (PRE && !BA3C_DIAG_NOSTAGE && bi + 1 < G::NBANDS) {
+      if (PRE && bi + 1 < G::NBANDS) {
         const int y1 = y0 + G::RB, ro1 = min(G::RB, G::HO - y1);
 #pragma unroll
         for (int i = 0; i < NNEW; ++i) O::load1(a, img, y1, ro1, 0, FNEW + tid + 256u * i, pv[i], pc[i]);
       }
-      if (!BA3C_DIAG_NOCOMPUTE) O::compute(a, lds, wave, lane, img, y0, rows_out, us1, us2, pos, omax, [](int) {});
+      O::compute(a, lds, wave, lane, img, y0, rows_out, us1, us2, pos, omax, [](int) {});
     }
     if (L::NS == 2) amax_publish(a.amax_out, img, omax, lane);
     img = dyn ? gx + *tslot : img + 1;   // (written at band 1; bands >= 2 put barriers in between)
@@ -744,7 +719,7 @@ template <class L, bool PRE_ = L::G::SRC == 1>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) conv_band6r_kernel(const Band6Args a) {
   __shared__ uint4 lds4[L::LDS_BYTES / 16];
   __shared__ int tslot[1];
-  if constexpr (BA3C_UNPOOL_STAGE && L::G::SRC == 1 && L::NS == 2)
+  if constexpr (L::G::SRC == 1 && L::NS == 2)
     band6r_up_body<L>(a, blockIdx.x, gridDim.x, reinterpret_cast<char*>(lds4), tslot);
   else
     band6r_body<L, PRE_>(a, blockIdx.x, gridDim.x, reinterpret_cast<char*>(lds4), tslot);
@@ -885,7 +860,7 @@ __device__ __forceinline__ void wprep6_body(const WPrep6Args& a, int bx, int by,
   for (int d = bx * 256 + threadIdx.x; d < j.n; d += gx * 256) {
     const int kk = d & 7, li = (d >> 3) & 15, lq = (d >> 7) & 3, rest = d >> 9;
     const int k32 = rest / NB, nb = rest - k32 * NB;
-    const int e = BA3C_WFRAG ? (nb * 16 + li) * K + k32 * 32 + lq * 8 + kk : d;
+    const int e = (nb * 16 + li) * K + k32 * 32 + lq * 8 + kk;
     const float v = wprep_value(j, e);
     uint32_t hi, lo;
     split2(v * sc, hi, lo);

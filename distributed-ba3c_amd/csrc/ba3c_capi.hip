@@ -185,8 +185,8 @@ struct ba3c_handle {
   bool held = false;
   hipStream_t held_stream = nullptr;
   ReduceJobs held_jobs{};
-  // recorded on the pass's stream after conv3's gradient launches of every phase-2 pass
-  // (ba3c_set_phase2_event; null: none)
+  // recorded on the pass's stream after conv3's input-gradient launch of every phase-2 pass,
+  // and its weight gradient's unless BA3C_C3W_RIDE is set (ba3c_set_phase2_event; null: none)
   hipEvent_t ev_mid = nullptr;
   hipStream_t side = nullptr;
   hipEvent_t ev_fork[4] = {}, ev_join = nullptr;
@@ -235,26 +235,13 @@ using GConv2DS = BandGeom<22, 22, 64, 32, 5, 5, 3, false, 1, 8, 4, 4, 7, 7, 14, 
 struct Lay {
   using C1F = Band6<GConv1F, 160, 128, 7, 0, 2, true>;
   using C2F = Band6<GConv2F, 160, 64, 7, 0, 2>;   // (double-buffered: 256 VGPRs, neutral, r04)
-#ifndef BA3C_C1D_TILE4
-#define BA3C_C1D_TILE4 1
-#endif
-#if BA3C_C1D_TILE4
   using C1D = Band6<GConv1D, 160, 0, 5, 0, 2, true, true>;   // 4x4 tiles: RP = 128 mod 256 B
-#else
-  using C1D = Band6<GConv1D, 160, 128, 5, 0, 2, true>;
-#endif
-#ifndef BA3C_C2D_PADSKIP
-#define BA3C_C2D_PADSKIP 1
-#endif
-#ifndef BA3C_C2D_DBUF
-#define BA3C_C2D_DBUF 0
-#endif
-  using C2D = Band6<GConv2DW, 160, 128, 11, 32, 2, BA3C_C2D_DBUF, false, BA3C_C2D_PADSKIP>;
+  using C2D = Band6<GConv2DW, 160, 128, 11, 32, 2, false, false, true>;   // padding skip, no A double buffer
   using C2FS = Band6<GConv2FS, 160, 64, 2, 0, 2, true>;
   using C2DS = Band6<GConv2DS, 160, 128, 2, 32, 2, true>;
   using W1 = Wg6Geom<40, 40, 32, 32, 4, 16, 32, 96, 160, 2>;
   using W2 = Wg6Geom<18, 18, 32, 64, 14, 16, 32, 96, 160, 2>;
-  using W1W = Wg6WGeom<40, 40, 32, 32, 4, 160, 160>;   // conv1, B >= W6W_MIN_B (76.8 KB LDS)
+  using W1W = Wg6WGeom<40, 40, 32, 32, 4, 160, 160>;   // conv1, B >= W6W_MIN_B (66.2 KB LDS)
 };
 // persistent grid bound of conv1's partial slabs
 constexpr int WG_P1 = 512;
@@ -338,9 +325,6 @@ WgradPlan plan_wgrad(int M, int N, int K, int BM, int BN, int target = kWgradTar
 // 28.0 us (half the fc1 slabs); not the 3x the VALU count suggested — the two workgroups per CU
 // that 60 KB of LDS allows leave each k-tile's staging exposed, and 3- / 4-deep load rings
 // (BA3C_FCD_DEPTH) made it 0.079 / 0.080 ms.
-#ifndef BA3C_FC1_BIGTILE
-#define BA3C_FC1_BIGTILE 1
-#endif
 #ifndef BA3C_FC1W_TARGET
 #define BA3C_FC1W_TARGET 256
 #endif
@@ -352,18 +336,15 @@ WgradPlan fc1w_plan(int F, int B, bool legacy, bool bigtile) {
 // geometry constants (train.py:92, :177-212)
 constexpr int P0 = 40 * 40 * 32, P1 = 18 * 18 * 32, P2 = 7 * 7 * 64, A3 = 1600;
 // FC1 fwd split-K: 5 fixed chunks of 10 k-tiles (batch-independent rounding), each the sum
-// of its even and its odd k-tiles (BA3C_FC_HALVES, gemm6_body PAR: two groups at B <= 64, one
+// of its even and its odd k-tiles (gemm6_body PAR: two groups at B <= 64, one
 // group with two accumulator sets above; the same association, so every row rounds the same
 // at any batch).
 // r02: 416 (4 chunks of 13 k-tiles) left B=32 with 8 workgroups walking 13 dependent k-tiles
 // (17.6 us).  r06aa / r06ab: 5 chunks instead of 10 (half the partial sums written by fc1 and
 // read by the heads kernel) took the B=2048 step 1.713 -> 1.685 and 1.685 -> 1.665 ms, but
 // B=32 0.1565 -> 0.1612 ms with 10 k-tiles per workgroup in series: hence the two groups.
-#ifndef BA3C_FC_HALVES
-#define BA3C_FC_HALVES 1
-#endif
 #ifndef BA3C_FC_KCHUNK
-#define BA3C_FC_KCHUNK (BA3C_FC_HALVES ? 320 : 160)
+#define BA3C_FC_KCHUNK 320
 #endif
 constexpr int FC_KCHUNK = BA3C_FC_KCHUNK, FC_SPLIT = (A3 + FC_KCHUNK - 1) / FC_KCHUNK;
 static_assert(FC_SPLIT <= FC_SPLIT_MAX, "heads kernel finishes at most FC_SPLIT_MAX chunks");
@@ -418,10 +399,7 @@ Workspace carve(const ba3c_handle* h, void* base, int B, bool train) {
   w.p2 = (float*)take(Bz * P2 * 4);
   w.a3 = (float*)take(Bz * A3 * 4);
   w.h = (float*)take(Bz * F * 4);
-#ifndef BA3C_FCPART_LAST
-#define BA3C_FCPART_LAST 0   // A/B: fc1's forward partials at the end of the workspace
-#endif
-  if (!BA3C_FCPART_LAST) w.fcpart = (float*)take((size_t)FC_SPLIT * Bz * F * 4);
+  w.fcpart = (float*)take((size_t)FC_SPLIT * Bz * F * 4);
   w.relu = (unsigned long long*)take(RELU_WORDS * 8);
   w.wt = (float*)take((size_t)WT_TOTAL * 4);
   w.wt6 = (uint16_t*)take((size_t)3 * WT_C0F * 2);
@@ -444,7 +422,6 @@ Workspace carve(const ba3c_handle* h, void* base, int B, bool train) {
     w.part_1 = (float*)take(ps.conv1 * 4);
     w.part0 = (float*)take(max_partials0(h, B) * 4);
   }
-  if (BA3C_FCPART_LAST) w.fcpart = (float*)take((size_t)FC_SPLIT * Bz * F * 4);
   w.bytes = off;
   return w;
 }
@@ -832,21 +809,15 @@ int run_forward(ba3c_handle* h, hipStream_t s, const float* prm, const uint8_t* 
   {
     ProbeScope ps(h, s, BA3C_K_FC1_FWD);
     const dim3 grid((B + 127) / 128, (F + 63) / 64, FC_SPLIT);
-    constexpr bool HV = BA3C_FC_HALVES;
-    constexpr int KSS = HV ? 2 : 1;   // small batches: even and odd k-tiles in two groups
+    constexpr bool HV = true;
+    constexpr int KSS = 2;   // small batches: even and odd k-tiles in two groups
     if (h->g6 && B <= 64)   // 64-row tiles: same per-row K order, half the dead rows staged
       hipLaunchKernelGGL((gemm6_kernel<64, 64, 2, 2, FcFwd, 4, KSS, HV>), dim3((B + 63) / 64, grid.y, grid.z),
                          dim3(GEMM_THREADS * KSS), 0, s, fc);
     else if (h->g6 && (int)(grid.x * grid.y * grid.z) < h->cus)
       hipLaunchKernelGGL((gemm6_kernel<128, 64, 2, 2, FcFwd, 4, 1, HV>), grid, dim3(GEMM_THREADS), 0, s, fc);
-#ifndef BA3C_FC1F_BIGTILE
-#define BA3C_FC1F_BIGTILE 0   // full grids on 128 x 128 tiles (same K chunks: bit-identical; r06v
-                              // 0.0299 -> 0.0333 ms, not used)
-#endif
-    else if (h->g6 && BA3C_FC1F_BIGTILE)
-      hipLaunchKernelGGL((gemm6_kernel<128, 128, 2, 2, FcFwd, BA3C_FC_DEPTH, 1, HV>), dim3(grid.x, (F + 127) / 128, grid.z),
-                         dim3(GEMM_THREADS), 0, s, fc);
-    else if (h->g6)
+    else if (h->g6)   // (full grids on 128 x 128 tiles, same K chunks, were bit-identical and
+                      // slower: r06v 0.0299 -> 0.0333 ms, not kept)
       hipLaunchKernelGGL((gemm6_kernel<128, 64, 2, 2, FcFwd, BA3C_FC_DEPTH, 1, HV>), grid, dim3(GEMM_THREADS), 0, s, fc);
     else
       hipLaunchKernelGGL((gemm_kernel<128, 64, 2, 2, FcFwd>), grid, dim3(GEMM_THREADS), 0, s, fc);
@@ -906,7 +877,7 @@ int run_backward(ba3c_handle* h, hipStream_t s, const float* prm, const uint8_t*
   static_assert(OVERLAP_B <= SMALL_B, "multi-job conv2 input gradient is the small-batch geometry");
   if (!mj && h->side && (h->overlap == 1 || B <= OVERLAP_B)) ws = h->side;
   const bool big = B > OVERLAP_B;   // multi-job gemm jobs: 2-deep k-tile rings (full grids)
-  const bool fc1big = BA3C_FC1_BIGTILE && mj_fc && big;   // fc1w_plan
+  const bool fc1big = mj_fc && big;   // fc1w_plan
   // every weight-gradient reduction is deferred into one launch at the end (RAII: an early
   // error return leaves the handle in immediate mode)
   struct DeferGuard {
@@ -1036,10 +1007,7 @@ int run_backward(ba3c_handle* h, hipStream_t s, const float* prm, const uint8_t*
       const Conv3Args da{w.dy3, w.wt6 + 2 * (size_t)WT_C3D, w.wexp + WJ_C3D, w.dp2, nullptr,
                          w.am(AM_DP2, h), B, w.am(AM_DY3, h)};
       const int gx = conv3_wgrad_p(B, h->cus);
-#ifndef BA3C_C3PAIR
-#define BA3C_C3PAIR 1   // 0: A/B build with the small-batch conv3 gradients in two launches
-#endif
-      if (mj && BA3C_C3PAIR) {
+      if (mj) {
         // small batches: input and weight gradient in one launch (two 256-thread workgroups per
         // weight-gradient slab; the weight gradient reduces max |dY3| itself, since the input
         // gradient publishes it only as it runs)

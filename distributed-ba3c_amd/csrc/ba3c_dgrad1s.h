@@ -131,10 +131,6 @@ __device__ __forceinline__ void dgrad1s_body(const Band6Args& a, int bx, int gx,
   const uint16_t* wb = a.wt6 + ((size_t)(eps * G::KSTEPS * 2 + nt) * 64 + lane) * G::WFRAG;
   constexpr size_t BSTEP = 2 * 64 * G::WFRAG;
 
-#ifndef BA3C_DIAG_D1S
-#define BA3C_DIAG_D1S 0       // diagnostics only (A/B timing): 1 = no staging, 2 = no MFMA loop,
-                              // 3 = weight fragments of the first k-steps reused (no L2 weight stream)
-#endif
   // whole images per workgroup, bands in order (the halo rows move down in LDS)
   const int ipw = (a.batch + gx - 1) / gx;
   const int img0 = bx * ipw, img1 = min(a.batch, img0 + ipw);
@@ -144,7 +140,7 @@ __device__ __forceinline__ void dgrad1s_body(const Band6Args& a, int bx, int gx,
     for (int bi = 0; bi < G::NBANDS; ++bi) {
     const int y0 = bi * G::RB;
     __syncthreads();                                   // previous band's LDS reads are done
-    if (BA3C_DIAG_D1S != 1 && bi > 0) {
+    if (bi > 0) {
       // staged rows 4 .. 7 -> 0 .. 3 (PV and MV planes) and pooled index rows 2, 3 -> 0, 1;
       // every copy completes before any new row is stored over its source
       constexpr int NPV = G::PV_RS, NMV = G::MV_RS;    // uint4 per plane (4 rows)
@@ -172,20 +168,18 @@ __device__ __forceinline__ void dgrad1s_body(const Band6Args& a, int bx, int gx,
       }
       __syncthreads();
     }
-    if (BA3C_DIAG_D1S != 1) {
-      if (bi == 0) {
+    if (bi == 0) {
 #pragma unroll 1
-        for (int f = tid; f < G::NITEM; f += 256) {
-          float4 x0, x1;
-          uint32_t k0, k1;
-          item_load(img, y0, f, x0, x1, k0, k1);
-          item_store(asc, f, x0, x1, k0, k1);
-        }
-      } else {
-#pragma unroll
-        for (int i = 0; i < IPN; ++i)
-          if (FNEW + tid + 256 * i < G::NITEM) item_store(asc, FNEW + tid + 256 * i, v0[i], v1[i], c0[i], c1[i]);
+      for (int f = tid; f < G::NITEM; f += 256) {
+        float4 x0, x1;
+        uint32_t k0, k1;
+        item_load(img, y0, f, x0, x1, k0, k1);
+        item_store(asc, f, x0, x1, k0, k1);
       }
+    } else {
+#pragma unroll
+      for (int i = 0; i < IPN; ++i)
+        if (FNEW + tid + 256 * i < G::NITEM) item_store(asc, FNEW + tid + 256 * i, v0[i], v1[i], c0[i], c1[i]);
     }
     __syncthreads();
     f32x4 acc[5];
@@ -222,19 +216,17 @@ __device__ __forceinline__ void dgrad1s_body(const Band6Args& a, int bx, int gx,
     };
     u32x4 ar[3][2];
     int xr[3];
-    if (BA3C_DIAG_D1S != 2) {
-      read_item(0, 0, 0, ar[0], xr[0]);
-      read_item(0, 0, 1, ar[1], xr[1]);
-    }
+    read_item(0, 0, 0, ar[0], xr[0]);
+    read_item(0, 0, 1, ar[1], xr[1]);
 #pragma unroll 1
-    for (int kh = 0; kh < (BA3C_DIAG_D1S == 2 ? 0 : 5); ++kh) {
+    for (int kh = 0; kh < 5; ++kh) {
       // the next band's new rows mid-band (vmcnt waits are in issue order: loads issued before
       // the first weight-ring loads would hold up this band's first k-steps)
-      if (BA3C_DIAG_D1S != 1 && kh == 1 && bi + 1 < G::NBANDS) load_new(img, y0 + G::RB);
+      if (kh == 1 && bi + 1 < G::NBANDS) load_new(img, y0 + G::RB);
 #pragma unroll
       for (int i = 0; i < 15; ++i) {
         const int t = i / 5, jt = i - 5 * t, s = 3 * kh + t;
-        if (jt == 0 && s + LA < G::KSTEPS && BA3C_DIAG_D1S != 3) {
+        if (jt == 0 && s + LA < G::KSTEPS) {
 #pragma unroll
           for (int sp = 0; sp < 2; ++sp) {
             const uint4* p = reinterpret_cast<const uint4*>(wb + (s + LA) * BSTEP + (size_t)sp * G::WPLANE);

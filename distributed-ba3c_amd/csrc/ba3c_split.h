@@ -86,22 +86,13 @@ __device__ __forceinline__ uint32_t pack_f16x2(float a, float b) {
   return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2v){a, b}, f16x2v));
 }
 // (a, b) = hi + lo (+ 2^-22 relative), each a packed fp16 pair.  lo = RN_f16(a - hi) with
-// a - hi exact in fp32: v_fma_mixlo_f16 / v_fma_mixhi_f16 take hi's halves as fp16 operands
-// and write the rounded fp16 results into lo's halves, 2 instructions for the pair instead of
-// 2 conversions to fp32 and a packed fma + pack (BA3C_SPLIT_MIX=1).  Bit-identical, but slower:
-// conv1 forward 0.2856 -> 0.2913 ms, conv1 dgrad +3 us (r06q), so the plain form is the default
-#ifndef BA3C_SPLIT_MIX
-#define BA3C_SPLIT_MIX 0
-#endif
+// a - hi exact in fp32.  An inline-asm v_fma_mixlo_f16 / v_fma_mixhi_f16 form (hi's halves as
+// fp16 operands, 2 instructions for the pair) was bit-identical but slower: conv1 forward
+// 0.2856 -> 0.2913 ms, conv1 dgrad +3 us (r06q), not kept
 __device__ __forceinline__ void split2x2(float a, float b, uint32_t& hi, uint32_t& lo) {
   hi = pack_f16x2(a, b);
-#if BA3C_SPLIT_MIX
-  asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(lo) : "v"(hi), "v"(a));
-  asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lo) : "v"(hi), "v"(b));
-#else
   const f16x2v h = __builtin_bit_cast(f16x2v, hi);
   lo = pack_f16x2(a - (float)h[0], b - (float)h[1]);
-#endif
 }
 __device__ __forceinline__ void split2(float w, uint32_t& hi, uint32_t& lo) {
   uint32_t h2, l2;
@@ -157,14 +148,8 @@ struct Conv0S {
   static constexpr int PROWS_W = RB / 2 / 4;       // pooled rows per wave (2)
   static constexpr int MBROW = (WO / 2) / 4;       // m-blocks per pooled row (10)
   static constexpr int MBW = PROWS_W * MBROW;      // m-blocks per wave (20)
-#ifndef BA3C_C0F_PIPE
-#define BA3C_C0F_PIPE 1   // chunk c's MFMAs interleaved with chunk c - 1's pool epilogue (two accumulator sets)
-#endif
-#ifndef BA3C_C0F_POSPK
-#define BA3C_C0F_POSPK 1  // ReLU positives by saturating pack + byte gather + popcount (A/B: 0)
-#endif
 #ifndef BA3C_C0F_MCH
-#define BA3C_C0F_MCH (BA3C_C0F_PIPE ? 2 : 5)
+#define BA3C_C0F_MCH 2
 #endif
   static constexpr int MCH = BA3C_C0F_MCH;          // m-blocks per accumulator chunk
   // prepared weights: [split][nt][kstep][lane] x 16 bytes (room for the 3-plane family)
@@ -251,19 +236,10 @@ struct Conv0SArgs {
   unsigned* zerr;
 };
 
-// 1 if the fp32 bits x are a positive value (x > 0 as a signed integer), else 0: one
-// v_med3_i32 (x, 0, 1); in C the clamp is turned back into a compare + select through VCC.
-// x is an MFMA result: inline asm is not seen by the MFMA -> VALU read hazard check, so the
-// asm also takes `after`, a compiler-visible VALU result of the same accumulator (the window
-// max), which orders it behind the wait states the compiler inserted for that read.
-__device__ __forceinline__ int c0w_pos1(int x, int after) {
-  int r;
-  asm("v_med3_i32 %0, %1, 0, 1" : "=v"(r) : "v"(x), "v"(after));
-  return r;
-}
-
-// max(t, x, 0) in one v_max3_i32; x an MFMA result read after t, a compiler-visible VALU
-// result of the same accumulator (as c0w_pos1)
+// max(t, x, 0) in one v_max3_i32.  x is an MFMA result: inline asm is not seen by the
+// MFMA -> VALU read hazard check, so the asm also takes t, a compiler-visible VALU result of
+// the same accumulator, which orders it behind the wait states the compiler inserted for
+// that read.
 __device__ __forceinline__ int c0w_max3z(int t, int x) {
   int r;
   asm("v_max3_i32 %0, %1, %2, 0" : "=v"(r) : "v"(t), "v"(x));
@@ -423,7 +399,7 @@ __device__ __forceinline__ void conv0s_fwd_body_t(const Conv0SArgs& a, int bx, i
       lb[s][h] = pix0 + (tap / G::KT) * RP + tap % G::KT;
     }
 
-  int pos = 0;                                      // this lane's ReLU positives (TRAIN; 8x with BA3C_C0F_POSPK)
+  int pos = 0;                                      // this lane's ReLU positives (TRAIN), times 8
   // (sum_k u8 * w 2^kw) * (2^-kw / 255): scaling by a power of two commutes with the rounding
   const float oscale = (1.0f / 255.0f) * exp2i(-wx);
   // Epilogue stores go through a wave-private LDS area holding one pooled row of outputs
@@ -495,24 +471,15 @@ __device__ __forceinline__ void conv0s_fwd_body_t(const Conv0SArgs& a, int bx, i
             arg = b1 == m ? 1u : arg;
             arg = b0 == m ? 0u : arg;
             wsc[lane_el + cofs] = (uint8_t)(m != 0 ? arg : 255u);
-            // positives by v_cmp -> SGPR mask -> s_bcnt1 (one VALU instruction per value; the
-            // bits compare as signed integers: x > 0 exactly for positive x)
-            // ReLU positives: the bits compare as signed integers (x > 0 exactly for x > 0).
-            // Per-lane compare + add; a v_cmp -> SGPR ballot + s_bcnt1 form has fewer VALU
-            // instructions but measured slower (0.189 -> 0.209 ms, VALU-to-SALU dependencies)
-            // (x > 0) as med3(x, 0, 1) on the bits (v_med3_i32) and three-input adds: no VCC
-            // round trips (a compare + add-with-carry per value chained the four through VCC)
-#if BA3C_C0F_POSPK
-            // 8 x (positives): v_cvt_pk_i16_i32 saturates the bits of a positive value to
+            // 8 x (ReLU positives): v_cvt_pk_i16_i32 saturates the bits of a positive value to
             // 0x7FFF, of zero to 0, of a negative one to 0x8000, so the low byte of each half is
             // 0xFF exactly for a positive value; one v_perm_b32 gathers the four low bytes and
-            // v_bcnt_u32_b32 adds 8 per positive (4 VALU per window instead of 6)
+            // v_bcnt_u32_b32 adds 8 per positive: 4 VALU per window.  Tried and not kept: a
+            // v_med3_i32 per value + three-input adds (6 VALU), and a v_cmp -> SGPR ballot +
+            // s_bcnt1 form (0.189 -> 0.209 ms, VALU-to-SALU dependencies)
             pos += __builtin_popcount(__builtin_amdgcn_perm(
                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pk_i16(b2, b3)),
                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pk_i16(b0, b1)), 0x06040200u));
-#else
-            pos += (c0w_pos1(b0, m) + c0w_pos1(b1, m)) + (c0w_pos1(b2, m) + c0w_pos1(b3, m));
-#endif
             // materialise the count here: otherwise it is sunk to its only use after the band
             // loop, keeping every accumulator of the chunk live (r03g: > 256 registers)
             asm volatile("" : "+v"(pos));
@@ -543,32 +510,18 @@ __device__ __forceinline__ void conv0s_fwd_body_t(const Conv0SArgs& a, int bx, i
         }
       }
     };
-    if constexpr (BA3C_C0F_PIPE) {
-      // software pipeline over the band's chunks: the epilogue of chunk c - 1 (VALU) issues
-      // between the MFMAs of chunk c, which do not depend on it, so one wave keeps the matrix
-      // core and the VALU busy together (two MCH = 2 accumulator sets: 32 registers, fewer than
-      // one MCH = 5 set)
-      f32x4 acc[2][G::MCH][2];
-      chunk_mma(0, acc[0]);
+    // software pipeline over the band's chunks: the epilogue of chunk c - 1 (VALU) issues
+    // between the MFMAs of chunk c, which do not depend on it, so one wave keeps the matrix
+    // core and the VALU busy together (two MCH = 2 accumulator sets: 32 registers, fewer than
+    // the one MCH = 5 set of the earlier unpipelined loop)
+    f32x4 acc[2][G::MCH][2];
+    chunk_mma(0, acc[0]);
 #pragma unroll
-      for (int ch = 1; ch < NCH; ++ch) {
-        chunk_mma(ch, acc[ch & 1]);
-        chunk_epi(ch - 1, acc[(ch - 1) & 1]);
-      }
-      chunk_epi(NCH - 1, acc[(NCH - 1) & 1]);
-    } else {
-#pragma unroll
-      for (int ch = 0; ch < NCH; ++ch) {
-        // chunks do not overlap inside a wave (the two waves per SIMD overlap each other's
-        // epilogue and MFMAs): without this fence the scheduler interleaves chunk c + 1's A reads
-        // and MFMAs with chunk c's epilogue, two MCH = 5 accumulator sets live -> > 256
-        // registers and one wave per SIMD (r03g: 0.35 ms)
-        __builtin_amdgcn_sched_barrier(0);
-        f32x4 acc[G::MCH][2];
-        chunk_mma(ch, acc);
-        chunk_epi(ch, acc);
-      }
+    for (int ch = 1; ch < NCH; ++ch) {
+      chunk_mma(ch, acc[ch & 1]);
+      chunk_epi(ch - 1, acc[(ch - 1) & 1]);
     }
+    chunk_epi(NCH - 1, acc[(NCH - 1) & 1]);
     // max over the window maxima, then the scale: a positive scale is monotone in fp32
     if (!zdone) {
       chain_wait_wave(a.zsig, a.zneed, a.zerr);
@@ -578,7 +531,7 @@ __device__ __forceinline__ void conv0s_fwd_body_t(const Conv0SArgs& a, int bx, i
   }
   if (!zdone) chain_wait_wave(a.zsig, a.zneed, a.zerr);
   if (TRAIN && a.relu_count)
-    relu_count_add(a.relu_count, (unsigned long long)(BA3C_C0F_POSPK ? pos >> 3 : pos), lane);
+    relu_count_add(a.relu_count, (unsigned long long)(pos >> 3), lane);
 }
 
 #if !BA3C_SHARED_KERNELS  // emitted by ba3c_conv0.hip only
@@ -678,22 +631,16 @@ __device__ __forceinline__ uint32_t c0w_mask16_eq0(uint32_t d) {
 
 // bx / gx: first band and persistent stride (blockIdx.x / gridDim.x of the plain kernel; a
 // paired launch passes its own); lds: Conv0W<NS>::ALLOC_U4 uint4 of LDS, red4: 4 words
-#ifndef BA3C_C0W_SPARSE
-#define BA3C_C0W_SPARSE 1
-#endif
 template <int NS>
 __device__ __forceinline__ void conv0s_wgrad_body(const Conv0WArgs& a, int bx, int gx, uint4* lds, uint32_t* red4) {
   using G = Conv0W<NS>;
   using SP = SplitP<NS>;
-  constexpr bool C0W_SPARSE = BA3C_C0W_SPARSE && NS == 2;
-#ifndef BA3C_C0W_XFIRST
-#define BA3C_C0W_XFIRST 1
-#endif
+  constexpr bool C0W_SPARSE = NS == 2;
   // X first: its A-fragment addresses are then lane offset + k-step offset with no LDS base to
   // add (the base of a region past 1 KB does not fit the ds_read2 offset fields, and the
   // compiler added it to each of the 14 dword-pair reads of a k-step)
-  uint16_t* xs = reinterpret_cast<uint16_t*>(lds) + (BA3C_C0W_XFIRST ? 0 : G::Y_16);
-  uint16_t* ys = reinterpret_cast<uint16_t*>(lds) + (BA3C_C0W_XFIRST ? G::X_16 : 0);
+  uint16_t* xs = reinterpret_cast<uint16_t*>(lds);
+  uint16_t* ys = reinterpret_cast<uint16_t*>(lds) + G::X_16;
   uint8_t* yc8 = reinterpret_cast<uint8_t*>(reinterpret_cast<uint16_t*>(lds) + G::X_16 + G::Y_16);
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 15, lq = lane >> 4;
@@ -792,7 +739,7 @@ __device__ __forceinline__ void conv0s_wgrad_body(const Conv0WArgs& a, int bx, i
       const uint32_t sy = (uint32_t)(r & 1);
       const int e0 = ((r >> 1) * G::COUT + li) * G::PW + (x0 >> 1);
       if constexpr (C0W_SPARSE) {
-        // 2:4-sparse form (BA3C_C0W_SPARSE): dY^T on the sparse A side of
+        // 2:4-sparse form: dY^T on the sparse A side of
         // v_smfmac_f32_16x16x32_f16 (rows o, the lane's 8 pixels = 2 quads of 2 windows each),
         // the frames' fragments above as its dense B (columns (tap, c)).  Per quad the two kept
         // values are the windows' gradients where their argmax lies in this pixel row (else 0)
@@ -822,48 +769,27 @@ __device__ __forceinline__ void conv0s_wgrad_body(const Conv0WArgs& a, int bx, i
         continue;
       }
       u32x4 bv[NS][2];
-#ifndef BA3C_C0W_PKMASK
-#define BA3C_C0W_PKMASK 1
-#endif
 #pragma unroll
       for (int nt = 0; nt < 2; ++nt) {
         const int e = e0 + 16 * nt * G::PW;
         const uint32_t cw = *reinterpret_cast<const uint32_t*>(yc8 + e);
-        if constexpr (BA3C_C0W_PKMASK) {
-          // the four windows' codes as 16-bit halves, xor 2 sy: a window's argmax is in this
-          // pixel row at sub-column h exactly when its half equals h (255 ^ 2 sy never does);
-          // m0 / m1 = 0xFFFF halves where it is sub-column 0 / 1 (packed 16-bit compares:
-          // 14 VALU per n-tile for what took a bfe + compare + select per window and mask)
-          const uint32_t sx = sy * 0x00020002u;
-          const uint32_t k01 = __builtin_amdgcn_perm(cw, cw, 0x0C010C00u) ^ sx;
-          const uint32_t k23 = __builtin_amdgcn_perm(cw, cw, 0x0C030C02u) ^ sx;
-          const uint32_t m0a = c0w_mask16_eq0(k01), m1a = c0w_mask16_eq0(k01 ^ 0x00010001u);
-          const uint32_t m0b = c0w_mask16_eq0(k23), m1b = c0w_mask16_eq0(k23 ^ 0x00010001u);
-#pragma unroll
-          for (int sp = 0; sp < NS; ++sp) {
-            const uint2 u = *reinterpret_cast<const uint2*>(ys + sp * (G::PRB * G::COUT * G::PW) + e);
-            // window j's dword = (v_j at sub-column 0, v_j at sub-column 1): low halves of
-            // (u & m0, u & m1) for even j, high halves for odd j
-            const uint32_t a0 = u.x & m0a, b0 = u.x & m1a, a1 = u.y & m0b, b1 = u.y & m1b;
-            bv[sp][nt] = u32x4{__builtin_amdgcn_perm(b0, a0, 0x05040100u), __builtin_amdgcn_perm(b0, a0, 0x07060302u),
-                               __builtin_amdgcn_perm(b1, a1, 0x05040100u), __builtin_amdgcn_perm(b1, a1, 0x07060302u)};
-          }
-          continue;
-        }
-        uint32_t mk[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const uint32_t k = (cw >> (8 * j)) & 255u;   // 0..3, or 255 (no gradient)
-          mk[j] = (k >> 1) == sy ? ((k & 1u) ? 0xFFFF0000u : 0x0000FFFFu) : 0u;
-        }
+        // the four windows' codes as 16-bit halves, xor 2 sy: a window's argmax is in this
+        // pixel row at sub-column h exactly when its half equals h (255 ^ 2 sy never does);
+        // m0 / m1 = 0xFFFF halves where it is sub-column 0 / 1 (packed 16-bit compares:
+        // 14 VALU per n-tile for what took a bfe + compare + select per window and mask)
+        const uint32_t sx = sy * 0x00020002u;
+        const uint32_t k01 = __builtin_amdgcn_perm(cw, cw, 0x0C010C00u) ^ sx;
+        const uint32_t k23 = __builtin_amdgcn_perm(cw, cw, 0x0C030C02u) ^ sx;
+        const uint32_t m0a = c0w_mask16_eq0(k01), m1a = c0w_mask16_eq0(k01 ^ 0x00010001u);
+        const uint32_t m0b = c0w_mask16_eq0(k23), m1b = c0w_mask16_eq0(k23 ^ 0x00010001u);
 #pragma unroll
         for (int sp = 0; sp < NS; ++sp) {
           const uint2 u = *reinterpret_cast<const uint2*>(ys + sp * (G::PRB * G::COUT * G::PW) + e);
-          // (lo, lo) and (hi, hi) half-word pairs of each dword
-          bv[sp][nt] = u32x4{__builtin_amdgcn_perm(u.x, u.x, 0x01000100u) & mk[0],
-                             __builtin_amdgcn_perm(u.x, u.x, 0x03020302u) & mk[1],
-                             __builtin_amdgcn_perm(u.y, u.y, 0x01000100u) & mk[2],
-                             __builtin_amdgcn_perm(u.y, u.y, 0x03020302u) & mk[3]};
+          // window j's dword = (v_j at sub-column 0, v_j at sub-column 1): low halves of
+          // (u & m0, u & m1) for even j, high halves for odd j
+          const uint32_t a0 = u.x & m0a, b0 = u.x & m1a, a1 = u.y & m0b, b1 = u.y & m1b;
+          bv[sp][nt] = u32x4{__builtin_amdgcn_perm(b0, a0, 0x05040100u), __builtin_amdgcn_perm(b0, a0, 0x07060302u),
+                             __builtin_amdgcn_perm(b1, a1, 0x05040100u), __builtin_amdgcn_perm(b1, a1, 0x07060302u)};
         }
       }
 #pragma unroll

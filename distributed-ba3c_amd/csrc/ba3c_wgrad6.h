@@ -113,17 +113,14 @@ __device__ __forceinline__ void wgrad6_body(const Wg6Args& a, int bx, int by, in
   constexpr int XN = G::XROWS * G::WS * XQ;
   constexpr int XPT = (XN + 255) / 256;
   constexpr int YQ = G::OW / 4;                           // float4 per dY pixel (8)
-  // UNP (BA3C_W6_UNPOOL, default): dY staged per POOLED element — each (pooled pixel, 4
+  // UNP (whole 2-row windows per band): dY staged per POOLED element — each (pooled pixel, 4
   // channels) of dP is loaded and split once and written to the four pixels of its window
   // under per-channel code masks (as wgrad6s / band6r_up): a quarter of the loads and splits,
   // and 5 float4 + 5 code registers per thread fewer held through the k-loop (conv2's pair
   // launch spilled 20 B/lane at 256 VGPRs).  The staged LDS image is the per-pixel one bit for
   // bit (a masked split of v is the split of the masked v; the padded pixels KP .. KPAD - 1 are
   // zeroed once and never written again)
-#ifndef BA3C_W6_UNPOOL
-#define BA3C_W6_UNPOOL 1
-#endif
-  constexpr bool UNP = BA3C_W6_UNPOOL && G::HO % G::RB == 0 && G::RB % 2 == 0;
+  constexpr bool UNP = G::HO % G::RB == 0 && G::RB % 2 == 0;
   constexpr int YN = UNP ? (G::RB / 2) * G::PW * YQ : G::KPAD * YQ;
   constexpr int YPT = (YN + 255) / 256;
   float4 xv[XPT], yv[YPT];
@@ -274,19 +271,16 @@ __device__ __forceinline__ void wgrad6_body(const Wg6Args& a, int bx, int by, in
     const int kvalid = rows_out * G::WO;
     // first window row of this band in the X slots (ring: slot bi & 1)
     const int xbase = ring ? (bi & 1) * G::RB * G::WS * G::PX : 0;
-#ifndef BA3C_DIAG_W6
-#define BA3C_DIAG_W6 0        // diagnostics only (A/B timing): 1 = no staging, 2 = no MFMA loop
-#endif
     __syncthreads();                                      // previous band's LDS reads done
-    if (BA3C_DIAG_W6 != 1) store_band(band);
+    store_band(band);
     __syncthreads();
-    if (BA3C_DIAG_W6 != 1 && band + bstep < band_end) load_band(band + bstep);
+    if (band + bstep < band_end) load_band(band + bstep);
 
 #ifndef BA3C_W6_UNROLL
 #define BA3C_W6_UNROLL 2      // k-steps unrolled per loop iteration: 2 since the pooled staging
 #endif                        // freed the registers (r06l: conv2 pair 0.2157 -> 0.2105 ms; r03: 1 -> 2 spilled)
 #pragma unroll BA3C_W6_UNROLL
-    for (int s = 0; s < (BA3C_DIAG_W6 == 2 ? 0 : G::KS); ++s) {
+    for (int s = 0; s < G::KS; ++s) {
       // this lane's pixel rows for tr reads r = 0, 1
       int xb[2], yb[2];
 #pragma unroll
@@ -319,20 +313,13 @@ __device__ __forceinline__ void wgrad6_body(const Wg6Args& a, int bx, int by, in
           av[sp] = u32x4{u0.x, u0.y, u1.x, u1.y};
         }
       };
-#ifndef BA3C_W6_DBUF
-#define BA3C_W6_DBUF 1
-#endif
       u32x4 avb[2][G::NS];
-      if (BA3C_W6_DBUF) read_a(0, avb[0]);
+      read_a(0, avb[0]);
 #pragma unroll
       for (int t = 0; t < G::TW; ++t) {
         if (t >= ntap) break;
-        if (BA3C_W6_DBUF) {
-          if (t + 1 < ntap) read_a(t + 1, avb[(t + 1) & 1]);
-          __builtin_amdgcn_sched_barrier(0);              // keep those reads ahead of the MFMAs
-        } else {
-          read_a(t, avb[t & 1]);
-        }
+        if (t + 1 < ntap) read_a(t + 1, avb[(t + 1) & 1]);
+        __builtin_amdgcn_sched_barrier(0);                // keep those reads ahead of the MFMAs
         const u32x4 (&av)[G::NS] = avb[t & 1];
         // the family's cross products, interleaved over the two n-blocks
 #pragma unroll
@@ -370,11 +357,11 @@ __device__ __forceinline__ void wgrad6_body(const Wg6Args& a, int bx, int by, in
 // Here one workgroup takes all (tap, c) rows of its images: dY is staged once, X (all 32
 // channels) lives in an XROWS-row window — band i + 1's first HALO rows are band i's last ones
 // and move down with one LDS-to-LDS copy, so only RB new rows are loaded and split — and the
-// workgroup writes one full [M][COUT] partial slab.  Wave w owns a run of 7 / 6 / 6 / 6 taps x
-// both 16-channel c-blocks x both 16-column n-blocks.  Per output the accumulation runs over
-// the same k-steps in the same order as wgrad6_body's (bands in order, 32 permuted pixels per
-// k-step); only the grouping of images into slabs differs.
+// workgroup writes one full [M][COUT] partial slab.  The waves share the (tap, c-block) units
+// (Wg6WUnits) and run them on the 2:4-sparse MFMA (wgrad6s_units); the dense body this began
+// as (un-pooled dY in LDS, wgrad6_body's k-order) lost to it and is gone.
 
+// (PY_ was the dense body's dY pixel pitch: unused, kept for the kernels' names)
 template <int HS_, int WS_, int CIN_, int COUT_, int RB_, int PX_, int PY_>
 struct Wg6WGeom {
   static constexpr int NS = 2;
@@ -382,16 +369,14 @@ struct Wg6WGeom {
   static constexpr int KH = 5, KW = 5, NTAP = 25;
   static constexpr int HO = HS - KH + 1, WO = WS - KW + 1, PH = HO / 2, PW = WO / 2;
   static constexpr int NBANDS = HO / RB;
-  static constexpr int KP = RB * WO, KS = (KP + 31) / 32, KPAD = 32 * KS;
   static constexpr int HALO = KH - 1, XROWS = RB + HALO;
-  static constexpr int PX = PX_, PY = PY_;
-  static constexpr int XSB = 2 * CIN, YSB = 2 * COUT;
-  static constexpr int X_BYTES = XROWS * WS * PX, Y_BYTES = KPAD * PY;
-  static constexpr int CB = CIN / 16, NB = COUT / 16;
-  static constexpr int TBASE = NTAP / 4, TREM = NTAP % 4, TW = TBASE + (TREM > 0);
+  static constexpr int PX = PX_;
+  static constexpr int XSB = 2 * CIN;
+  static constexpr int X_BYTES = XROWS * WS * PX;
+  static constexpr int CB = CIN / 16;
   static constexpr int M = NTAP * CIN;
   static_assert(HO % RB == 0 && RB == HALO, "whole bands; the halo copy's ranges are disjoint");
-  static_assert(PX >= NS * XSB && PY >= NS * YSB && PX % 32 == 0 && PY % 32 == 0, "pitches");
+  static_assert(PX >= NS * XSB && PX % 32 == 0, "pitches");
   static_assert(RB * WS * (CIN / 4) % 256 == 0, "new X rows: whole float4 per thread");
   static_assert(X_BYTES % 16 == 0 && (HALO * WS * PX) % 16 == 0, "wgrad6w geometry");
   // 2:4-sparse layout (wgrad6s_units): K = quads of 4 consecutive output pixels of one row (two
@@ -410,319 +395,21 @@ using Conv1W6W = Wg6WGeom<40, 40, 32, 32, 4, 160, 160>;
 
 // Work units of a workgroup: (tap, c-block) pairs u = 2 tap + cb, 50 of them for 25 taps x 2
 // c-blocks; a unit's A fragments feed both n-blocks (6 MFMAs per k-step).  Wave w owns units
-// [U0, U0 + NU).  BA3C_W6W_BAL=1 (default): 13 / 13 / 12 / 12 units — the r03/r04 split was
-// whole taps, 7 / 6 / 6 / 6 = 14 / 12 / 12 / 12 units, and every band waited for the 14-unit
-// wave (25 / 28 of the MFMA pipes busy).  Per output the k-order is unchanged, so the slabs
-// are bit-identical either way.
-#ifndef BA3C_W6W_BAL
-#define BA3C_W6W_BAL 1
-#endif
-#ifndef BA3C_W6W_PF
-#define BA3C_W6W_PF 1
-#endif
+// [U0, U0 + NU), a balanced 13 / 13 / 12 / 12 units — the r03/r04 split was whole taps,
+// 7 / 6 / 6 / 6 = 14 / 12 / 12 / 12 units, and every band waited for the 14-unit wave (25 / 28
+// of the MFMA pipes busy).  Per output the k-order is unchanged, so the slabs were
+// bit-identical either way.
 template <class G>
 struct Wg6WUnits {
   static constexpr int UNITS = G::NTAP * G::CB;
   static constexpr int BASE = UNITS / 4, REM = UNITS % 4;
-  __host__ __device__ static constexpr int u0(int w) {
-    return BA3C_W6W_BAL ? w * BASE + (w < REM ? w : REM)
-                        : G::CB * (w * G::TBASE + (w < G::TREM ? w : G::TREM));
-  }
+  __host__ __device__ static constexpr int u0(int w) { return w * BASE + (w < REM ? w : REM); }
   __host__ __device__ static constexpr int nu(int w) { return u0(w + 1) - u0(w); }
-  static constexpr int MAXU = BA3C_W6W_BAL ? BASE + (REM > 0) : G::CB * G::TW;
+  static constexpr int MAXU = BASE + (REM > 0);
 };
 
-template <class G, int U0, int NU>
-__device__ __forceinline__ void wgrad6w_units(const Wg6Args& a, int bx, int gx, char* xs, uint32_t* red4) {
-  using SP = SplitP<G::NS>;
-  const int kx = amax_exp(amax_all(a.amax_x, a.batch, red4));
-  const int ky = amax_exp(amax_all(a.amax_dp, a.batch, red4));
-  const float xsc = exp2i(kx), ysc = exp2i(ky);
-  char* ys = xs + G::X_BYTES;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int g = lane >> 4, q = (lane >> 2) & 3, pq = lane & 3;
-  const int kperm = 16 * (g >> 1) + 4 * (g & 1) + q;      // + 8 r for read r (wgrad6_body)
-
-  f32x4 acc[NU][G::NB];
-#pragma unroll
-  for (int u = 0; u < NU; ++u)
-#pragma unroll
-    for (int nb = 0; nb < G::NB; ++nb) acc[u][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  constexpr int XQ = G::CIN / 4;                          // float4 per X pixel
-  constexpr int XPT = G::RB * G::WS * XQ / 256;           // float4 of RB rows per thread
-  constexpr int YQ = G::COUT / 4;
-#ifndef BA3C_W6W_UNPOOL
-#define BA3C_W6W_UNPOOL 1     // dY staged per pooled element (0: per un-pooled pixel, A/B)
-#endif
-  // UNP: each (pooled pixel, 4 channels) of dP is loaded and split once and written to the four
-  // pixels of its window with per-channel masks (as band6r_up_body); the padded pixels KP ..
-  // KPAD - 1 are zeroed once and never written again
-  constexpr bool UNP = BA3C_W6W_UNPOOL;
-  constexpr int YN = UNP ? (G::RB / 2) * G::PW * YQ : G::KPAD * YQ;
-  constexpr int YPT = (YN + 255) / 256;
-  float4 xv[XPT], yv[YPT];
-  uint32_t yc[YPT];
-
-  const int ipw = (a.batch + gx - 1) / gx;                // whole images per workgroup
-  const int img0 = min(a.batch, bx * ipw), img1 = min(a.batch, img0 + ipw);
-  const int band_end = img1 * G::NBANDS;
-
-  // RB image rows from row y of image img -> registers
-  auto load_x = [&](int img, int y, float4 (&v)[XPT]) {
-    const float* src = a.x + ((size_t)(img * G::HS + y) * G::WS) * G::CIN;
-#pragma unroll
-    for (int i = 0; i < XPT; ++i) v[i] = reinterpret_cast<const float4*>(src)[tid + 256 * i];
-  };
-  auto load_y = [&](int img, int bi) {
-    const int y0 = bi * G::RB;
-    if constexpr (UNP) {
-#pragma unroll
-      for (int i = 0; i < YPT; ++i) {
-        const int f = tid + 256 * i;
-        const int oq = f % YQ, rest = f / YQ;
-        const int pc = rest % G::PW, py = (y0 >> 1) + rest / G::PW;
-        const bool ok = f < YN;                         // branch-free (see wgrad6_body)
-        const size_t off = ok ? ((size_t)(img * G::PH + py) * G::PW + pc) * G::COUT + oq * 4 : 0;
-        yv[i] = ld4(a.dp + off, ok);
-        yc[i] = ld_u8x4(a.code + off, ok);
-      }
-      return;
-    }
-#pragma unroll
-    for (int i = 0; i < YPT; ++i) {
-      const int f = tid + 256 * i;
-      const int p = f / YQ, oq = f - p * YQ;
-      const int ry = p / G::WO, x = p - ry * G::WO;
-      yv[i] = f4zero();
-      yc[i] = 0;
-      if (f < YN && ry < G::RB) {
-        const int y = y0 + ry;
-        const size_t pidx = (size_t)(img * G::PH + (y >> 1)) * G::PW + (x >> 1);
-        yv[i] = *reinterpret_cast<const float4*>(a.dp + pidx * G::COUT + oq * 4);
-        yc[i] = *reinterpret_cast<const uint32_t*>(a.code + pidx * G::COUT + oq * 4);
-      }
-    }
-  };
-  // RB rows -> window rows wr .. wr + RB - 1, split
-  auto store_x = [&](int wr, const float4 (&v)[XPT]) {
-#pragma unroll
-    for (int i = 0; i < XPT; ++i) {
-      const int f = tid + 256 * i;
-      const int pix = f / XQ, cq = f - pix * XQ;
-      uint32_t s0[G::NS], s1[G::NS];
-      SP::split(v[i].x, v[i].y, xsc, s0);
-      SP::split(v[i].z, v[i].w, xsc, s1);
-      char* p = xs + (wr * G::WS + pix) * G::PX + cq * 8;
-#pragma unroll
-      for (int sp = 0; sp < G::NS; ++sp) *reinterpret_cast<uint2*>(p + sp * G::XSB) = make_uint2(s0[sp], s1[sp]);
-    }
-  };
-  auto store_y = [&](int bi) {
-    const int y0 = bi * G::RB;
-    if constexpr (UNP) {
-#pragma unroll
-      for (int i = 0; i < YPT; ++i) {
-        const int f = tid + 256 * i;
-        if (f < YN) {
-          const int oq = f % YQ, rest = f / YQ;
-          const int pc = rest % G::PW, pr = rest / G::PW;
-          uint32_t s0[G::NS], s1[G::NS];
-          SP::split(yv[i].x, yv[i].y, ysc, s0);
-          SP::split(yv[i].z, yv[i].w, ysc, s1);
-          const uint32_t c01 = __builtin_amdgcn_perm(yc[i], yc[i], 0x0C010C00u);   // codes as halves
-          const uint32_t c23 = __builtin_amdgcn_perm(yc[i], yc[i], 0x0C030C02u);
-          char* base = ys + ((2 * pr) * G::WO + 2 * pc) * G::PY + oq * 8;
-#pragma unroll
-          for (int sub = 0; sub < 4; ++sub) {
-            const uint32_t S = (uint32_t)sub * 0x00010001u;
-            const uint32_t m01 = w6_mask16_eq0(c01 ^ S), m23 = w6_mask16_eq0(c23 ^ S);
-            char* d = base + ((sub >> 1) * G::WO + (sub & 1)) * G::PY;
-#pragma unroll
-            for (int sp = 0; sp < G::NS; ++sp)
-              *reinterpret_cast<uint2*>(d + sp * G::YSB) = make_uint2(s0[sp] & m01, s1[sp] & m23);
-          }
-        }
-      }
-      return;
-    }
-#pragma unroll
-    for (int i = 0; i < YPT; ++i) {
-      const int f = tid + 256 * i;
-      if (f < YN) {
-        const int p = f / YQ, oq = f - p * YQ;
-        const int ry = p / G::WO, x = p - ry * G::WO;
-        const uint32_t sb = (((y0 + ry) & 1) << 1) | (x & 1), c = yc[i];
-        float e[4] = {yv[i].x, yv[i].y, yv[i].z, yv[i].w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) e[k] = ((c >> (8 * k)) & 255u) == sb ? e[k] : 0.f;
-        uint32_t s0[G::NS], s1[G::NS];
-        SP::split(e[0], e[1], ysc, s0);
-        SP::split(e[2], e[3], ysc, s1);
-        char* d = ys + p * G::PY + oq * 8;
-#pragma unroll
-        for (int sp = 0; sp < G::NS; ++sp) *reinterpret_cast<uint2*>(d + sp * G::YSB) = make_uint2(s0[sp], s1[sp]);
-      }
-    }
-  };
-
-  if constexpr (UNP) {
-    // padded pixels KP .. KPAD - 1 of dY stay zero (the pooled items never write them)
-    for (int i = tid; i < (G::KPAD - G::KP) * G::PY / 16; i += 256)
-      reinterpret_cast<uint4*>(ys + G::KP * G::PY)[i] = make_uint4(0, 0, 0, 0);
-  }
-  int band = img0 * G::NBANDS;
-  if (band < band_end) {
-    load_x(img0, G::HALO, xv);
-    load_y(img0, 0);
-  }
-  for (; band < band_end; ++band) {
-    const int img = band / G::NBANDS;
-    const int bi = band - img * G::NBANDS;
-    __syncthreads();                                      // previous band's LDS reads are done
-    if (bi > 0) {
-      // window rows RB .. RB + HALO - 1 -> 0 .. HALO - 1 (disjoint); every wave's copy is
-      // complete before any wave stores the new rows over the source rows (barrier)
-      constexpr int N16 = G::HALO * G::WS * G::PX / 16;
-      const uint4* src = reinterpret_cast<const uint4*>(xs + G::RB * G::WS * G::PX);
-      uint4* dst = reinterpret_cast<uint4*>(xs);
-      for (int i = tid; i < N16; i += 256) dst[i] = src[i];
-      __syncthreads();
-    }
-    store_x(G::HALO, xv);
-    store_y(bi);
-    if (bi == 0) {                                        // an image's first HALO rows
-      load_x(img, 0, xv);
-      store_x(0, xv);
-    }
-    __syncthreads();
-    if (band + 1 < band_end) {
-      const int ni = (band + 1) / G::NBANDS, nbi = band + 1 - ni * G::NBANDS;
-      load_x(ni, nbi * G::RB + G::HALO, xv);
-      load_y(ni, nbi);
-    }
-    // software-pipelined k-steps: unit u + 1's A fragments are read before unit u's MFMAs, and
-    // during the last unit of a k-step the next k-step's B fragments and its first unit's A
-    // fragments (r04 ISA: each tap's reads were issued ~2 MFMAs ahead of their use and every
-    // k-step opened with a full LDS round trip, at one wave per SIMD nothing hid them)
-    int xb[2];
-    auto addr = [&](int s, int (&xbo)[2], int (&ybo)[2]) {
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        int p = 32 * s + kperm + 8 * r;
-        ybo[r] = p * G::PY + 8 * pq;
-        if (p >= G::KP) p = 0;                            // padded pixels: dY is zero
-        const int y = p / G::WO, x = p - y * G::WO;
-        xbo[r] = (y * G::WS + x) * G::PX + 8 * pq;
-      }
-    };
-    auto read_b = [&](const int (&ybo)[2], u32x4 (&bo)[G::NB][G::NS]) {
-#pragma unroll
-      for (int nb = 0; nb < G::NB; ++nb)
-#pragma unroll
-        for (int sp = 0; sp < G::NS; ++sp) {
-          const uint2 u0 = lds_tr16(ys + ybo[0] + nb * 32 + sp * G::YSB);
-          const uint2 u1 = lds_tr16(ys + ybo[1] + nb * 32 + sp * G::YSB);
-          bo[nb][sp] = u32x4{u0.x, u0.y, u1.x, u1.y};
-        }
-    };
-    auto read_a = [&](int u, const int (&xbo)[2], u32x4 (&av)[G::NS]) {
-      const int unit = U0 + u, tap = unit / G::CB, cb = unit - tap * G::CB;
-      const int kh = tap / G::KW, kw = tap - kh * G::KW;
-      const int off = (kh * G::WS + kw) * G::PX + cb * 32;   // compile-time
-#pragma unroll
-      for (int sp = 0; sp < G::NS; ++sp) {
-        const uint2 u0 = lds_tr16(xs + xbo[0] + off + sp * G::XSB);
-        const uint2 u1 = lds_tr16(xs + xbo[1] + off + sp * G::XSB);
-        av[sp] = u32x4{u0.x, u0.y, u1.x, u1.y};
-      }
-    };
-    // D: units of lookahead for the A fragments (BA3C_W6W_PF, A/B)
-    constexpr int D = BA3C_W6W_PF, NBUF = D + 1;
-    static_assert(D >= 1 && D < NU, "prefetch distance");
-    u32x4 b[G::NB][G::NS], bn[G::NB][G::NS], avb[NBUF][G::NS];
-    {
-      int yb[2];
-      addr(0, xb, yb);
-      read_b(yb, b);
-#pragma unroll
-      for (int j = 0; j < D; ++j) read_a(j, xb, avb[j]);
-    }
-    // one k-step; PF: prefetch the next k-step's B and first D units' A fragments (all but
-    // the last k-step of a band)
-    auto kstep = [&](int s, auto pf) {
-      constexpr bool PF = decltype(pf)::value;
-      int xbn[2], ybn[2];
-#pragma unroll
-      for (int u = 0; u < NU; ++u) {
-        const int v = u + D;                              // the unit whose A is read now
-        if (v < NU) {
-          read_a(v, xb, avb[v % NBUF]);
-        } else if (PF) {
-          if (v == NU) {
-            addr(s + 1, xbn, ybn);
-            read_b(ybn, bn);
-          }
-          read_a(v - NU, xbn, avb[v % NBUF]);
-        }
-        __builtin_amdgcn_sched_barrier(0);                // keep those reads ahead of the MFMAs
-        const u32x4 (&av)[G::NS] = avb[u % NBUF];
-#pragma unroll
-        for (int pr = 0; pr < SP::NPROD; ++pr)
-#pragma unroll
-          for (int nb = 0; nb < G::NB; ++nb)
-            acc[u][nb] = SP::mfma(av[SP::pa(pr)], b[nb][SP::pb(pr)], acc[u][nb]);
-      }
-      if (PF) {
-#pragma unroll
-        for (int nb = 0; nb < G::NB; ++nb)
-#pragma unroll
-          for (int sp = 0; sp < G::NS; ++sp) b[nb][sp] = bn[nb][sp];
-        xb[0] = xbn[0];
-        xb[1] = xbn[1];
-        // the next step's units 0 .. D - 1 were read into buffers NU % NBUF ..: rotate
-        u32x4 t[D][G::NS];
-#pragma unroll
-        for (int j = 0; j < D; ++j)
-#pragma unroll
-          for (int sp = 0; sp < G::NS; ++sp) t[j][sp] = avb[(NU + j) % NBUF][sp];
-#pragma unroll
-        for (int j = 0; j < D; ++j)
-#pragma unroll
-          for (int sp = 0; sp < G::NS; ++sp) avb[j][sp] = t[j][sp];
-      }
-    };
-#ifndef BA3C_W6W_PRIO
-#define BA3C_W6W_PRIO 0       // A/B: the k-steps at wave priority 1 (the staging at 0)
-#endif
-    if (BA3C_W6W_PRIO) __builtin_amdgcn_s_setprio(1);
-#pragma unroll 1
-    for (int s = 0; s + 1 < G::KS; ++s) kstep(s, std::true_type{});
-    kstep(G::KS - 1, std::false_type{});
-    if (BA3C_W6W_PRIO) __builtin_amdgcn_s_setprio(0);
-  }
-
-  // ---- epilogue: one full slab per workgroup (lane: column o = 16 nb + (lane & 15), rows
-  // c = 16 cb + 4 (lane >> 4) + r) ----
-  float* pz = a.part + (size_t)bx * G::M * G::COUT;
-  const float us1 = exp2i(-kx), us2 = exp2i(-ky);
-#pragma unroll
-  for (int u = 0; u < NU; ++u) {
-    const int unit = U0 + u, tap = unit / G::CB, cb = unit - tap * G::CB;
-#pragma unroll
-    for (int nb = 0; nb < G::NB; ++nb) {
-      const int o = nb * 16 + (lane & 15);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int c = cb * 16 + 4 * (lane >> 4) + r;
-        pz[((size_t)tap * G::CIN + c) * G::COUT + o] = acc[u][nb][r] * us1 * us2;
-      }
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------------
-// 2:4-sparse conv1 weight gradient (BA3C_W6W_SPARSE=1, default).  The un-pooled output
+// 2:4-sparse conv1 weight gradient (wgrad6w_body's units).  The un-pooled output
 // gradient dY = MaxPoolGrad(dP) * ReluGrad has at most ONE non-zero per 2x2 window and channel,
 // so along a row of output pixels every group of 4 consecutive pixels (two windows) holds at
 // most 2 non-zeros per channel: exactly the 2:4 structured sparsity of gfx950's
@@ -736,18 +423,9 @@ __device__ __forceinline__ void wgrad6w_units(const Wg6Args& a, int bx, int gx, 
 //    0 / 1, in window 1: 2 / 3).  Staged once per band from the POOLED dP (no un-pooling).
 //  * B (X): lane l = channel l & 15 of the unit, K = quads 2g, 2g + 1, 8 + 2g, 9 + 2g (g = l >>
 //    4) of the k-step: four ds_read_b64_tr_b16 of 4 pixels each per plane.
-// Same products (dY_hi X_hi, dY_hi X_lo, dY_lo X_hi), same scales, same slabs; the k-order
-// differs from the dense body, so the sums agree to rounding, not bit for bit.
+// Same products (dY_hi X_hi, dY_hi X_lo, dY_lo X_hi), same scales and same slabs as the dense
+// body it replaced; the k-order differed, so the sums agreed to rounding, not bit for bit.
 // ---------------------------------------------------------------------------------------
-#ifndef BA3C_W6W_SPARSE
-#define BA3C_W6W_SPARSE 1
-#endif
-#ifndef BA3C_W6S_HALF
-#define BA3C_W6S_HALF 1       // the band's last 4 quads on a half-size sparse k-step (0: a padded full one)
-#endif
-#ifndef BA3C_DIAG_W6S
-#define BA3C_DIAG_W6S 0       // diagnostics only (A/B timing): 1 = no band staging, 2 = no MFMA loop
-#endif
 typedef _Float16 f16x16v __attribute__((ext_vector_type(16)));
 
 // Logical quad J (the MFMA's K / 4) -> physical quad of the k-step: bits 0 and 1 swapped
@@ -855,51 +533,36 @@ __device__ __forceinline__ void wgrad6s_units(const Wg6Args& a, int bx, int gx, 
     reinterpret_cast<uint32_t*>(yq)[row * G::QS + Q] = 0u;
     if (row < G::COUT) yi[row * G::QS + Q] = (uint8_t)(2u << 2);
   }
-  // BA3C_W6S_XPF: 1 = the next band's new X rows are loaded into registers before this band's
-  // k-steps and held through them; 0 (default) = loaded at the start of the band's staging.
-  // Holding them put the pair kernel at 256 VGPRs with 44 B/lane of scratch (loop constants
-  // spilled and reloaded in every band's staging); the exposed load is hidden by the conv0
-  // workgroup beside it: same-box r06j, pair 0.4218 -> 0.3928 ms, step 1.739 -> 1.712 ms
-#ifndef BA3C_W6S_XPF
-#define BA3C_W6S_XPF 0
-#endif
-  // BA3C_W6S_APF (A/B): 1 (default) = the next k-step's A words and index nibbles are read
-  // during the last unit of a k-step; 0 = at the k-step's end (16 + 2 fewer live VGPRs)
-#ifndef BA3C_W6S_APF
-#define BA3C_W6S_APF 1
-#endif
+  // The band's new X rows are loaded at the start of its staging.  Loading the next band's
+  // before this band's k-steps and holding them through put the pair kernel at 256 VGPRs with
+  // 44 B/lane of scratch (loop constants spilled and reloaded in every band's staging); the
+  // exposed load is hidden by the conv0 workgroup beside it: same-box r06j, pair 0.4218 ->
+  // 0.3928 ms, step 1.739 -> 1.712 ms
   int band = img0 * G::NBANDS;
-  if (band < band_end) {
-    if (BA3C_W6S_XPF) load_x(img0, G::HALO, xv);
-    load_y(img0, 0);
-  }
+  if (band < band_end) load_y(img0, 0);
   for (; band < band_end; ++band) {
     const int img = band / G::NBANDS;
     const int bi = band - img * G::NBANDS;
-    if (!BA3C_W6S_XPF && BA3C_DIAG_W6S != 1) load_x(img, bi * G::RB + G::HALO, xv);
+    load_x(img, bi * G::RB + G::HALO, xv);
     __syncthreads();                                      // previous band's LDS reads are done
-    if (BA3C_DIAG_W6S != 1 && bi > 0) {
+    if (bi > 0) {
       constexpr int N16 = G::HALO * G::WS * G::PX / 16;
       const uint4* src = reinterpret_cast<const uint4*>(xs + G::RB * G::WS * G::PX);
       uint4* dst = reinterpret_cast<uint4*>(xs);
       for (int i = tid; i < N16; i += 256) dst[i] = src[i];
       __syncthreads();
     }
-    if (BA3C_DIAG_W6S != 1) {
-      store_x(G::HALO, xv);
-      store_y();
-      if (bi == 0) {
-        load_x(img, 0, xv);
-        store_x(0, xv);
-      }
+    store_x(G::HALO, xv);
+    store_y();
+    if (bi == 0) {
+      load_x(img, 0, xv);
+      store_x(0, xv);
     }
     __syncthreads();
-    if (BA3C_DIAG_W6S != 1 && band + 1 < band_end) {
+    if (band + 1 < band_end) {
       const int ni = (band + 1) / G::NBANDS, nbi = band + 1 - ni * G::NBANDS;
-      if (BA3C_W6S_XPF) load_x(ni, nbi * G::RB + G::HALO, xv);
       load_y(ni, nbi);
     }
-    if (BA3C_DIAG_W6S == 2) continue;
 
     // per k-step: the lane's four quad pixel bases (B reads) and its A / index words
     int xq[4];
@@ -954,8 +617,9 @@ __device__ __forceinline__ void wgrad6s_units(const Wg6Args& a, int bx, int gx, 
         if (u + 1 < NU) {
           read_b(u + 1, xq, bb[(u + 1) & 1]);
         } else if (PF) {
+          // the next k-step's A words and index nibbles, read during this k-step's last unit
           addr(s + 1, xn);
-          if (BA3C_W6S_APF) read_a(s + 1, avn, ixn);
+          read_a(s + 1, avn, ixn);
           read_b(0, xn, bb[NU & 1]);
         }
         __builtin_amdgcn_sched_barrier(0);                // keep those reads ahead of the MFMAs
@@ -977,15 +641,11 @@ __device__ __forceinline__ void wgrad6s_units(const Wg6Args& a, int bx, int gx, 
                 __builtin_bit_cast(f16x8, av[m][pr == 2 ? 1 : 0]), b16[pr == 1 ? 1 : 0], acc[u][m], (int)ix[m], 0, 0);
       }
       if (PF) {
-        if (BA3C_W6S_APF) {
 #pragma unroll
-          for (int m = 0; m < 2; ++m) {
-            av[m][0] = avn[m][0];
-            av[m][1] = avn[m][1];
-            ix[m] = ixn[m];
-          }
-        } else {
-          read_a(s + 1, av, ix);                          // (not prefetched: read here)
+        for (int m = 0; m < 2; ++m) {
+          av[m][0] = avn[m][0];
+          av[m][1] = avn[m][1];
+          ix[m] = ixn[m];
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) xq[r] = xn[r];
@@ -1000,7 +660,7 @@ __device__ __forceinline__ void wgrad6s_units(const Wg6Args& a, int bx, int gx, 
     };
     // a band of NQ = 16 SKF + r quads with 0 < r <= 8 ends in a half k-step: the last 8 slots on
     // v_smfmac_f32_16x16x32_f16 (conv1: 36 quads issue 40 instead of 48)
-    constexpr bool HALF = BA3C_W6S_HALF && G::NQ % 16 != 0 && G::NQ % 16 <= 8;
+    constexpr bool HALF = G::NQ % 16 != 0 && G::NQ % 16 <= 8;
     constexpr int SKF = HALF ? G::SKS - 1 : G::SKS;
 #pragma unroll 1
     for (int s = 0; s + 1 < SKF; ++s) kstep(s, std::true_type{});
@@ -1073,21 +733,17 @@ __device__ __forceinline__ void wgrad6w_body(const Wg6Args& a, int bx, int gx, c
   using U = Wg6WUnits<G>;
   static_assert(U::u0(4) == U::UNITS && U::nu(0) <= U::MAXU, "unit partition");
   switch (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) {
-#define BA3C_W6W_CASE(w)                                                                  \
-    if constexpr (BA3C_W6W_SPARSE) wgrad6s_units<G, U::u0(w), U::nu(w)>(a, bx, gx, xs, red4); \
-    else wgrad6w_units<G, U::u0(w), U::nu(w)>(a, bx, gx, xs, red4);
-    case 0: BA3C_W6W_CASE(0) break;
-    case 1: BA3C_W6W_CASE(1) break;
-    case 2: BA3C_W6W_CASE(2) break;
-    default: BA3C_W6W_CASE(3) break;
-#undef BA3C_W6W_CASE
+    case 0: wgrad6s_units<G, U::u0(0), U::nu(0)>(a, bx, gx, xs, red4); break;
+    case 1: wgrad6s_units<G, U::u0(1), U::nu(1)>(a, bx, gx, xs, red4); break;
+    case 2: wgrad6s_units<G, U::u0(2), U::nu(2)>(a, bx, gx, xs, red4); break;
+    default: wgrad6s_units<G, U::u0(3), U::nu(3)>(a, bx, gx, xs, red4); break;
   }
 }
 
-// LDS bytes of wgrad6w_body (dense: X window + un-pooled dY; sparse: X window + quads)
+// LDS bytes of wgrad6w_body (X window + quads)
 template <class G>
 __host__ __device__ constexpr int wgrad6w_lds_bytes() {
-  return BA3C_W6W_SPARSE ? G::S_BYTES : G::X_BYTES + G::Y_BYTES;
+  return G::S_BYTES;
 }
 
 template <class G>

@@ -173,10 +173,12 @@ int ba3c_train_grads_phase(ba3c_handle* h, void* stream, const float* params, co
  * variables' gradients of OpenAIGym/train.py:598-606 (their aggregation starts from here). */
 int ba3c_launch_held(ba3c_handle* h, void* stream);
 /* Record the HIP event `event` (a hipEvent_t of the caller's, NULL: none) on the pass's stream
- * in every later phase-2 pass, right after conv3's gradient launches: the N>1 step starts the
- * fc1 + heads bucket's exchange from there, so its collective's workgroups take CUs at the
- * boundary before conv2's launch (short, non-persistent workgroups the dispatcher rebalances)
- * instead of beside conv3's persistent ones. */
+ * in every later phase-2 pass, right after conv3's input-gradient launch and its weight
+ * gradient's (with BA3C_C3W_RIDE set the weight gradient is a job of conv2's launch and runs
+ * after the event; the event only has to follow phase 1): the N>1 step starts the fc1 + heads
+ * bucket's exchange from there, so its collective's workgroups take CUs at the boundary before
+ * conv2's launch (short, non-persistent workgroups the dispatcher rebalances) instead of
+ * beside conv3's persistent ones. */
 int ba3c_set_phase2_event(ba3c_handle* h, void* event);
 /* Launch a reduction that a phase-3 pass left pending, on the pass's stream (no-op when none
  * is pending; also launches a held phase-4 reduction).  For callers that read `grads` through another API (a torch view, a gradient
