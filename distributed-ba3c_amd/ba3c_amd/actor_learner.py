@@ -63,7 +63,7 @@ class ActorLearner(object):
     def __init__(self, trainer, n_envs, batch_size, seed=0, rs=None, on_train_step=None,
                  dummy_predictor=False, env=None):
         """env: the vector of simulators (None: SyntheticAtari, as before); an env with
-        `step_into(actions, hist)` (ba3c_amd.breakout.BreakoutVec) is stepped through it, the
+        `step_into(actions, hist)` (BreakoutVec, BoxingVec) is stepped through it, the
         frame-history push fused into the env's launch.
         on_train_step(trainer): called after every learner step (callbacks / metrics);
         dummy_predictor: --dummy_predictor 1 (predict/base.py:94-105) — uniform policy and

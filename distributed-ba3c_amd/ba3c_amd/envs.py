@@ -365,17 +365,145 @@ class BreakoutPlayer(RLEnvironment):
         return self.space
 
 
+class BoxingPlayer(RLEnvironment):
+    """GridBoxing (ba3c_amd.boxing holds the rules and constants) as one host player, for the
+    simulator processes: the same integer rules as scalar Python ints.  Auto-restarts like
+    GymEnv and records the episode 'score' stat (agent minus opponent) in finish_episode.
+    `limit` (None: none) ends an episode after that many steps; get_player leaves that to
+    LimitLengthPlayer.  `last_events` names what the last action() met, from: hit1, hit2, miss,
+    got1, got2, ko_win, ko_loss, over_clock, over_limit."""
+
+    def __init__(self, idx=0, num_actions=18, seed=0, limit=None):
+        super(BoxingPlayer, self).__init__()
+        from . import boxing as K
+        self.K = K
+        self.idx = int(idx)
+        self.limit = limit
+        self.rng = (int(seed) * 1000 + self.idx) % (1 << 32)
+        self.space = DiscreteActionSpace(int(num_actions), seed=seed + 1)
+        self.last_events = set()
+        self.last_ep_score = None
+        self.restart_episode()
+
+    def restart_episode(self):
+        K = self.K
+        self.ax, self.ay, self.ox, self.oy = K.AX0, K.AY0, K.OX0, K.OY0
+        self.a_cd = self.o_cd = self.a_score = self.o_score = self.t = 0
+
+    def finish_episode(self):
+        self.stats["score"].append(self.a_score - self.o_score)
+
+    def game_row(self):
+        """The episode state as the device's int32 row (boxing.py layout)."""
+        rng = self.rng - (1 << 32) if self.rng >= (1 << 31) else self.rng
+        return [self.ax, self.ay, self.ox, self.oy, self.a_cd, self.o_cd, self.a_score,
+                self.o_score, self.t, rng, 0, 0, 0, 0, 0, 0]
+
+    def current_state(self):
+        K = self.K
+        f = np.zeros((K.H, K.W), np.uint8)
+        f[K.RING_Y0, K.RING_X0:K.RING_X1 + 1] = f[K.RING_Y1, K.RING_X0:K.RING_X1 + 1] = K.DIM
+        f[K.RING_Y0:K.RING_Y1 + 1, K.RING_X0] = f[K.RING_Y0:K.RING_Y1 + 1, K.RING_X1] = K.DIM
+        f[K.CLOCK_Y, :max(K.W - self.t // K.CLOCK_DIV, 0)] = K.DIM
+        f[K.O_BAR_Y:K.O_BAR_Y + 2, K.W - self.o_score // 2:] = K.OPP_SHADE
+        f[K.A_BAR_Y:K.A_BAR_Y + 2, :self.a_score // 2] = K.AGENT_SHADE
+        # later paints win: opponent arm, opponent body, agent arm, agent body
+        for x, y, cd, arm_left, shade in (
+                (self.ox, self.oy, self.o_cd, self.ox >= self.ax, K.OPP_SHADE),
+                (self.ax, self.ay, self.a_cd, not self.ax <= self.ox, K.AGENT_SHADE)):
+            if cd >= K.ARM_CD:
+                x0 = x - K.ARM_W if arm_left else x + K.BODY_W
+                f[y + K.ARM_ROW:y + K.ARM_ROW + K.ARM_H, x0:x0 + K.ARM_W] = shade
+            f[y:y + K.BODY_H, x:x + K.BODY_W] = shade
+        return f
+
+    def _pts(self):
+        K = self.K
+        gx, gy = abs(self.ax - self.ox), abs(self.ay - self.oy)
+        if gy > K.REACH_Y or gx > K.REACH_FAR:
+            return 0
+        return 2 if gx <= K.REACH_NEAR else 1
+
+    def action(self, act):
+        K = self.K
+        ev = set()
+        act = int(act)
+        if not 0 <= act < K.NUM_ACTIONS:
+            act = K.NOOP
+        clamp = lambda v, lo, hi: min(max(v, lo), hi)
+        sign = lambda v: (v > 0) - (v < 0)
+        reward = 0
+        dx = (act in K.RIGHT_SET) - (act in K.LEFT_SET)
+        dy = (act in K.DOWN_SET) - (act in K.UP_SET)
+        self.a_cd = max(self.a_cd - 1, 0)
+        self.o_cd = max(self.o_cd - 1, 0)
+        self.rng = (self.rng * K.LCG_A + K.LCG_C) % (1 << 32)
+        r = self.rng >> 16
+        self.ax = clamp(self.ax + K.AGENT_STEP * dx, K.X_MIN, K.X_MAX)
+        self.ay = clamp(self.ay + K.AGENT_STEP * dy, K.Y_MIN, K.Y_MAX)
+        if r & 3:
+            s, gap = sign(self.ax - self.ox), abs(self.ax - self.ox)
+            ody = sign(self.ay - self.oy)
+            if gap > K.CLOSE_FAR:
+                odx = s
+            elif gap < K.CLOSE_NEAR:
+                odx = -s if s != 0 else 1
+            else:
+                odx = 0
+        else:
+            odx, ody = ((r >> 2) % 3) - 1, ((r >> 4) % 3) - 1
+        self.ox = clamp(self.ox + K.OPP_STEP * odx, K.X_MIN, K.X_MAX)
+        self.oy = clamp(self.oy + K.OPP_STEP * ody, K.Y_MIN, K.Y_MAX)
+        if act in K.FIRE_SET and self.a_cd == 0:
+            self.a_cd = K.COOLDOWN
+            p = self._pts()
+            ev.add("hit%d" % p if p else "miss")
+            if p:
+                reward += p
+                self.a_score += p
+                self.ox = clamp(self.ox + (K.KNOCK if self.ox >= self.ax else -K.KNOCK),
+                                K.X_MIN, K.X_MAX)
+        if self.o_cd == 0 and ((r >> 8) & 1) == 0 and self._pts() > 0:
+            self.o_cd = K.COOLDOWN
+            p = self._pts()
+            ev.add("got%d" % p)
+            reward -= p
+            self.o_score += p
+            self.ax = clamp(self.ax + (K.KNOCK if self.ax > self.ox else -K.KNOCK),
+                            K.X_MIN, K.X_MAX)
+        self.t += 1
+        if self.a_score >= K.KO:
+            ev.add("ko_win")
+        if self.o_score >= K.KO:
+            ev.add("ko_loss")
+        if self.t >= K.CLOCK:
+            ev.add("over_clock")
+        if self.limit is not None and self.t >= self.limit:
+            ev.add("over_limit")
+        over = bool(ev & {"ko_win", "ko_loss", "over_clock", "over_limit"})
+        if over:
+            self.last_ep_score = self.a_score - self.o_score
+            self.finish_episode()
+            self.restart_episode()
+        self.last_events = ev
+        return float(reward), over
+
+    def get_action_space(self):
+        return self.space
+
+
+# game key -> the host player of get_player / SyntheticSimulatorWorker
+PLAYERS = {"synthetic": SyntheticAtariPlayer, "breakout": BreakoutPlayer, "boxing": BoxingPlayer}
+
+
 def get_player(idx=0, num_actions=4, seed=0, train=False, frame_history=FRAME_HISTORY,
                limit=40000, game="synthetic"):
-    """OpenAIGym/train.py:113-128 with the synthetic game (or game="breakout": GridBreakout):
-    history of `frame_history` frames, PreventStuckPlayer(30, 1) for evaluation players,
-    LimitLengthPlayer(40000)."""
-    if game == "breakout":
-        pl = BreakoutPlayer(idx, num_actions, seed)
-    elif game == "synthetic":
-        pl = SyntheticAtariPlayer(idx, num_actions, seed)
-    else:
-        raise ValueError("unknown game %r (synthetic, breakout)" % (game,))
+    """OpenAIGym/train.py:113-128 with the synthetic game (or game="breakout": GridBreakout,
+    game="boxing": GridBoxing): history of `frame_history` frames, PreventStuckPlayer(30, 1)
+    for evaluation players, LimitLengthPlayer(40000)."""
+    if game not in PLAYERS:
+        raise ValueError("unknown game %r (%s)" % (game, ", ".join(sorted(PLAYERS))))
+    pl = PLAYERS[game](idx, num_actions, seed)
     pl = HistoryFramePlayer(pl, frame_history)
     if not train:
         pl = PreventStuckPlayer(pl, 30, 1)

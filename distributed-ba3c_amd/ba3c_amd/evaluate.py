@@ -1,9 +1,11 @@
-"""Evaluation on GridBreakout: the reference's `eval_with_funcs` / `play_one_episode` and its
-`Evaluator` callback (OpenAIGym/common.py:24-141) over a vector of on-device simulators.
+"""Evaluation on an on-device game (flags.GAMES: GridBreakout, GridBoxing): the reference's
+`eval_with_funcs` / `play_one_episode` and its `Evaluator` callback (OpenAIGym/common.py:24-141)
+over a vector of on-device simulators.
 
 The reference runs NR_PROC evaluation players (get_player(train=False): HistoryFramePlayer,
 PreventStuckPlayer(30, 1), LimitLengthPlayer) on threads that share one predictor; here the
-players are the rows of one `BreakoutVec`, all answered by ONE predictor forward per step:
+players are the rows of one `BreakoutVec` / `BoxingVec`, all answered by ONE predictor forward
+per step:
 
   state (FrameHistory) -> engine.forward -> greedy_actions (argmax, the action space's sample
   where random() < 0.001) -> PreventStuckPlayer(30, 1) per env -> fused step + history push
@@ -14,7 +16,8 @@ every step fetches `over` / `ep_score` to the host to count the finished episode
 import numpy as np
 import torch
 
-from .breakout import DEFAULT_LIMIT, BreakoutVec
+from .breakout import DEFAULT_LIMIT
+from .flags import GAMES, GRID_BREAKOUT
 from .metrics import StatCounter
 from .predict import greedy_actions
 from .rollout import FrameHistory
@@ -23,9 +26,10 @@ STUCK_REPEAT, STUCK_ACTION = 30, 1     # PreventStuckPlayer(pl, 30, 1), train.py
 GREEDY_EPS = 0.001                     # common.py:28
 
 
-def eval_with_envs(engine, nr_eval, n_envs, seed=0, limit=DEFAULT_LIMIT, policy=None):
-    """Play `n_envs` GridBreakout evaluation players with `engine`'s greedy policy until
-    `nr_eval` episodes have finished; returns (mean, max) of their scores (common.py:42-86).
+def eval_with_envs(engine, nr_eval, n_envs, seed=0, limit=DEFAULT_LIMIT, policy=None,
+                   game=GRID_BREAKOUT):
+    """Play `n_envs` evaluation players of `game` (a key of flags.GAMES) with `engine`'s greedy
+    policy until `nr_eval` episodes have finished; returns (mean, max) of their scores (common.py:42-86).
     Episodes that finish in the same step as the nr_eval-th are counted too (the reference
     also feeds the runs its workers were finishing).  `limit` is LimitLengthPlayer's.
     policy(state) -> probs [E,A] replaces the engine's forward (e.g. a uniform-random
@@ -33,7 +37,8 @@ def eval_with_envs(engine, nr_eval, n_envs, seed=0, limit=DEFAULT_LIMIT, policy=
     assert nr_eval >= 1 and 1 <= n_envs <= engine.max_batch
     dev, A = engine.device, engine.num_actions
     rs = np.random.RandomState(seed)
-    env = BreakoutVec(n_envs, seed=seed, limit=limit, device=dev)
+    env = GAMES[game][0](n_envs, seed=seed, limit=limit, device=dev)
+    assert env.A <= A
     hist = FrameHistory(n_envs, hist_len=4, channels=1, device=dev)
     env.reset_history(hist)
     last = torch.full((n_envs,), -1, dtype=torch.int64, device=dev)
@@ -72,17 +77,18 @@ class Evaluator(object):
     max) message to the metrics client."""
 
     def __init__(self, engine, nr_eval, client=None, n_envs=None, seed=0, limit=DEFAULT_LIMIT,
-                 worker_id=0):
+                 worker_id=0, game=GRID_BREAKOUT):
         self.engine, self.nr_eval, self.client = engine, int(nr_eval), client
         # NR_PROC = min(cpu_count // 2, 20) players in the reference (common.py:118)
         self.n_envs = int(n_envs) if n_envs else max(1, min(self.nr_eval, 20, engine.max_batch))
-        self.seed, self.limit, self.worker_id = seed, limit, worker_id
+        self.seed, self.limit, self.worker_id, self.game = seed, limit, worker_id, game
         self.calls = 0
         self.history = []
 
     def __call__(self):
         mean, mx = eval_with_envs(self.engine, self.nr_eval, self.n_envs,
-                                  seed=self.seed + self.calls, limit=self.limit)
+                                  seed=self.seed + self.calls, limit=self.limit,
+                                  game=self.game)
         self.calls += 1
         self.history.append((mean, mx))
         if self.client is not None:

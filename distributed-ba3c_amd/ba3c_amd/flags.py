@@ -4,8 +4,13 @@ its single-node launcher (`python -m ba3c_amd.train`) consume.  Slurm / TF-serve
 flags are accepted and ignored."""
 import argparse
 
+from .boxing import BoxingVec
+from .breakout import BreakoutVec
 
 GRID_BREAKOUT = "GridBreakout-v0"
+GRID_BOXING = "GridBoxing-v0"
+# -e name -> (vector class, the game's number of actions, envs.get_player's game key)
+GAMES = {GRID_BREAKOUT: (BreakoutVec, 4, "breakout"), GRID_BOXING: (BoxingVec, 18, "boxing")}
 
 
 def string_to_bool(s):        # parse.py:5-6
@@ -31,8 +36,9 @@ def build_parser():
     p.add_argument("--beta2", type=float, default=0.999)
     p.add_argument("--adam_debug", action="store_true")
     p.add_argument("--environment", "-e", "--env", dest="environment", default="Breakout-v0",
-                   help="GridBreakout-v0: the on-device Breakout (ba3c_amd.breakout); any other "
-                        "name: the synthetic environment")
+                   help="GridBreakout-v0 / GridBoxing-v0: the on-device Breakout / Boxing "
+                        "(ba3c_amd.breakout, ba3c_amd.boxing); any other name: the synthetic "
+                        "environment")
     p.add_argument("--channels", type=int, default=1)
     p.add_argument("--num_actions", type=int, default=4)
     p.add_argument("--predict_batch_size", type=int, default=16)
@@ -48,7 +54,7 @@ def build_parser():
     p.add_argument("--send_debug_every", type=int, default=100)
     p.add_argument("--nr_eval", type=int, default=0,
                    help="episodes the Evaluator plays every --steps_per_epoch learner steps on "
-                        "rank 0 (0: off; needs -e GridBreakout-v0)")
+                        "rank 0 (0: off; needs -e GridBreakout-v0 or GridBoxing-v0)")
     p.add_argument("--dummy", type=int, default=0)
     p.add_argument("--dummy_predictor", type=int, default=0)
     p.add_argument("--models_dir", default="models")
@@ -72,18 +78,20 @@ def build_parser():
 def resolve(args):
     """Apply the reference's implicit rules: --use_normal_fc disables replace_with_conv
     (run_job.py:131); --adam_debug sets beta2 := beta1 (train.py:460-461); --use_sync needs
-    --ngrads (run_job.py:55-57).  -e GridBreakout-v0 needs --channels 1 and --num_actions >= 4."""
+    --ngrads (run_job.py:55-57).  An on-device game (GAMES) needs --channels 1 and --num_actions
+    >= its own number of actions; --nr_eval needs one of them."""
     if args.replace_with_conv is None:
         args.replace_with_conv = not args.use_normal_fc
     if args.adam_debug:
         args.beta2 = args.beta1
     if args.use_sync and args.ngrads is None:
         raise SystemExit("if using SyncReplicasOptimizer you have to specify --ngrads argument")
-    if args.environment == GRID_BREAKOUT:
+    if args.environment in GAMES:
+        name, A = args.environment, GAMES[args.environment][1]
         if args.channels != 1:
-            raise SystemExit("-e %s renders grayscale frames: it requires --channels 1" % GRID_BREAKOUT)
-        if args.num_actions < 4:
-            raise SystemExit("-e %s has 4 actions: it requires --num_actions >= 4" % GRID_BREAKOUT)
+            raise SystemExit("-e %s renders grayscale frames: it requires --channels 1" % name)
+        if args.num_actions < A:
+            raise SystemExit("-e %s has %d actions: it requires --num_actions >= %d" % (name, A, A))
     elif args.nr_eval:
-        raise SystemExit("--nr_eval needs a game to evaluate: pass -e %s" % GRID_BREAKOUT)
+        raise SystemExit("--nr_eval needs a game to evaluate: pass -e %s" % " or -e ".join(sorted(GAMES)))
     return args

@@ -271,8 +271,8 @@ SimulatorProcess = SimulatorProcessStateExchange     # simulator.py:111-112
 
 
 class SyntheticSimulatorWorker(SimulatorProcess):
-    """MySimulatorWorker (train.py:134-136) over the synthetic game, or over GridBreakout's
-    host player with game="breakout"."""
+    """MySimulatorWorker (train.py:134-136) over the synthetic game, or over GridBreakout's /
+    GridBoxing's host player with game="breakout" / game="boxing"."""
 
     def __init__(self, idx, pipe_c2s, pipe_s2c, num_actions=4, seed=0, game="synthetic"):
         super(SyntheticSimulatorWorker, self).__init__(idx, pipe_c2s, pipe_s2c)

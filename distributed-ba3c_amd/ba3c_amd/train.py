@@ -5,9 +5,9 @@ Replaces run_job.py:13-148 -> distributed_tensorpack_mkl.sh -> OpenAIGym/train.p
 (`-o`, :582-597), SyncReplicasOptimizer for `--use_sync -g N` (:598-606, here an RCCL
 all-reduce over the node's GPUs), the trainer and the actor-learner loop (simulator master +
 predictor + BatchData, :520-534 — with the synthetic on-device environment, gym/ALE being
-absent, or with `-e GridBreakout-v0` the on-device Breakout of ba3c_amd.breakout and, for
-`--nr_eval N`, the Evaluator callback every --steps_per_epoch steps), plus the
-DebugLogCallback metrics channels and PeriodicPerStepCallback(ModelSaver) (:608-630) and
+absent, or with `-e GridBreakout-v0` / `-e GridBoxing-v0` the on-device Breakout / Boxing of
+flags.GAMES and, for `--nr_eval N`, the Evaluator callback every --steps_per_epoch steps), plus
+the DebugLogCallback metrics channels and PeriodicPerStepCallback(ModelSaver) (:608-630) and
 `--load` (SaverRestore, :706-707).
 
 One process per GPU: launch N > 1 with
@@ -26,7 +26,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .flags import GRID_BREAKOUT, build_parser, resolve
+from .flags import GAMES, build_parser, resolve
 
 
 def _free_port():
@@ -158,7 +158,8 @@ def _run(args, rank, world):
     evaluator = None
     if args.nr_eval and rank == 0:
         from .evaluate import Evaluator
-        evaluator = Evaluator(trainer.engine, args.nr_eval, client, seed=1000 + rank)
+        evaluator = Evaluator(trainer.engine, args.nr_eval, client, seed=1000 + rank,
+                              game=args.environment)
 
     def on_step(tr):
         metrics(tr)
@@ -182,9 +183,9 @@ def _run(args, rank, world):
         sim_steps = 0
     else:
         env = None
-        if args.environment == GRID_BREAKOUT:
-            from .breakout import BreakoutVec
-            env = BreakoutVec(args.simulator_procs, seed=rank, device=trainer.engine.device)
+        if args.environment in GAMES:
+            env = GAMES[args.environment][0](args.simulator_procs, seed=rank,
+                                             device=trainer.engine.device)
         al = ActorLearner(trainer, n_envs=args.simulator_procs, batch_size=args.batch_size,
                           seed=rank, rs=np.random.RandomState(rank), on_train_step=on_step,
                           dummy_predictor=bool(args.dummy_predictor), env=env)

@@ -6,18 +6,13 @@
 //
 // game[e] = [px, bx, by, vx, vy, in_play, lives, score, t, rng, b0..b5], 16 int32 = 64 bytes.
 //
-// One 256-thread workgroup per simulator.  Every thread loads the game row and computes the
-// (wave-uniform) step redundantly, a barrier separates those loads from thread 0's store of
-// the new row, then the workgroup renders the 84x84 frame, 4 pixels (one 16-byte group of the
-// H=4, c=1 history) per thread per iteration.  HBM-bound: 2 * 28224 bytes of state per env.
+// The launch is env_kernel<BreakoutRules> (ba3c_envkernel.h: one 256-thread workgroup per
+// simulator, the skeleton GridBoxing shares); this file holds the game's step and pixel rules.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
+#include "ba3c_envkernel.h"
 
 namespace ba3c {
 
-constexpr int BK_W = 84, BK_PIXELS = 84 * 84, BK_GROUPS = BK_PIXELS / 4;   // 1764 groups of 4 px
 constexpr int BK_ROWS = 6, BK_COLS = 14, BK_BRICK_W = 6, BK_BRICK_H = 3, BK_BRICK_Y0 = 18;
 constexpr int BK_PADDLE_Y = 78, BK_PADDLE_W = 12, BK_PX_MAX = 72, BK_LIVES = 5;
 constexpr int32_t BK_FULL_ROW = 0x3FFF;
@@ -26,17 +21,6 @@ struct BreakoutGame {
   int32_t px, bx, by, vx, vy, in_play, lives, score, t;
   uint32_t rng;
   int32_t b0, b1, b2, b3, b4, b5;   // named, not an array: r is never a compile-time constant
-};
-
-struct BreakoutArgs {
-  int32_t* game;            // [E][16]
-  const int64_t* action;    // [E] (null: render only)
-  int32_t limit;
-  double* reward;           // [E]
-  uint8_t* over;            // [E]
-  int32_t* ep_score;        // [E], written where over
-  uint8_t* frame;           // [E][84*84] or null
-  uint8_t* state;           // [E][84*84][4] or null
 };
 
 __device__ __forceinline__ int32_t bk_row_value(int r) { return r < 2 ? 7 : (r < 4 ? 4 : 1); }
@@ -131,55 +115,41 @@ __device__ __forceinline__ uint32_t bk_pixel(const BreakoutGame& g, int y, int x
   return 0u;
 }
 
-__global__ void __launch_bounds__(256) breakout_kernel(const BreakoutArgs a) {
-  const int e = blockIdx.x;
-  const int tid = threadIdx.x;
-  const int4* row = reinterpret_cast<const int4*>(a.game + (size_t)e * 16);
-  const int4 r0 = row[0], r1 = row[1], r2 = row[2], r3 = row[3];
-  BreakoutGame g;
-  g.px = r0.x; g.bx = r0.y; g.by = r0.z; g.vx = r0.w;
-  g.vy = r1.x; g.in_play = r1.y; g.lives = r1.z; g.score = r1.w;
-  g.t = r2.x; g.rng = (uint32_t)r2.y; g.b0 = r2.z; g.b1 = r2.w;
-  g.b2 = r3.x; g.b3 = r3.y; g.b4 = r3.z; g.b5 = r3.w;
-  bool over = a.action == nullptr;      // render only: the history starts (zeros + frame)
-  if (a.action != nullptr) {
-    int32_t ep = 0;
-    const int32_t reward = bk_step(g, a.action[e], a.limit, &over, &ep);
-    __syncthreads();                    // every thread has read the row before it is replaced
-    if (tid == 0) {
-      int4* out = reinterpret_cast<int4*>(a.game + (size_t)e * 16);
-      out[0] = make_int4(g.px, g.bx, g.by, g.vx);
-      out[1] = make_int4(g.vy, g.in_play, g.lives, g.score);
-      out[2] = make_int4(g.t, (int32_t)g.rng, g.b0, g.b1);
-      out[3] = make_int4(g.b2, g.b3, g.b4, g.b5);
-      a.reward[e] = (double)reward;
-      a.over[e] = over ? 1 : 0;
-      if (over) a.ep_score[e] = ep;
-    }
+// The game as ba3c_envkernel.h's env_kernel takes it.
+struct BreakoutRules {
+  using Game = BreakoutGame;
+  struct Row {
+    int32_t bricks;   // row y's brick mask, 0 outside the brick band
+    uint32_t shade;
+  };
+  static __device__ __forceinline__ void load(Game& g, int4 r0, int4 r1, int4 r2, int4 r3) {
+    g.px = r0.x; g.bx = r0.y; g.by = r0.z; g.vx = r0.w;
+    g.vy = r1.x; g.in_play = r1.y; g.lives = r1.z; g.score = r1.w;
+    g.t = r2.x; g.rng = (uint32_t)r2.y; g.b0 = r2.z; g.b1 = r2.w;
+    g.b2 = r3.x; g.b3 = r3.y; g.b4 = r3.z; g.b5 = r3.w;
   }
-  uint4* st = a.state ? reinterpret_cast<uint4*>(a.state + (size_t)e * BK_PIXELS * 4) : nullptr;
-  uint32_t* fr = a.frame ? reinterpret_cast<uint32_t*>(a.frame + (size_t)e * BK_PIXELS) : nullptr;
-  for (int q = tid; q < BK_GROUPS; q += 256) {
-    const int y = q / (BK_W / 4), x0 = 4 * (q - y * (BK_W / 4));
-    int32_t bricks = 0;
-    uint32_t shade = 0;
+  static __device__ __forceinline__ void store(const Game& g, int4* out) {
+    out[0] = make_int4(g.px, g.bx, g.by, g.vx);
+    out[1] = make_int4(g.vy, g.in_play, g.lives, g.score);
+    out[2] = make_int4(g.t, (int32_t)g.rng, g.b0, g.b1);
+    out[3] = make_int4(g.b2, g.b3, g.b4, g.b5);
+  }
+  static __device__ __forceinline__ int32_t step(Game& g, int64_t a, int32_t limit, bool* over_out,
+                                                 int32_t* ep_out) {
+    return bk_step(g, a, limit, over_out, ep_out);
+  }
+  static __device__ __forceinline__ Row row(const Game& g, int y) {
+    Row rw{0, 0u};
     if ((unsigned)(y - BK_BRICK_Y0) < (unsigned)(BK_ROWS * BK_BRICK_H)) {
       const int r = (y - BK_BRICK_Y0) / BK_BRICK_H;
-      bricks = bk_row_mask(g, r);
-      shade = 230u - 30u * (uint32_t)r;
+      rw.bricks = bk_row_mask(g, r);
+      rw.shade = 230u - 30u * (uint32_t)r;
     }
-    const uint32_t p0 = bk_pixel(g, y, x0, bricks, shade), p1 = bk_pixel(g, y, x0 + 1, bricks, shade),
-                   p2 = bk_pixel(g, y, x0 + 2, bricks, shade), p3 = bk_pixel(g, y, x0 + 3, bricks, shade);
-    if (fr) fr[q] = p0 | (p1 << 8) | (p2 << 16) | (p3 << 24);
-    if (st) {
-      uint4 v = over ? make_uint4(0, 0, 0, 0) : st[q];
-      v.x = (v.x >> 8) | (p0 << 24);
-      v.y = (v.y >> 8) | (p1 << 24);
-      v.z = (v.z >> 8) | (p2 << 24);
-      v.w = (v.w >> 8) | (p3 << 24);
-      st[q] = v;
-    }
+    return rw;
   }
-}
+  static __device__ __forceinline__ uint32_t pixel(const Game& g, int y, int x, const Row& rw) {
+    return bk_pixel(g, y, x, rw.bricks, rw.shade);
+  }
+};
 
 }  // namespace ba3c

@@ -19,6 +19,7 @@
 
 #include "../../include/ba3c.h"
 #include "ba3c_band6.h"
+#include "ba3c_boxing.h"
 #include "ba3c_breakout.h"
 #include "ba3c_conv.h"
 #include "ba3c_conv3.h"
@@ -1318,6 +1319,37 @@ int rccl_fail(ncclResult_t e, const char* what) {
 }
 }  // namespace
 
+// The two entry points every on-device game has (Rules: ba3c_envkernel.h).
+template <class Rules>
+static int env_step(void* stream, int32_t* game, const int64_t* action, int32_t n_envs, int32_t limit,
+                    double* reward, uint8_t* over, int32_t* ep_score, uint8_t* frame, uint8_t* state) {
+  if (!game || !action) return fail(BA3C_ERR_INVALID, "null game / action pointer");
+  if (!reward || !over || !ep_score) return fail(BA3C_ERR_INVALID, "null output pointer");
+  if (n_envs < 1 || limit < 1) return fail(BA3C_ERR_INVALID, "n_envs and limit must be >= 1");
+  if (!check_ptr(game) || (state && !check_ptr(state)) || (reinterpret_cast<uintptr_t>(frame) & 3))
+    return fail(BA3C_ERR_INVALID, "game / state must be 16-byte and frame 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  EnvArgs a{game, action, limit, reward, over, ep_score, frame, state};
+  hipLaunchKernelGGL(env_kernel<Rules>, dim3(n_envs), dim3(256), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return BA3C_OK;
+}
+
+template <class Rules>
+static int env_render(void* stream, const int32_t* game, int32_t n_envs, uint8_t* frame, uint8_t* state) {
+  if (!game) return fail(BA3C_ERR_INVALID, "null game pointer");
+  if (n_envs < 1) return fail(BA3C_ERR_INVALID, "n_envs must be >= 1");
+  if (!check_ptr(game) || (state && !check_ptr(state)) || (reinterpret_cast<uintptr_t>(frame) & 3))
+    return fail(BA3C_ERR_INVALID, "game / state must be 16-byte and frame 4-byte aligned");
+  if (!frame && !state) return BA3C_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // render only: the kernel never writes the row when action is null
+  EnvArgs a{const_cast<int32_t*>(game), nullptr, 1, nullptr, nullptr, nullptr, frame, state};
+  hipLaunchKernelGGL(env_kernel<Rules>, dim3(n_envs), dim3(256), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return BA3C_OK;
+}
+
 // =========================================================================================
 extern "C" {
 
@@ -1931,31 +1963,23 @@ int ba3c_history_push(void* stream, const uint8_t* frame, uint8_t* state, const 
 int ba3c_breakout_step(void* stream, int32_t* game, const int64_t* action, int32_t n_envs,
                        int32_t limit, double* reward, uint8_t* over, int32_t* ep_score,
                        uint8_t* frame, uint8_t* state) {
-  if (!game || !action) return fail(BA3C_ERR_INVALID, "null game / action pointer");
-  if (!reward || !over || !ep_score) return fail(BA3C_ERR_INVALID, "null output pointer");
-  if (n_envs < 1 || limit < 1) return fail(BA3C_ERR_INVALID, "n_envs and limit must be >= 1");
-  if (!check_ptr(game) || (state && !check_ptr(state)) || (reinterpret_cast<uintptr_t>(frame) & 3))
-    return fail(BA3C_ERR_INVALID, "game / state must be 16-byte and frame 4-byte aligned");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  BreakoutArgs a{game, action, limit, reward, over, ep_score, frame, state};
-  hipLaunchKernelGGL(breakout_kernel, dim3(n_envs), dim3(256), 0, s, a);
-  HIP_TRY(hipGetLastError());
-  return BA3C_OK;
+  return env_step<BreakoutRules>(stream, game, action, n_envs, limit, reward, over, ep_score, frame, state);
 }
 
 int ba3c_breakout_render(void* stream, const int32_t* game, int32_t n_envs, uint8_t* frame,
                          uint8_t* state) {
-  if (!game) return fail(BA3C_ERR_INVALID, "null game pointer");
-  if (n_envs < 1) return fail(BA3C_ERR_INVALID, "n_envs must be >= 1");
-  if (!check_ptr(game) || (state && !check_ptr(state)) || (reinterpret_cast<uintptr_t>(frame) & 3))
-    return fail(BA3C_ERR_INVALID, "game / state must be 16-byte and frame 4-byte aligned");
-  if (!frame && !state) return BA3C_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  // render only: the kernel never writes the row when action is null
-  BreakoutArgs a{const_cast<int32_t*>(game), nullptr, 1, nullptr, nullptr, nullptr, frame, state};
-  hipLaunchKernelGGL(breakout_kernel, dim3(n_envs), dim3(256), 0, s, a);
-  HIP_TRY(hipGetLastError());
-  return BA3C_OK;
+  return env_render<BreakoutRules>(stream, game, n_envs, frame, state);
+}
+
+int ba3c_boxing_step(void* stream, int32_t* game, const int64_t* action, int32_t n_envs,
+                     int32_t limit, double* reward, uint8_t* over, int32_t* ep_score,
+                     uint8_t* frame, uint8_t* state) {
+  return env_step<BoxingRules>(stream, game, action, n_envs, limit, reward, over, ep_score, frame, state);
+}
+
+int ba3c_boxing_render(void* stream, const int32_t* game, int32_t n_envs, uint8_t* frame,
+                       uint8_t* state) {
+  return env_render<BoxingRules>(stream, game, n_envs, frame, state);
 }
 
 int ba3c_kernel_split(const ba3c_handle* h, int32_t kid) {

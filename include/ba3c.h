@@ -349,6 +349,34 @@ int ba3c_breakout_step(void* stream, int32_t* game, const int64_t* action, int32
 int ba3c_breakout_render(void* stream, const int32_t* game, int32_t n_envs, uint8_t* frame,
                          uint8_t* state);
 
+/* ---- GridBoxing: a second on-device game (18 actions, an adversary, signed rewards) ------ */
+
+/* A small integer-only Boxing for n_envs simulators; ba3c_amd/boxing.py states the rules
+ * (constants, step_numpy, render_numpy) and is the oracle of these entry points.  All game
+ * state is int32, one 64-byte (16-byte aligned) row per simulator:
+ *   game[e] = [ax, ay, ox, oy, a_cd, o_cd, a_score, o_score, t, rng, 0, 0, 0, 0, 0, 0]
+ * (ax, ay) / (ox, oy): top-left of the agent's / the scripted opponent's 6x8 body (x in 4..74,
+ * y in 14..70); a_cd / o_cd: steps until each may punch again (8 after a punch; the arm is
+ * drawn while >= 6); a_score / o_score: points of the episode; t: its steps; rng: the
+ * opponent LCG's uint32 bits; the six padding ints are written as 0.
+ *
+ * ba3c_boxing_step applies action[e] (ALE's 18: 0 NOOP, 1 FIRE, 2 UP, 3 RIGHT, 4 LEFT, 5 DOWN,
+ * 6..9 the diagonals, 10..17 the same eight moves with FIRE; anything outside [0, 18) is
+ * NOOP; the value is range-checked and shifts constant bit masks, it is never used as an
+ * index) and writes reward[e] (float64: points landed minus points taken in this step),
+ * over[e], and ep_score[e] ONLY where over[e] (a_score - o_score of the finished episode, in
+ * [-101, 101]; the row is then already reset).  An episode ends when either score reaches
+ * 100, at t >= 1680 (the clock) or at t >= limit (LimitLengthPlayer).  frame / state are as
+ * for ba3c_breakout_step, and ba3c_boxing_render is ba3c_breakout_render for these rows.
+ *
+ * Same argument contract and host-side refusals as the Breakout pair, the same launch shape
+ * (both games are one kernel template, one 256-thread workgroup per simulator). */
+int ba3c_boxing_step(void* stream, int32_t* game, const int64_t* action, int32_t n_envs,
+                     int32_t limit, double* reward, uint8_t* over, int32_t* ep_score,
+                     uint8_t* frame, uint8_t* state);
+int ba3c_boxing_render(void* stream, const int32_t* game, int32_t n_envs, uint8_t* frame,
+                       uint8_t* state);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,10 +1,13 @@
-"""Environment step time on the GPU (GridBreakout section): µs per fused
-`BreakoutVec.step_into` against `SyntheticAtari.step` + `FrameHistory.push`, and the fused
+"""Environment step time on the GPU (GridBreakout / GridBoxing sections): µs per fused
+`step_into` of the on-device game (--game breakout: `BreakoutVec`; --game boxing: `BoxingVec`,
+timed next to GridBreakout's fused step in the same run) against `SyntheticAtari.step` +
+`FrameHistory.push`, and the fused
 kernel's achieved bytes/s against this box's measured HBM copy rate (a device-to-device copy, and
 an in-place update over the kernel's own footprint).  With --random N also the
-evaluation score of a uniform-random policy over N episodes.  Prints one JSON line.
+evaluation scores of a uniform-random policy (and, for boxing, of a NOOP policy) over N
+episodes.  Prints one JSON line.
 
-    python scripts/env_throughput.py [--envs 8192 64] [--iters 200] [--random 20]
+    python scripts/env_throughput.py [--game boxing] [--envs 8192 64] [--iters 200] [--random 20]
 """
 import argparse
 import json
@@ -39,12 +42,16 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--random", type=int, default=0)
+    ap.add_argument("--game", choices=["breakout", "boxing"], default="breakout")
     args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "needs the GPU: a CPU run measures nothing"
     from ba3c_amd.actor_learner import SyntheticAtari
     from ba3c_amd.breakout import BreakoutVec
+    from ba3c_amd.flags import GAMES, GRID_BOXING, GRID_BREAKOUT
     from ba3c_amd.rollout import FrameHistory
-    out = {"iters": args.iters, "envs": {}}
+    name = GRID_BOXING if args.game == "boxing" else GRID_BREAKOUT
+    Vec, A = GAMES[name][:2]
+    out = {"game": name, "iters": args.iters, "envs": {}}
 
     # HBM copy rate: a device-to-device copy the size of E=8192 states (read + write)
     n = 8192 * STATE_BYTES
@@ -60,18 +67,24 @@ def main(argv=None):
 
     for E in args.envs:
         g = torch.Generator(device="cuda").manual_seed(0)
-        actions = torch.randint(0, 4, (E,), generator=g, device="cuda")
-        env, hist = BreakoutVec(E, seed=0), FrameHistory(E, 4, 1)
+        actions = torch.randint(0, A, (E,), generator=g, device="cuda")
+        env, hist = Vec(E, seed=0), FrameHistory(E, 4, 1)
         env.reset_history(hist)
+        if Vec is not BreakoutVec:                        # the yardstick: GridBreakout's fused step
+            actions_b = torch.randint(0, 4, (E,), generator=g, device="cuda")
+            env_b, hist_b = BreakoutVec(E, seed=0), FrameHistory(E, 4, 1)
+            env_b.reset_history(hist_b)
         syn, hist_s = SyntheticAtari(E, 4, seed=0), FrameHistory(E, 4, 1)
 
         def synthetic():
             frames, _, over = syn.step(actions)
             hist_s.push(frames, over)
-        # alternate the two so that both see the same machine state
-        fused, base = [], []
+        # alternate them so that all see the same machine state
+        fused, base, brk = [], [], []
         for _ in range(args.repeats):
             fused.append(timed(lambda: env.step_into(actions, hist), args.iters))
+            if Vec is not BreakoutVec:
+                brk.append(timed(lambda: env_b.step_into(actions_b, hist_b), args.iters))
             base.append(timed(synthetic, args.iters))
         traffic = 2 * E * STATE_BYTES                     # the history is read and written once
         out["envs"][str(E)] = {
@@ -80,14 +93,25 @@ def main(argv=None):
             "state_bytes": traffic,
             "fused_GBps": round(traffic / min(fused) / 1e3, 1),
         }
+        if brk:
+            out["envs"][str(E)]["breakout_fused_step_into_us"] = [round(v, 2) for v in brk]
+            out["envs"][str(E)]["fused_over_breakout"] = round(min(fused) / min(brk), 3)
     if args.random:
         from ba3c_amd.evaluate import eval_with_envs, uniform_policy
         from ba3c_amd.model import Model
-        m = Model(num_actions=4, fc_neurons=128, fc_splits=4, batch_size=32, max_batch=32, seed=0)
+        m = Model(num_actions=A, fc_neurons=128, fc_splits=4, batch_size=32, max_batch=32, seed=0)
         torch.manual_seed(0)
         mean, mx = eval_with_envs(m.engine, args.random, min(args.random, 20), seed=0,
-                                  policy=uniform_policy(4))
+                                  policy=uniform_policy(A), game=name)
         out["random_policy"] = {"episodes": args.random, "mean_score": mean, "max_score": mx}
+        if args.game == "boxing":
+            def noop(state):                              # argmax 0 = NOOP (FIRE every 30th step:
+                p = torch.zeros(state.shape[0], A, dtype=torch.float32, device=state.device)
+                p[:, 0] = 1.0                             # the evaluation's PreventStuckPlayer)
+                return p
+            mean, mx = eval_with_envs(m.engine, args.random, min(args.random, 20), seed=0,
+                                      policy=noop, game=name)
+            out["noop_policy"] = {"episodes": args.random, "mean_score": mean, "max_score": mx}
     print(json.dumps(out), flush=True)
     return out
 
