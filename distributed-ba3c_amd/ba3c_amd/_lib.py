@@ -104,6 +104,8 @@ def load():
         "ba3c_breakout_render": (i32, [P, P, i32, P, P]),
         "ba3c_boxing_step": (i32, [P, P, P, i32, i32, P, P, P, P, P]),
         "ba3c_boxing_render": (i32, [P, P, i32, P, P]),
+        "ba3c_breakout_step_skip": (i32, [P, P, P, P, i32, i32, i32, i32, i32, P, P, P, P, P]),
+        "ba3c_boxing_step_skip": (i32, [P, P, P, P, i32, i32, i32, i32, i32, P, P, P, P, P]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("BA3C_LIB") and name in AB_OPTIONAL and not hasattr(lib, name):

@@ -207,14 +207,15 @@ class BoxingVec(object):
     """E GridBoxing simulators in HBM with BreakoutVec's interface (`E`, `A`, `frames()`,
     `reset_history`, `step(actions) -> frames, reward, over`, `step_into(actions, hist)`,
     `last_over`, `last_ep_score`, `game`, `ep_score`); every step is one HIP launch
-    (ba3c_boxing_step)."""
+    (ba3c_boxing_step), or with `frame_skip` / `sticky` one decision of ba3c_amd.frameskip
+    (ba3c_boxing_step_skip, aux rows in `aux`), as for BreakoutVec."""
 
     A = NUM_ACTIONS
 
-    def __init__(self, n_envs, seed=0, limit=DEFAULT_LIMIT, device="cuda"):
+    def __init__(self, n_envs, seed=0, limit=DEFAULT_LIMIT, device="cuda", frame_skip=1, sticky=0.0):
         import torch
 
-        from . import _lib
+        from . import _lib, frameskip
         self.lib = _lib.load()
         self._check = _lib.check
         self._torch = torch
@@ -229,6 +230,11 @@ class BoxingVec(object):
         self.over = torch.zeros(self.E, dtype=torch.uint8, device=dev)
         self.ep_score = torch.zeros(self.E, dtype=torch.int32, device=dev)
         self.frame = torch.zeros((self.E, H, W, 1), dtype=torch.uint8, device=dev)
+        # (lo, hi, q16) of ba3c_amd.frameskip, or None: the plain one-step launch and no aux rows
+        self.skip = frameskip.setting(frame_skip, sticky)
+        self.aux = None
+        if self.skip is not None:
+            self.aux = torch.from_numpy(frameskip.initial_aux(self.E, seed)).to(dev)
 
     def _ptr(self, t):
         return ctypes.c_void_p(t.data_ptr()) if t is not None else None
@@ -262,10 +268,17 @@ class BoxingVec(object):
 
     def _step(self, actions, frame, state):
         a = self._actions(actions)
-        self._check(self.lib.ba3c_boxing_step(
-            self._stream(), self._ptr(self.game), self._ptr(a), self.E, self.limit,
-            self._ptr(self.reward), self._ptr(self.over), self._ptr(self.ep_score),
-            self._ptr(frame), self._ptr(state)))
+        if self.skip is None:
+            self._check(self.lib.ba3c_boxing_step(
+                self._stream(), self._ptr(self.game), self._ptr(a), self.E, self.limit,
+                self._ptr(self.reward), self._ptr(self.over), self._ptr(self.ep_score),
+                self._ptr(frame), self._ptr(state)))
+        else:
+            lo, hi, q16 = self.skip
+            self._check(self.lib.ba3c_boxing_step_skip(
+                self._stream(), self._ptr(self.game), self._ptr(self.aux), self._ptr(a), self.E,
+                self.limit, lo, hi, q16, self._ptr(self.reward), self._ptr(self.over),
+                self._ptr(self.ep_score), self._ptr(frame), self._ptr(state)))
         return self.reward, self.over.view(self._torch.bool)
 
     def step(self, actions):

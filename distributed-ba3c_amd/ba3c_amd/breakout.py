@@ -180,14 +180,17 @@ class BreakoutVec(object):
     `step(actions) -> frames, reward, over`); every step is one HIP launch
     (ba3c_breakout_step).  `step_into(actions, hist)` also pushes the new frames into a
     FrameHistory(hist_len=4, channels=1) in that same launch.  `last_ep_score` / `last_over`
-    expose the episodes the last step finished."""
+    expose the episodes the last step finished.  A non-default `frame_skip` (K or an inclusive
+    (lo, hi)) / `sticky` (a probability) makes every step one DECISION of ba3c_amd.frameskip,
+    still one launch (ba3c_breakout_step_skip), with the aux rows in `aux`; `limit` counts game
+    steps either way."""
 
     A = NUM_ACTIONS
 
-    def __init__(self, n_envs, seed=0, limit=DEFAULT_LIMIT, device="cuda"):
+    def __init__(self, n_envs, seed=0, limit=DEFAULT_LIMIT, device="cuda", frame_skip=1, sticky=0.0):
         import torch
 
-        from . import _lib
+        from . import _lib, frameskip
         self.lib = _lib.load()
         self._check = _lib.check
         self._torch = torch
@@ -202,6 +205,11 @@ class BreakoutVec(object):
         self.over = torch.zeros(self.E, dtype=torch.uint8, device=dev)
         self.ep_score = torch.zeros(self.E, dtype=torch.int32, device=dev)
         self.frame = torch.zeros((self.E, H, W, 1), dtype=torch.uint8, device=dev)
+        # (lo, hi, q16) of ba3c_amd.frameskip, or None: the plain one-step launch and no aux rows
+        self.skip = frameskip.setting(frame_skip, sticky)
+        self.aux = None
+        if self.skip is not None:
+            self.aux = torch.from_numpy(frameskip.initial_aux(self.E, seed)).to(dev)
 
     def _ptr(self, t):
         return ctypes.c_void_p(t.data_ptr()) if t is not None else None
@@ -235,10 +243,17 @@ class BreakoutVec(object):
 
     def _step(self, actions, frame, state):
         a = self._actions(actions)
-        self._check(self.lib.ba3c_breakout_step(
-            self._stream(), self._ptr(self.game), self._ptr(a), self.E, self.limit,
-            self._ptr(self.reward), self._ptr(self.over), self._ptr(self.ep_score),
-            self._ptr(frame), self._ptr(state)))
+        if self.skip is None:
+            self._check(self.lib.ba3c_breakout_step(
+                self._stream(), self._ptr(self.game), self._ptr(a), self.E, self.limit,
+                self._ptr(self.reward), self._ptr(self.over), self._ptr(self.ep_score),
+                self._ptr(frame), self._ptr(state)))
+        else:
+            lo, hi, q16 = self.skip
+            self._check(self.lib.ba3c_breakout_step_skip(
+                self._stream(), self._ptr(self.game), self._ptr(self.aux), self._ptr(a), self.E,
+                self.limit, lo, hi, q16, self._ptr(self.reward), self._ptr(self.over),
+                self._ptr(self.ep_score), self._ptr(frame), self._ptr(state)))
         return self.reward, self.over.view(self._torch.bool)
 
     def step(self, actions):

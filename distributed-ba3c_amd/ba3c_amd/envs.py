@@ -492,19 +492,77 @@ class BoxingPlayer(RLEnvironment):
         return self.space
 
 
+class FrameSkipPlayer(ProxyPlayer):
+    """Frame skip and sticky actions around a BreakoutPlayer / BoxingPlayer: ba3c_amd.frameskip's
+    decision as scalar Python ints, for the simulator processes.  One action() draws k in
+    [lo, hi], plays k game steps of the wrapped player (each repeats the previous effective
+    action when its 16-bit draw is below q16, else plays `act`), sums their rewards and stops at
+    an episode's end.  `aux_row()` is the device's aux row [rng2, prev], next to the wrapped
+    player's `game_row()`.  The wrapped player's `limit` counts game steps, not decisions."""
+
+    def __init__(self, player, lo, hi, q16, seed=0, idx=0):
+        super(FrameSkipPlayer, self).__init__(player)
+        from . import frameskip as F
+        F.check(lo, hi, q16)
+        self.F = F
+        self.lo, self.hi, self.q16 = int(lo), int(hi), int(q16)
+        self.rng2 = F.initial_rng2(seed, idx)
+        self.prev = 0
+
+    def game_row(self):
+        return self.player.game_row()
+
+    def aux_row(self):
+        rng2 = self.rng2 - (1 << 32) if self.rng2 >= (1 << 31) else self.rng2
+        return [rng2, self.prev]
+
+    def action(self, act):
+        F = self.F
+        act = int(act)
+        if not 0 <= act < F.ACTION_BOUND:
+            act = 0
+        self.rng2 = F.lcg(self.rng2)
+        k = self.lo + ((self.rng2 >> 16) % (self.hi - self.lo + 1))
+        reward, over = 0.0, False
+        for _ in range(k):
+            self.rng2 = F.lcg(self.rng2)
+            if ((self.rng2 >> 8) & 0xFFFF) >= self.q16:
+                self.prev = act
+            r, over = self.player.action(self.prev)
+            reward += r
+            if over:                          # the player has restarted: drop the rest
+                self.prev = 0
+                break
+        return reward, over
+
+    def restart_episode(self):
+        super(FrameSkipPlayer, self).restart_episode()
+        self.prev = 0
+
+
 # game key -> the host player of get_player / SyntheticSimulatorWorker
 PLAYERS = {"synthetic": SyntheticAtariPlayer, "breakout": BreakoutPlayer, "boxing": BoxingPlayer}
 
 
 def get_player(idx=0, num_actions=4, seed=0, train=False, frame_history=FRAME_HISTORY,
-               limit=40000, game="synthetic"):
+               limit=40000, game="synthetic", frame_skip=1, sticky=0.0):
     """OpenAIGym/train.py:113-128 with the synthetic game (or game="breakout": GridBreakout,
     game="boxing": GridBoxing): history of `frame_history` frames, PreventStuckPlayer(30, 1)
-    for evaluation players, LimitLengthPlayer(40000)."""
+    for evaluation players, LimitLengthPlayer(40000).
+    A non-default `frame_skip` (K or (lo, hi)) / `sticky` (a probability) puts a FrameSkipPlayer
+    under the history, for GridBreakout / GridBoxing only; `limit` then counts game steps as it
+    does on the device: the game's own player ends the episode, in place of LimitLengthPlayer."""
     if game not in PLAYERS:
         raise ValueError("unknown game %r (%s)" % (game, ", ".join(sorted(PLAYERS))))
-    pl = PLAYERS[game](idx, num_actions, seed)
+    from .frameskip import setting
+    skip = setting(frame_skip, sticky)
+    if skip is None:
+        pl = PLAYERS[game](idx, num_actions, seed)
+    elif game == "synthetic":
+        raise ValueError("frame_skip / sticky need game='breakout' or game='boxing'")
+    else:
+        pl = FrameSkipPlayer(PLAYERS[game](idx, num_actions, seed, limit=limit), *skip, seed=seed, idx=idx)
     pl = HistoryFramePlayer(pl, frame_history)
     if not train:
         pl = PreventStuckPlayer(pl, 30, 1)
-    return LimitLengthPlayer(pl, limit)
+    return pl if skip is not None else LimitLengthPlayer(pl, limit)

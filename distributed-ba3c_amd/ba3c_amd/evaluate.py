@@ -27,17 +27,20 @@ GREEDY_EPS = 0.001                     # common.py:28
 
 
 def eval_with_envs(engine, nr_eval, n_envs, seed=0, limit=DEFAULT_LIMIT, policy=None,
-                   game=GRID_BREAKOUT):
+                   game=GRID_BREAKOUT, frame_skip=1, sticky=0.0):
     """Play `n_envs` evaluation players of `game` (a key of flags.GAMES) with `engine`'s greedy
     policy until `nr_eval` episodes have finished; returns (mean, max) of their scores (common.py:42-86).
     Episodes that finish in the same step as the nr_eval-th are counted too (the reference
     also feeds the runs its workers were finishing).  `limit` is LimitLengthPlayer's.
     policy(state) -> probs [E,A] replaces the engine's forward (e.g. a uniform-random
-    baseline); the argmax / eps / PreventStuck path is the same."""
+    baseline); the argmax / eps / PreventStuck path is the same.  frame_skip / sticky: the
+    vector's (ba3c_amd.frameskip); PreventStuck keeps counting chosen actions, one per decision,
+    and `limit` counts game steps."""
     assert nr_eval >= 1 and 1 <= n_envs <= engine.max_batch
     dev, A = engine.device, engine.num_actions
     rs = np.random.RandomState(seed)
-    env = GAMES[game][0](n_envs, seed=seed, limit=limit, device=dev)
+    env = GAMES[game][0](n_envs, seed=seed, limit=limit, device=dev, frame_skip=frame_skip,
+                         sticky=sticky)
     assert env.A <= A
     hist = FrameHistory(n_envs, hist_len=4, channels=1, device=dev)
     env.reset_history(hist)
@@ -77,18 +80,19 @@ class Evaluator(object):
     max) message to the metrics client."""
 
     def __init__(self, engine, nr_eval, client=None, n_envs=None, seed=0, limit=DEFAULT_LIMIT,
-                 worker_id=0, game=GRID_BREAKOUT):
+                 worker_id=0, game=GRID_BREAKOUT, frame_skip=1, sticky=0.0):
         self.engine, self.nr_eval, self.client = engine, int(nr_eval), client
         # NR_PROC = min(cpu_count // 2, 20) players in the reference (common.py:118)
         self.n_envs = int(n_envs) if n_envs else max(1, min(self.nr_eval, 20, engine.max_batch))
         self.seed, self.limit, self.worker_id, self.game = seed, limit, worker_id, game
+        self.frame_skip, self.sticky = frame_skip, sticky
         self.calls = 0
         self.history = []
 
     def __call__(self):
         mean, mx = eval_with_envs(self.engine, self.nr_eval, self.n_envs,
                                   seed=self.seed + self.calls, limit=self.limit,
-                                  game=self.game)
+                                  game=self.game, frame_skip=self.frame_skip, sticky=self.sticky)
         self.calls += 1
         self.history.append((mean, mx))
         if self.client is not None:

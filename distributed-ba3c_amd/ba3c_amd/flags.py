@@ -4,6 +4,7 @@ its single-node launcher (`python -m ba3c_amd.train`) consume.  Slurm / TF-serve
 flags are accepted and ignored."""
 import argparse
 
+from . import frameskip
 from .boxing import BoxingVec
 from .breakout import BreakoutVec
 
@@ -15,6 +16,15 @@ GAMES = {GRID_BREAKOUT: (BreakoutVec, 4, "breakout"), GRID_BOXING: (BoxingVec, 1
 
 def string_to_bool(s):        # parse.py:5-6
     return str(s).lower() == "true"
+
+
+def frame_skip_arg(s):
+    """--frame_skip K -> K, --frame_skip LO-HI -> (LO, HI); the range is checked by resolve."""
+    try:
+        lo, hi = frameskip.parse_skip(str(s))
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected K or LO-HI, got %r" % s)
+    return lo if "-" not in str(s) else (lo, hi)
 
 
 def build_parser():
@@ -55,6 +65,12 @@ def build_parser():
     p.add_argument("--nr_eval", type=int, default=0,
                    help="episodes the Evaluator plays every --steps_per_epoch learner steps on "
                         "rank 0 (0: off; needs -e GridBreakout-v0 or GridBoxing-v0)")
+    p.add_argument("--frame_skip", type=frame_skip_arg, default=1,
+                   help="game steps per policy decision: K, or LO-HI for a uniform draw per "
+                        "decision (ALE's -v0: 2-4); 1 <= LO <= HI <= 16; needs an on-device game")
+    p.add_argument("--sticky", type=float, default=0.0,
+                   help="probability that a game step repeats the previous step's action "
+                        "(ALE's repeat_action_probability: 0.25); needs an on-device game")
     p.add_argument("--dummy", type=int, default=0)
     p.add_argument("--dummy_predictor", type=int, default=0)
     p.add_argument("--models_dir", default="models")
@@ -79,7 +95,7 @@ def resolve(args):
     """Apply the reference's implicit rules: --use_normal_fc disables replace_with_conv
     (run_job.py:131); --adam_debug sets beta2 := beta1 (train.py:460-461); --use_sync needs
     --ngrads (run_job.py:55-57).  An on-device game (GAMES) needs --channels 1 and --num_actions
-    >= its own number of actions; --nr_eval needs one of them."""
+    >= its own number of actions; --nr_eval, --frame_skip and --sticky need one of them."""
     if args.replace_with_conv is None:
         args.replace_with_conv = not args.use_normal_fc
     if args.adam_debug:
@@ -94,4 +110,11 @@ def resolve(args):
             raise SystemExit("-e %s has %d actions: it requires --num_actions >= %d" % (name, A, A))
     elif args.nr_eval:
         raise SystemExit("--nr_eval needs a game to evaluate: pass -e %s" % " or -e ".join(sorted(GAMES)))
+    try:
+        skip = frameskip.setting(args.frame_skip, args.sticky)
+    except ValueError as e:
+        raise SystemExit("--frame_skip / --sticky: %s" % e)
+    if skip is not None and args.environment not in GAMES:
+        raise SystemExit("--frame_skip / --sticky need an on-device game: pass -e %s"
+                         % " or -e ".join(sorted(GAMES)))
     return args

@@ -272,18 +272,22 @@ SimulatorProcess = SimulatorProcessStateExchange     # simulator.py:111-112
 
 class SyntheticSimulatorWorker(SimulatorProcess):
     """MySimulatorWorker (train.py:134-136) over the synthetic game, or over GridBreakout's /
-    GridBoxing's host player with game="breakout" / game="boxing"."""
+    GridBoxing's host player with game="breakout" / game="boxing" (frame_skip / sticky: as
+    envs.get_player takes them)."""
 
-    def __init__(self, idx, pipe_c2s, pipe_s2c, num_actions=4, seed=0, game="synthetic"):
+    def __init__(self, idx, pipe_c2s, pipe_s2c, num_actions=4, seed=0, game="synthetic",
+                 frame_skip=1, sticky=0.0):
         super(SyntheticSimulatorWorker, self).__init__(idx, pipe_c2s, pipe_s2c)
         self.num_actions = num_actions
         self.seed = seed
         self.game = game
+        self.frame_skip = frame_skip
+        self.sticky = sticky
 
     def _build_player(self):
         from .envs import get_player
         return get_player(self.idx, self.num_actions, self.seed + self.idx, train=True,
-                          game=self.game)
+                          game=self.game, frame_skip=self.frame_skip, sticky=self.sticky)
 
 
 def client_index(identity):

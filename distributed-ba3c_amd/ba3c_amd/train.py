@@ -6,7 +6,8 @@ Replaces run_job.py:13-148 -> distributed_tensorpack_mkl.sh -> OpenAIGym/train.p
 all-reduce over the node's GPUs), the trainer and the actor-learner loop (simulator master +
 predictor + BatchData, :520-534 — with the synthetic on-device environment, gym/ALE being
 absent, or with `-e GridBreakout-v0` / `-e GridBoxing-v0` the on-device Breakout / Boxing of
-flags.GAMES and, for `--nr_eval N`, the Evaluator callback every --steps_per_epoch steps), plus
+flags.GAMES (`--frame_skip` / `--sticky`: ALE's frame skip and sticky actions, for training and
+evaluation alike) and, for `--nr_eval N`, the Evaluator callback every --steps_per_epoch steps), plus
 the DebugLogCallback metrics channels and PeriodicPerStepCallback(ModelSaver) (:608-630) and
 `--load` (SaverRestore, :706-707).
 
@@ -159,7 +160,7 @@ def _run(args, rank, world):
     if args.nr_eval and rank == 0:
         from .evaluate import Evaluator
         evaluator = Evaluator(trainer.engine, args.nr_eval, client, seed=1000 + rank,
-                              game=args.environment)
+                              game=args.environment, frame_skip=args.frame_skip, sticky=args.sticky)
 
     def on_step(tr):
         metrics(tr)
@@ -185,7 +186,8 @@ def _run(args, rank, world):
         env = None
         if args.environment in GAMES:
             env = GAMES[args.environment][0](args.simulator_procs, seed=rank,
-                                             device=trainer.engine.device)
+                                             device=trainer.engine.device,
+                                             frame_skip=args.frame_skip, sticky=args.sticky)
         al = ActorLearner(trainer, n_envs=args.simulator_procs, batch_size=args.batch_size,
                           seed=rank, rs=np.random.RandomState(rank), on_train_step=on_step,
                           dummy_predictor=bool(args.dummy_predictor), env=env)

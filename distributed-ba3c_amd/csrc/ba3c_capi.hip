@@ -1350,6 +1350,30 @@ static int env_render(void* stream, const int32_t* game, int32_t n_envs, uint8_t
   return BA3C_OK;
 }
 
+// One decision of ba3c_amd/frameskip.py for every simulator (env_skip_kernel).
+template <class Rules>
+static int env_step_skip(void* stream, int32_t* game, int32_t* aux, const int64_t* action, int32_t n_envs,
+                         int32_t limit, int32_t skip_lo, int32_t skip_hi, int32_t sticky_q16, double* reward,
+                         uint8_t* over, int32_t* ep_score, uint8_t* frame, uint8_t* state) {
+  if (!game || !action) return fail(BA3C_ERR_INVALID, "null game / action pointer");
+  if (!aux) return fail(BA3C_ERR_INVALID, "null aux pointer");
+  if (!reward || !over || !ep_score) return fail(BA3C_ERR_INVALID, "null output pointer");
+  if (n_envs < 1 || limit < 1) return fail(BA3C_ERR_INVALID, "n_envs and limit must be >= 1");
+  if (!check_ptr(game) || (state && !check_ptr(state)) || (reinterpret_cast<uintptr_t>(frame) & 3))
+    return fail(BA3C_ERR_INVALID, "game / state must be 16-byte and frame 4-byte aligned");
+  if (reinterpret_cast<uintptr_t>(aux) & 7) return fail(BA3C_ERR_INVALID, "aux must be 8-byte aligned");
+  if (skip_lo < 1 || skip_hi < skip_lo || skip_hi > 16)
+    return fail(BA3C_ERR_INVALID, "frame skip must satisfy 1 <= skip_lo <= skip_hi <= 16");
+  if (sticky_q16 < 0 || sticky_q16 > 65536)
+    return fail(BA3C_ERR_INVALID, "sticky_q16 must be in [0, 65536]");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  EnvArgs a{game, action, limit, reward, over, ep_score, frame, state};
+  EnvSkipArgs k{aux, skip_lo, (uint32_t)(skip_hi - skip_lo + 1), (uint32_t)sticky_q16};
+  hipLaunchKernelGGL(env_skip_kernel<Rules>, dim3(n_envs), dim3(256), 0, s, a, k);
+  HIP_TRY(hipGetLastError());
+  return BA3C_OK;
+}
+
 // =========================================================================================
 extern "C" {
 
@@ -1975,6 +1999,22 @@ int ba3c_boxing_step(void* stream, int32_t* game, const int64_t* action, int32_t
                      int32_t limit, double* reward, uint8_t* over, int32_t* ep_score,
                      uint8_t* frame, uint8_t* state) {
   return env_step<BoxingRules>(stream, game, action, n_envs, limit, reward, over, ep_score, frame, state);
+}
+
+int ba3c_breakout_step_skip(void* stream, int32_t* game, int32_t* aux, const int64_t* action, int32_t n_envs,
+                            int32_t limit, int32_t skip_lo, int32_t skip_hi, int32_t sticky_q16,
+                            double* reward, uint8_t* over, int32_t* ep_score, uint8_t* frame,
+                            uint8_t* state) {
+  return env_step_skip<BreakoutRules>(stream, game, aux, action, n_envs, limit, skip_lo, skip_hi, sticky_q16,
+                                      reward, over, ep_score, frame, state);
+}
+
+int ba3c_boxing_step_skip(void* stream, int32_t* game, int32_t* aux, const int64_t* action, int32_t n_envs,
+                          int32_t limit, int32_t skip_lo, int32_t skip_hi, int32_t sticky_q16,
+                          double* reward, uint8_t* over, int32_t* ep_score, uint8_t* frame,
+                          uint8_t* state) {
+  return env_step_skip<BoxingRules>(stream, game, aux, action, n_envs, limit, skip_lo, skip_hi, sticky_q16,
+                                    reward, over, ep_score, frame, state);
 }
 
 int ba3c_boxing_render(void* stream, const int32_t* game, int32_t n_envs, uint8_t* frame,

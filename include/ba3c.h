@@ -377,6 +377,36 @@ int ba3c_boxing_step(void* stream, int32_t* game, const int64_t* action, int32_t
 int ba3c_boxing_render(void* stream, const int32_t* game, int32_t n_envs, uint8_t* frame,
                        uint8_t* state);
 
+/* ---- Frame skip and sticky actions for the on-device games ------------------------------- */
+
+/* One DECISION per call instead of one game step: ALE's `-v0` behaviour of a frame skip drawn
+ * per decision and of sticky actions.  ba3c_amd/frameskip.py states the semantics and is the
+ * oracle.  aux[e] = [rng2, prev] (two int32, 8-byte aligned rows) is the decision's own LCG
+ * (the games' multiplier and increment; a stream separate from the row's rng) and the last
+ * effective action.  Per simulator, in this order:
+ *   a = action[e] if 0 <= action[e] < 32 else 0
+ *   rng2 = lcg(rng2); k = skip_lo + (rng2 >> 16) % (skip_hi - skip_lo + 1)
+ *   k times: rng2 = lcg(rng2); eff = prev if ((rng2 >> 8) & 0xFFFF) < sticky_q16 else a;
+ *            prev = eff; one game step under eff (the rules of ba3c_*_step, unchanged);
+ *            on over: prev = 0 and the remaining sub-steps are dropped
+ * reward[e] is the sum over the executed sub-steps, over[e] / ep_score[e] report the episode
+ * that ended, frame / state receive ONE frame, the one after the last executed sub-step (on
+ * over: the new episode's first, the history cleared), as ba3c_*_step writes them.  `limit`
+ * counts game steps (the row's t), not decisions.
+ *
+ * They refuse what ba3c_*_step refuses and a null or misaligned aux, a skip outside
+ * 1 <= skip_lo <= skip_hi <= 16 and a sticky_q16 outside [0, 65536] (65536: every sub-step
+ * repeats prev), all on the host before touching the device.  One launch, one 256-thread
+ * workgroup per simulator, the k steps in registers. */
+int ba3c_breakout_step_skip(void* stream, int32_t* game, int32_t* aux, const int64_t* action,
+                            int32_t n_envs, int32_t limit, int32_t skip_lo, int32_t skip_hi,
+                            int32_t sticky_q16, double* reward, uint8_t* over, int32_t* ep_score,
+                            uint8_t* frame, uint8_t* state);
+int ba3c_boxing_step_skip(void* stream, int32_t* game, int32_t* aux, const int64_t* action,
+                          int32_t n_envs, int32_t limit, int32_t skip_lo, int32_t skip_hi,
+                          int32_t sticky_q16, double* reward, uint8_t* over, int32_t* ep_score,
+                          uint8_t* frame, uint8_t* state);
+
 #ifdef __cplusplus
 }
 #endif

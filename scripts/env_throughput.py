@@ -5,9 +5,13 @@ timed next to GridBreakout's fused step in the same run) against `SyntheticAtari
 kernel's achieved bytes/s against this box's measured HBM copy rate (a device-to-device copy, and
 an in-place update over the kernel's own footprint).  With --random N also the
 evaluation scores of a uniform-random policy (and, for boxing, of a NOOP policy) over N
-episodes.  Prints one JSON line.
+episodes (under the frame skip / stickiness given).  With --frame_skip K | LO-HI and / or --sticky P also the frame-skip step (one
+launch per DECISION, ba3c_amd.frameskip), timed alternately with the one-step fused step in the
+same run: µs per decision, µs per game step (at the mean k = (LO + HI) / 2 of the draw) and the
+ratios to one and to k one-step launches.  Prints one JSON line.
 
     python scripts/env_throughput.py [--game boxing] [--envs 8192 64] [--iters 200] [--random 20]
+                                     [--frame_skip 2-4] [--sticky 0.25]
 """
 import argparse
 import json
@@ -43,15 +47,21 @@ def main(argv=None):
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--random", type=int, default=0)
     ap.add_argument("--game", choices=["breakout", "boxing"], default="breakout")
+    ap.add_argument("--frame_skip", default="1")
+    ap.add_argument("--sticky", type=float, default=0.0)
     args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "needs the GPU: a CPU run measures nothing"
     from ba3c_amd.actor_learner import SyntheticAtari
     from ba3c_amd.breakout import BreakoutVec
     from ba3c_amd.flags import GAMES, GRID_BOXING, GRID_BREAKOUT
+    from ba3c_amd.frameskip import setting
     from ba3c_amd.rollout import FrameHistory
+    skip = setting(args.frame_skip, args.sticky)          # (lo, hi, q16), None: off
     name = GRID_BOXING if args.game == "boxing" else GRID_BREAKOUT
     Vec, A = GAMES[name][:2]
     out = {"game": name, "iters": args.iters, "envs": {}}
+    if skip is not None:
+        out["frame_skip"], out["sticky_q16"] = list(skip[:2]), skip[2]
 
     # HBM copy rate: a device-to-device copy the size of E=8192 states (read + write)
     n = 8192 * STATE_BYTES
@@ -74,15 +84,21 @@ def main(argv=None):
             actions_b = torch.randint(0, 4, (E,), generator=g, device="cuda")
             env_b, hist_b = BreakoutVec(E, seed=0), FrameHistory(E, 4, 1)
             env_b.reset_history(hist_b)
+        if skip is not None:
+            env_k = Vec(E, seed=0, frame_skip=skip[:2], sticky=skip[2] / 65536.0)
+            hist_k = FrameHistory(E, 4, 1)
+            env_k.reset_history(hist_k)
         syn, hist_s = SyntheticAtari(E, 4, seed=0), FrameHistory(E, 4, 1)
 
         def synthetic():
             frames, _, over = syn.step(actions)
             hist_s.push(frames, over)
         # alternate them so that all see the same machine state
-        fused, base, brk = [], [], []
+        fused, base, brk, skipped = [], [], [], []
         for _ in range(args.repeats):
             fused.append(timed(lambda: env.step_into(actions, hist), args.iters))
+            if skip is not None:
+                skipped.append(timed(lambda: env_k.step_into(actions, hist_k), args.iters))
             if Vec is not BreakoutVec:
                 brk.append(timed(lambda: env_b.step_into(actions_b, hist_b), args.iters))
             base.append(timed(synthetic, args.iters))
@@ -93,6 +109,15 @@ def main(argv=None):
             "state_bytes": traffic,
             "fused_GBps": round(traffic / min(fused) / 1e3, 1),
         }
+        if skipped:
+            mean_k = (skip[0] + skip[1]) / 2.0
+            out["envs"][str(E)].update({
+                "skip_decision_us": [round(v, 2) for v in skipped],
+                "skip_game_step_us": [round(v / mean_k, 2) for v in skipped],
+                "mean_k": mean_k,
+                "skip_over_one_step": round(min(skipped) / min(fused), 3),
+                "skip_over_k_one_steps": round(min(skipped) / (mean_k * min(fused)), 3),
+            })
         if brk:
             out["envs"][str(E)]["breakout_fused_step_into_us"] = [round(v, 2) for v in brk]
             out["envs"][str(E)]["fused_over_breakout"] = round(min(fused) / min(brk), 3)
@@ -101,8 +126,9 @@ def main(argv=None):
         from ba3c_amd.model import Model
         m = Model(num_actions=A, fc_neurons=128, fc_splits=4, batch_size=32, max_batch=32, seed=0)
         torch.manual_seed(0)
+        fs = dict(frame_skip=skip[:2], sticky=skip[2] / 65536.0) if skip is not None else {}
         mean, mx = eval_with_envs(m.engine, args.random, min(args.random, 20), seed=0,
-                                  policy=uniform_policy(A), game=name)
+                                  policy=uniform_policy(A), game=name, **fs)
         out["random_policy"] = {"episodes": args.random, "mean_score": mean, "max_score": mx}
         if args.game == "boxing":
             def noop(state):                              # argmax 0 = NOOP (FIRE every 30th step:
@@ -110,7 +136,7 @@ def main(argv=None):
                 p[:, 0] = 1.0                             # the evaluation's PreventStuckPlayer)
                 return p
             mean, mx = eval_with_envs(m.engine, args.random, min(args.random, 20), seed=0,
-                                      policy=noop, game=name)
+                                      policy=noop, game=name, **fs)
             out["noop_policy"] = {"episodes": args.random, "mean_score": mean, "max_score": mx}
     print(json.dumps(out), flush=True)
     return out
