@@ -106,6 +106,8 @@ def load():
         "ba3c_boxing_render": (i32, [P, P, i32, P, P]),
         "ba3c_breakout_step_skip": (i32, [P, P, P, P, i32, i32, i32, i32, i32, P, P, P, P, P]),
         "ba3c_boxing_step_skip": (i32, [P, P, P, P, i32, i32, i32, i32, i32, P, P, P, P, P]),
+        "ba3c_breakout_view": (i32, [P, P, i32, P, i32, P, P, i32, P]),
+        "ba3c_boxing_view": (i32, [P, P, i32, P, i32, P, P, i32, P]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("BA3C_LIB") and name in AB_OPTIONAL and not hasattr(lib, name):

@@ -86,6 +86,13 @@ DEFAULT_LIMIT = 40000                    # LimitLengthPlayer(40000), train.py:12
 # column indices of a game row
 AX, AY, OX, OY, A_CD, O_CD, A_SCORE, O_SCORE, T, RNG = range(10)
 ROW_INTS = 16
+# the colour of every shade for ba3c_amd.view: grey (i, i, i) except the shades render draws
+COLOURS = {0: (88, 144, 72), AGENT_SHADE: (240, 240, 240), OPP_SHADE: (20, 20, 20),
+           DIM: (200, 160, 60)}
+PALETTE = np.repeat(np.arange(256, dtype=np.uint8)[:, None], 3, axis=1)
+for _shade, _rgb in COLOURS.items():
+    PALETTE[_shade] = _rgb
+PALETTE.setflags(write=False)
 
 
 def action_id(dx, dy, fire):
@@ -235,6 +242,7 @@ class BoxingVec(object):
         self.aux = None
         if self.skip is not None:
             self.aux = torch.from_numpy(frameskip.initial_aux(self.E, seed)).to(dev)
+        self._palette = None               # PALETTE on the device, uploaded by the first view()
 
     def _ptr(self, t):
         return ctypes.c_void_p(t.data_ptr()) if t is not None else None
@@ -292,6 +300,13 @@ class BoxingVec(object):
         -> (reward float64 [E], over bool [E])."""
         self._check_hist(hist)
         return self._step(actions, None, hist.state)
+
+    def view(self, scale=1, sel=None, hud=None):
+        """The colour view of the current games (ba3c_amd.view.view_numpy is its statement):
+        torch.uint8 [n, Hc*scale, 84*scale, 3] on the device, one launch (ba3c_boxing_view);
+        sel: simulator indices (None: all), hud: uint8 [n, 20] or None.  Reads `game` only."""
+        from .view import device_view
+        return device_view(self, self.lib.ba3c_boxing_view, PALETTE, scale, sel, hud)
 
     @property
     def last_over(self):

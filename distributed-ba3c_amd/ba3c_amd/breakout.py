@@ -70,6 +70,14 @@ DEFAULT_LIMIT = 40000                # LimitLengthPlayer(40000), train.py:127
 # column indices of a game row
 PX, BX, BY, VX, VY, IN_PLAY, N_LIVES, SCORE, T, RNG, B0 = range(11)
 ROW_INTS = 16
+# the colour of every shade for ba3c_amd.view: grey (i, i, i) except the shades render draws
+COLOURS = {0: (0, 0, 0), 255: (236, 236, 236), LIVES_SHADE: (214, 214, 64),
+           230: (200, 72, 72), 200: (198, 108, 58), 170: (180, 122, 48),
+           140: (162, 162, 42), 110: (72, 160, 72), 80: (66, 72, 200)}
+PALETTE = np.repeat(np.arange(256, dtype=np.uint8)[:, None], 3, axis=1)
+for _shade, _rgb in COLOURS.items():
+    PALETTE[_shade] = _rgb
+PALETTE.setflags(write=False)
 
 
 def initial_game(n_envs, seed=0):
@@ -210,6 +218,7 @@ class BreakoutVec(object):
         self.aux = None
         if self.skip is not None:
             self.aux = torch.from_numpy(frameskip.initial_aux(self.E, seed)).to(dev)
+        self._palette = None               # PALETTE on the device, uploaded by the first view()
 
     def _ptr(self, t):
         return ctypes.c_void_p(t.data_ptr()) if t is not None else None
@@ -267,6 +276,13 @@ class BreakoutVec(object):
         -> (reward float64 [E], over bool [E])."""
         self._check_hist(hist)
         return self._step(actions, None, hist.state)
+
+    def view(self, scale=1, sel=None, hud=None):
+        """The colour view of the current games (ba3c_amd.view.view_numpy is its statement):
+        torch.uint8 [n, Hc*scale, 84*scale, 3] on the device, one launch (ba3c_breakout_view);
+        sel: simulator indices (None: all), hud: uint8 [n, 20] or None.  Reads `game` only."""
+        from .view import device_view
+        return device_view(self, self.lib.ba3c_breakout_view, PALETTE, scale, sel, hud)
 
     @property
     def last_over(self):

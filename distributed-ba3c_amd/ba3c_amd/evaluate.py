@@ -26,6 +26,42 @@ STUCK_REPEAT, STUCK_ACTION = 30, 1     # PreventStuckPlayer(pl, 30, 1), train.py
 GREEDY_EPS = 0.001                     # common.py:28
 
 
+class EvalPlayers(object):
+    """The decision path of n_envs evaluation players, shared by eval_with_envs and
+    ba3c_amd.record: greedy + eps from `rs` (a numpy RandomState) + PreventStuckPlayer(30, 1)."""
+
+    def __init__(self, engine, n_envs, rs, policy=None):
+        dev = engine.device
+        self.engine, self.n_envs, self.rs, self.policy = engine, n_envs, rs, policy
+        self.last = torch.full((n_envs,), -1, dtype=torch.int64, device=dev)
+        self.run = torch.zeros(n_envs, dtype=torch.int64, device=dev)
+        self.fire = torch.full((n_envs,), STUCK_ACTION, dtype=torch.int64, device=dev)
+
+    def step(self, env, hist, before_step=None):
+        """One decision of every player: forward, choose, fused step + history push.
+        before_step(probs, value, act) sees the policy's output and the actions handed to the
+        env (after PreventStuck) while `env` still holds the state they were chosen for; value
+        is None under a `policy`.  -> (reward, over) of env.step_into."""
+        engine, n_envs, rs, dev = self.engine, self.n_envs, self.rs, self.engine.device
+        value = None
+        if self.policy is None:
+            probs, _, value = engine.forward(hist.state)
+        else:
+            probs = self.policy(hist.state)
+        u = torch.from_numpy(rs.random_sample(n_envs)).to(dev)
+        sample = torch.from_numpy(rs.randint(engine.num_actions, size=n_envs).astype(np.int64)).to(dev)
+        act = greedy_actions(engine, probs, u, sample, GREEDY_EPS)
+        # PreventStuckPlayer: the last STUCK_REPEAT chosen actions are all the same -> FIRE
+        self.run = torch.where((act == self.last) & (self.run > 0), self.run + 1, torch.ones_like(self.run))
+        self.last = act
+        act = torch.where(self.run >= STUCK_REPEAT, self.fire, act)
+        if before_step is not None:
+            before_step(probs, value, act)
+        reward, over = env.step_into(act, hist)
+        self.run = torch.where(over, torch.zeros_like(self.run), self.run)      # act_que.clear()
+        return reward, over
+
+
 def eval_with_envs(engine, nr_eval, n_envs, seed=0, limit=DEFAULT_LIMIT, policy=None,
                    game=GRID_BREAKOUT, frame_skip=1, sticky=0.0):
     """Play `n_envs` evaluation players of `game` (a key of flags.GAMES) with `engine`'s greedy
@@ -44,21 +80,10 @@ def eval_with_envs(engine, nr_eval, n_envs, seed=0, limit=DEFAULT_LIMIT, policy=
     assert env.A <= A
     hist = FrameHistory(n_envs, hist_len=4, channels=1, device=dev)
     env.reset_history(hist)
-    last = torch.full((n_envs,), -1, dtype=torch.int64, device=dev)
-    run = torch.zeros(n_envs, dtype=torch.int64, device=dev)
-    fire = torch.full((n_envs,), STUCK_ACTION, dtype=torch.int64, device=dev)
+    players = EvalPlayers(engine, n_envs, rs, policy)
     stat = StatCounter()
     while stat.count < nr_eval:
-        probs = engine.forward(hist.state)[0] if policy is None else policy(hist.state)
-        u = torch.from_numpy(rs.random_sample(n_envs)).to(dev)
-        sample = torch.from_numpy(rs.randint(A, size=n_envs).astype(np.int64)).to(dev)
-        act = greedy_actions(engine, probs, u, sample, GREEDY_EPS)
-        # PreventStuckPlayer: the last STUCK_REPEAT chosen actions are all the same -> FIRE
-        run = torch.where((act == last) & (run > 0), run + 1, torch.ones_like(run))
-        last = act
-        act = torch.where(run >= STUCK_REPEAT, fire, act)
-        _, over = env.step_into(act, hist)
-        run = torch.where(over, torch.zeros_like(run), run)      # act_que.clear()
+        _, over = players.step(env, hist)
         over_h = over.cpu().numpy()
         if over_h.any():
             for s in env.ep_score.cpu().numpy()[over_h]:

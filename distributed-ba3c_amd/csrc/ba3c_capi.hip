@@ -24,6 +24,7 @@
 #include "ba3c_conv.h"
 #include "ba3c_conv3.h"
 #include "ba3c_dgrad1s.h"
+#include "ba3c_envview.h"
 #include "ba3c_gemm6.h"
 #include "ba3c_launch.h"
 #include "ba3c_multi.h"
@@ -1374,6 +1375,23 @@ static int env_step_skip(void* stream, int32_t* game, int32_t* aux, const int64_
   return BA3C_OK;
 }
 
+// The colour view of selected simulators (env_view_kernel; ba3c_amd/view.py is its oracle).
+template <class Rules>
+static int env_view(void* stream, const int32_t* game, int32_t n_envs, const int32_t* sel, int32_t n_sel,
+                    const uint8_t* palette, const uint8_t* hud, int32_t scale, uint8_t* out) {
+  if (!game || !palette || !out) return fail(BA3C_ERR_INVALID, "null game / palette / out pointer");
+  if (n_envs < 1 || n_sel < 1) return fail(BA3C_ERR_INVALID, "n_envs and n_sel must be >= 1");
+  if (scale < 1 || scale > VIEW_MAX_SCALE) return fail(BA3C_ERR_INVALID, "scale must be in [1, 8]");
+  if (!check_ptr(game) || ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(sel) |
+                            reinterpret_cast<uintptr_t>(hud)) & 3))
+    return fail(BA3C_ERR_INVALID, "game must be 16-byte and sel / hud / out 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  ViewArgs a{game, n_envs, sel, palette, hud, scale, out};
+  hipLaunchKernelGGL(env_view_kernel<Rules>, dim3(n_sel), dim3(256), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return BA3C_OK;
+}
+
 // =========================================================================================
 extern "C" {
 
@@ -2020,6 +2038,16 @@ int ba3c_boxing_step_skip(void* stream, int32_t* game, int32_t* aux, const int64
 int ba3c_boxing_render(void* stream, const int32_t* game, int32_t n_envs, uint8_t* frame,
                        uint8_t* state) {
   return env_render<BoxingRules>(stream, game, n_envs, frame, state);
+}
+
+int ba3c_breakout_view(void* stream, const int32_t* game, int32_t n_envs, const int32_t* sel, int32_t n_sel,
+                       const uint8_t* palette, const uint8_t* hud, int32_t scale, uint8_t* out) {
+  return env_view<BreakoutRules>(stream, game, n_envs, sel, n_sel, palette, hud, scale, out);
+}
+
+int ba3c_boxing_view(void* stream, const int32_t* game, int32_t n_envs, const int32_t* sel, int32_t n_sel,
+                     const uint8_t* palette, const uint8_t* hud, int32_t scale, uint8_t* out) {
+  return env_view<BoxingRules>(stream, game, n_envs, sel, n_sel, palette, hud, scale, out);
 }
 
 int ba3c_kernel_split(const ba3c_handle* h, int32_t kid) {

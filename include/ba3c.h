@@ -407,6 +407,28 @@ int ba3c_boxing_step_skip(void* stream, int32_t* game, int32_t* aux, const int64
                           int32_t sticky_q16, double* reward, uint8_t* over, int32_t* ep_score,
                           uint8_t* frame, uint8_t* state);
 
+/* ---- The colour view of the on-device games ---------------------------------------------- */
+
+/* Draw the CURRENT game of selected simulators as RGB images; ba3c_amd/view.py (view_numpy)
+ * states the image and is the oracle.  Image i shows simulator sel[i] (sel null: simulator i;
+ * n_sel images either way); an index outside [0, n_envs) gives an all-zero image.  The canvas is
+ * 84 px wide and Hc = 84 high, or Hc = 104 with hud: rows 0..83 are palette[shade] of the frame
+ * ba3c_*_render draws (palette: 256 RGB triples), rows 84..103 the HUD strip of view.py drawn
+ * from hud[i] (20 bytes: the bar heights of actions 0..17, the chosen action or 255, the value
+ * bar's length; the kernel clamps them).  Canvas pixel (y, x) fills the scale x scale block at
+ * (y*scale, x*scale) of out = uint8 [n_sel][Hc*scale][84*scale][3].
+ *
+ * The launch reads game, sel, hud and palette and writes out only: no game row, aux row or
+ * history is written.  They refuse a null game / palette / out, n_envs < 1, n_sel < 1, a scale
+ * outside [1, 8], a game that is not 16-byte and a sel / hud / out that is not 4-byte aligned,
+ * all on the host before touching the device.  One launch, one 256-thread workgroup per image. */
+int ba3c_breakout_view(void* stream, const int32_t* game, int32_t n_envs, const int32_t* sel,
+                       int32_t n_sel, const uint8_t* palette, const uint8_t* hud, int32_t scale,
+                       uint8_t* out);
+int ba3c_boxing_view(void* stream, const int32_t* game, int32_t n_envs, const int32_t* sel,
+                     int32_t n_sel, const uint8_t* palette, const uint8_t* hud, int32_t scale,
+                     uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

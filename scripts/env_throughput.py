@@ -8,10 +8,13 @@ evaluation scores of a uniform-random policy (and, for boxing, of a NOOP policy)
 episodes (under the frame skip / stickiness given).  With --frame_skip K | LO-HI and / or --sticky P also the frame-skip step (one
 launch per DECISION, ba3c_amd.frameskip), timed alternately with the one-step fused step in the
 same run: µs per decision, µs per game step (at the mean k = (LO + HI) / 2 of the draw) and the
-ratios to one and to k one-step launches.  Prints one JSON line.
+ratios to one and to k one-step launches.  With --view S [S ...] also the colour view
+(`Vec.view`, ba3c_amd.view) of all E simulators with a HUD at each scale S, timed alternately with
+the fused step in the same run, and its store rate (Hc*S * 252*S bytes per simulator, Hc = 104).
+Prints one JSON line.
 
     python scripts/env_throughput.py [--game boxing] [--envs 8192 64] [--iters 200] [--random 20]
-                                     [--frame_skip 2-4] [--sticky 0.25]
+                                     [--frame_skip 2-4] [--sticky 0.25] [--view 1 3]
 """
 import argparse
 import json
@@ -49,6 +52,7 @@ def main(argv=None):
     ap.add_argument("--game", choices=["breakout", "boxing"], default="breakout")
     ap.add_argument("--frame_skip", default="1")
     ap.add_argument("--sticky", type=float, default=0.0)
+    ap.add_argument("--view", type=int, nargs="+", default=[])
     args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "needs the GPU: a CPU run measures nothing"
     from ba3c_amd.actor_learner import SyntheticAtari
@@ -74,6 +78,13 @@ def main(argv=None):
     us = min(timed(lambda: src.add_(1), 50) for _ in range(args.repeats))
     out["inplace_GBps"] = round(2 * n / us / 1e3, 1)
     del src, dst
+    if args.view:
+        # the view only stores: a fill the size of its largest output (E = 8192, S = max) as yardstick
+        fill = torch.empty(8192 * (104 * max(args.view)) * (252 * max(args.view)), dtype=torch.uint8, device="cuda")
+        us = min(timed(lambda: fill.zero_(), 20, 3) for _ in range(args.repeats))
+        out["fill_bytes"] = fill.numel()
+        out["fill_GBps"] = round(fill.numel() / us / 1e3, 1)
+        del fill
 
     for E in args.envs:
         g = torch.Generator(device="cuda").manual_seed(0)
@@ -95,8 +106,12 @@ def main(argv=None):
             hist_s.push(frames, over)
         # alternate them so that all see the same machine state
         fused, base, brk, skipped = [], [], [], []
+        viewed = {S: [] for S in args.view}
+        hud = torch.randint(0, 256, (E, 20), generator=g, device="cuda").to(torch.uint8)
         for _ in range(args.repeats):
             fused.append(timed(lambda: env.step_into(actions, hist), args.iters))
+            for S in args.view:                           # fewer calls: an image is up to 64x a frame
+                viewed[S].append(timed(lambda: env.view(scale=S, hud=hud), max(args.iters // 10, 10), 3))
             if skip is not None:
                 skipped.append(timed(lambda: env_k.step_into(actions, hist_k), args.iters))
             if Vec is not BreakoutVec:
@@ -118,6 +133,12 @@ def main(argv=None):
                 "skip_over_one_step": round(min(skipped) / min(fused), 3),
                 "skip_over_k_one_steps": round(min(skipped) / (mean_k * min(fused)), 3),
             })
+        for S, us in viewed.items():
+            n_bytes = E * (104 * S) * (252 * S)
+            out["envs"][str(E)]["view_S%d" % S] = {
+                "us": [round(v, 2) for v in us], "out_bytes": n_bytes,
+                "store_GBps": round(n_bytes / min(us) / 1e3, 1),
+                "over_fused_step": round(min(us) / min(fused), 2)}
         if brk:
             out["envs"][str(E)]["breakout_fused_step_into_us"] = [round(v, 2) for v in brk]
             out["envs"][str(E)]["fused_over_breakout"] = round(min(fused) / min(brk), 3)
