@@ -24,6 +24,20 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def greedy(probs, u, random_actions, eps=0.001, actions=None):
+    """Ba3cEngine.greedy; it needs no network (ba3c_greedy takes no handle), so a bare policy's
+    output can be put through the same kernel."""
+    B, A = probs.shape
+    assert u.dtype == torch.float64 and u.shape == (B,)
+    assert random_actions.dtype == torch.int64 and random_actions.shape == (B,)
+    if actions is None:
+        actions = torch.empty(B, dtype=torch.int64, device=probs.device)
+    _lib.check(_lib.load().ba3c_greedy(_stream(), _ptr(probs.contiguous()), _ptr(u),
+                                       _ptr(random_actions.contiguous()), B, A, float(eps),
+                                       _ptr(actions)))
+    return actions
+
+
 class Ba3cEngine(object):
     """One network instance on one GPU.
 
@@ -235,15 +249,7 @@ class Ba3cEngine(object):
 
     def greedy(self, probs, u, random_actions, eps=0.001, actions=None):
         """Evaluation action: first argmax of each row, random_actions[i] where u[i] < eps."""
-        B, A = probs.shape
-        assert u.dtype == torch.float64 and u.shape == (B,)
-        assert random_actions.dtype == torch.int64 and random_actions.shape == (B,)
-        if actions is None:
-            actions = torch.empty(B, dtype=torch.int64, device=probs.device)
-        _lib.check(self.lib.ba3c_greedy(_stream(), _ptr(probs.contiguous()), _ptr(u),
-                                        _ptr(random_actions.contiguous()), B, A, float(eps),
-                                        _ptr(actions)))
-        return actions
+        return greedy(probs, u, random_actions, eps, actions)
 
     # -- timing probe -------------------------------------------------------------------
     def probe_enable(self, kernel, every=1):

@@ -27,8 +27,8 @@ GREEDY_EPS = 0.001                     # common.py:28
 
 
 class EvalPlayers(object):
-    """The decision path of n_envs evaluation players, shared by eval_with_envs and
-    ba3c_amd.record: greedy + eps from `rs` (a numpy RandomState) + PreventStuckPlayer(30, 1)."""
+    """The decision path of n_envs evaluation players, shared by eval_with_envs,
+    ba3c_amd.record and ba3c_amd.duel.match (one per side): greedy + eps from `rs` (a numpy RandomState) + PreventStuckPlayer(30, 1)."""
 
     def __init__(self, engine, n_envs, rs, policy=None):
         dev = engine.device
@@ -37,17 +37,16 @@ class EvalPlayers(object):
         self.run = torch.zeros(n_envs, dtype=torch.int64, device=dev)
         self.fire = torch.full((n_envs,), STUCK_ACTION, dtype=torch.int64, device=dev)
 
-    def step(self, env, hist, before_step=None):
-        """One decision of every player: forward, choose, fused step + history push.
-        before_step(probs, value, act) sees the policy's output and the actions handed to the
-        env (after PreventStuck) while `env` still holds the state they were chosen for; value
-        is None under a `policy`.  -> (reward, over) of env.step_into."""
+    def decide(self, state):
+        """One decision of every player from `state` [n_envs,84,84,4]: forward, choose.
+        -> (probs, value, act): the policy's output (value is None under a `policy`) and the
+        actions to hand to the env (after PreventStuck).  Follow the env's step by `ended`."""
         engine, n_envs, rs, dev = self.engine, self.n_envs, self.rs, self.engine.device
         value = None
         if self.policy is None:
-            probs, _, value = engine.forward(hist.state)
+            probs, _, value = engine.forward(state)
         else:
-            probs = self.policy(hist.state)
+            probs = self.policy(state)
         u = torch.from_numpy(rs.random_sample(n_envs)).to(dev)
         sample = torch.from_numpy(rs.randint(engine.num_actions, size=n_envs).astype(np.int64)).to(dev)
         act = greedy_actions(engine, probs, u, sample, GREEDY_EPS)
@@ -55,10 +54,22 @@ class EvalPlayers(object):
         self.run = torch.where((act == self.last) & (self.run > 0), self.run + 1, torch.ones_like(self.run))
         self.last = act
         act = torch.where(self.run >= STUCK_REPEAT, self.fire, act)
+        return probs, value, act
+
+    def ended(self, over):
+        """The players whose episode ended in the step that followed `decide` (bool [n_envs])."""
+        self.run = torch.where(over, torch.zeros_like(self.run), self.run)      # act_que.clear()
+
+    def step(self, env, hist, before_step=None):
+        """One decision of every player: forward, choose, fused step + history push.
+        before_step(probs, value, act) sees the policy's output and the actions handed to the
+        env (after PreventStuck) while `env` still holds the state they were chosen for; value
+        is None under a `policy`.  -> (reward, over) of env.step_into."""
+        probs, value, act = self.decide(hist.state)
         if before_step is not None:
             before_step(probs, value, act)
         reward, over = env.step_into(act, hist)
-        self.run = torch.where(over, torch.zeros_like(self.run), self.run)      # act_que.clear()
+        self.ended(over)
         return reward, over
 
 

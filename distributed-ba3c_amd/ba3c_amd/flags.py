@@ -71,6 +71,10 @@ def build_parser():
     p.add_argument("--sticky", type=float, default=0.0,
                    help="probability that a game step repeats the previous step's action "
                         "(ALE's repeat_action_probability: 0.25); needs an on-device game")
+    p.add_argument("--self_play", action="store_true",
+                   help="train -e GridBoxing-v0 by self-play: --simulator_procs players (an even "
+                        "number) in --simulator_procs / 2 two-player games (ba3c_amd.duel); "
+                        "--nr_eval still plays the scripted opponent")
     p.add_argument("--dummy", type=int, default=0)
     p.add_argument("--dummy_predictor", type=int, default=0)
     p.add_argument("--models_dir", default="models")
@@ -95,7 +99,8 @@ def resolve(args):
     """Apply the reference's implicit rules: --use_normal_fc disables replace_with_conv
     (run_job.py:131); --adam_debug sets beta2 := beta1 (train.py:460-461); --use_sync needs
     --ngrads (run_job.py:55-57).  An on-device game (GAMES) needs --channels 1 and --num_actions
-    >= its own number of actions; --nr_eval, --frame_skip and --sticky need one of them."""
+    >= its own number of actions; --nr_eval, --frame_skip and --sticky need one of them.
+    --self_play needs GridBoxing, an even --simulator_procs and neither frame skip nor sticky."""
     if args.replace_with_conv is None:
         args.replace_with_conv = not args.use_normal_fc
     if args.adam_debug:
@@ -117,4 +122,11 @@ def resolve(args):
     if skip is not None and args.environment not in GAMES:
         raise SystemExit("--frame_skip / --sticky need an on-device game: pass -e %s"
                          % " or -e ".join(sorted(GAMES)))
+    if args.self_play:
+        if args.environment != GRID_BOXING:
+            raise SystemExit("--self_play is two-player GridBoxing: pass -e %s" % GRID_BOXING)
+        if args.simulator_procs % 2:
+            raise SystemExit("--self_play counts players, two per game: --simulator_procs must be even")
+        if skip is not None:
+            raise SystemExit("--self_play has no --frame_skip / --sticky")
     return args

@@ -7,7 +7,8 @@ all-reduce over the node's GPUs), the trainer and the actor-learner loop (simula
 predictor + BatchData, :520-534 — with the synthetic on-device environment, gym/ALE being
 absent, or with `-e GridBreakout-v0` / `-e GridBoxing-v0` the on-device Breakout / Boxing of
 flags.GAMES (`--frame_skip` / `--sticky`: ALE's frame skip and sticky actions, for training and
-evaluation alike) and, for `--nr_eval N`, the Evaluator callback every --steps_per_epoch steps), plus
+evaluation alike; `--self_play`: two-player GridBoxing, ba3c_amd.duel, every game's two sides
+both played by the learner) and, for `--nr_eval N`, the Evaluator callback every --steps_per_epoch steps), plus
 the DebugLogCallback metrics channels and PeriodicPerStepCallback(ModelSaver) (:608-630) and
 `--load` (SaverRestore, :706-707).
 
@@ -184,7 +185,11 @@ def _run(args, rank, world):
         sim_steps = 0
     else:
         env = None
-        if args.environment in GAMES:
+        if args.self_play:
+            # --simulator_procs players in half as many two-player games; both sides learn
+            from .duel import BoxingDuelVec
+            env = BoxingDuelVec(args.simulator_procs // 2, seed=rank, device=trainer.engine.device)
+        elif args.environment in GAMES:
             env = GAMES[args.environment][0](args.simulator_procs, seed=rank,
                                              device=trainer.engine.device,
                                              frame_skip=args.frame_skip, sticky=args.sticky)

@@ -24,6 +24,7 @@
 #include "ba3c_conv.h"
 #include "ba3c_conv3.h"
 #include "ba3c_dgrad1s.h"
+#include "ba3c_duel.h"
 #include "ba3c_envview.h"
 #include "ba3c_gemm6.h"
 #include "ba3c_launch.h"
@@ -2038,6 +2039,35 @@ int ba3c_boxing_step_skip(void* stream, int32_t* game, int32_t* aux, const int64
 int ba3c_boxing_render(void* stream, const int32_t* game, int32_t n_envs, uint8_t* frame,
                        uint8_t* state) {
   return env_render<BoxingRules>(stream, game, n_envs, frame, state);
+}
+
+int ba3c_boxing_duel_step(void* stream, int32_t* game, const int64_t* action, int32_t n_games, int32_t limit,
+                          double* reward, uint8_t* over, int32_t* ep_score, uint8_t* frame, uint8_t* state) {
+  if (!game || !action) return fail(BA3C_ERR_INVALID, "null game / action pointer");
+  if (!reward || !over || !ep_score) return fail(BA3C_ERR_INVALID, "null output pointer");
+  if (n_games < 1 || limit < 1) return fail(BA3C_ERR_INVALID, "n_games and limit must be >= 1");
+  if (!check_ptr(game) || (state && !check_ptr(state)) || (reinterpret_cast<uintptr_t>(frame) & 3))
+    return fail(BA3C_ERR_INVALID, "game / state must be 16-byte and frame 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DuelArgs a{game, action, n_games, limit, reward, over, ep_score, frame, state};
+  hipLaunchKernelGGL(duel_kernel, dim3(n_games), dim3(256), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return BA3C_OK;
+}
+
+int ba3c_boxing_duel_render(void* stream, const int32_t* game, int32_t n_games, uint8_t* frame,
+                            uint8_t* state) {
+  if (!game) return fail(BA3C_ERR_INVALID, "null game pointer");
+  if (n_games < 1) return fail(BA3C_ERR_INVALID, "n_games must be >= 1");
+  if (!check_ptr(game) || (state && !check_ptr(state)) || (reinterpret_cast<uintptr_t>(frame) & 3))
+    return fail(BA3C_ERR_INVALID, "game / state must be 16-byte and frame 4-byte aligned");
+  if (!frame && !state) return BA3C_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // render only: the kernel never writes the row when action is null
+  DuelArgs a{const_cast<int32_t*>(game), nullptr, n_games, 1, nullptr, nullptr, nullptr, frame, state};
+  hipLaunchKernelGGL(duel_kernel, dim3(n_games), dim3(256), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return BA3C_OK;
 }
 
 int ba3c_breakout_view(void* stream, const int32_t* game, int32_t n_envs, const int32_t* sel, int32_t n_sel,

@@ -377,6 +377,45 @@ int ba3c_boxing_step(void* stream, int32_t* game, const int64_t* action, int32_t
 int ba3c_boxing_render(void* stream, const int32_t* game, int32_t n_envs, uint8_t* frame,
                        uint8_t* state);
 
+/* ---- Two-player GridBoxing: both boxers driven by actions (self-play, matches) ----------- */
+
+/* A second way to run GridBoxing; ba3c_amd/duel.py states the rules (step_numpy, render_numpy,
+ * mirror_rows) and is the oracle of these entry points.  The row is GridBoxing's,
+ *   game[e] = [ax, ay, bx, by, a_cd, b_cd, a_score, b_score, t, rng, 0, 0, 0, 0, 0, 0]
+ * with side B in the scripted opponent's fields; rng is carried unchanged (no draw is made).
+ * n_games games have 2*n_games PLAYERS: player e is side A of game e, player n_games + e is
+ * side B of game e, and action, reward, over, ep_score, frame and state all have 2*n_games rows
+ * in that order.  Each side acts and sees in its own frame of reference, in which it is the
+ * white boxer that starts on the left: side B's is the mirror x -> 78 - x of the world (its
+ * RIGHT is the world's left, its dy is unchanged).
+ *
+ * ba3c_boxing_duel_step decodes both actions as ba3c_boxing_step does (ALE's 18, anything else
+ * NOOP, never an index) and applies, in this order: both cooldowns count down; both boxers
+ * move 2 px and are clamped; ONE judgement p in {0, 1, 2} of the reach on the positions after
+ * both moves (GridBoxing's pts); a side that fires with its cooldown at 0 starts its cooldown
+ * (8) and lands p; scores are added; a boxer that was hit is knocked 3 px away from the other
+ * (side B to the right iff bx >= ax at the judgement) and clamped; t += 1.  reward[e] = points
+ * landed by A minus points landed by B, reward[n_games + e] is its negative; over is shared
+ * (either score >= 100, t >= 1680 or t >= limit); where over, ep_score[e] = a_score - b_score,
+ * ep_score[n_games + e] its negative, and the row restarts as a fresh GridBoxing episode.
+ * Side A's frame is ba3c_boxing_render's frame of the row, side B's that of the mirrored row
+ * (78-bx, by, 78-ax, ay, b_cd, a_cd, b_score, a_score, t, rng); frame ([2G][84*84], may be
+ * NULL) and state ([2G][84*84][4], may be NULL) are written as by ba3c_boxing_step, on over
+ * both players' histories restart.
+ *
+ * ba3c_boxing_duel_render renders both sides of the current rows without stepping; with state
+ * it starts both histories; with neither frame nor state it returns BA3C_OK without a launch.
+ *
+ * The host-side refusals are ba3c_boxing_step's / ba3c_boxing_render's (null game / action /
+ * outputs, n_games < 1, limit < 1, misaligned game / state / frame -> BA3C_ERR_INVALID before
+ * touching the device); they never synchronise and never allocate.  One launch, one 256-thread
+ * workgroup per GAME, which steps the row once and renders both sides. */
+int ba3c_boxing_duel_step(void* stream, int32_t* game, const int64_t* action, int32_t n_games,
+                          int32_t limit, double* reward, uint8_t* over, int32_t* ep_score,
+                          uint8_t* frame, uint8_t* state);
+int ba3c_boxing_duel_render(void* stream, const int32_t* game, int32_t n_games, uint8_t* frame,
+                            uint8_t* state);
+
 /* ---- Frame skip and sticky actions for the on-device games ------------------------------- */
 
 /* One DECISION per call instead of one game step: ALE's `-v0` behaviour of a frame skip drawn

@@ -11,10 +11,13 @@ same run: µs per decision, µs per game step (at the mean k = (LO + HI) / 2 of 
 ratios to one and to k one-step launches.  With --view S [S ...] also the colour view
 (`Vec.view`, ba3c_amd.view) of all E simulators with a HUD at each scale S, timed alternately with
 the fused step in the same run, and its store rate (Hc*S * 252*S bytes per simulator, Hc = 104).
+With --duel also two-player GridBoxing (`BoxingDuelVec.step_into`, ba3c_amd.duel) at G = E / 2
+games next to `BoxingVec.step_into` at E simulators (by default G = 4096 against E = 8192 and
+G = 32 against E = 64: the same players and bytes), timed alternately in the same run.
 Prints one JSON line.
 
     python scripts/env_throughput.py [--game boxing] [--envs 8192 64] [--iters 200] [--random 20]
-                                     [--frame_skip 2-4] [--sticky 0.25] [--view 1 3]
+                                     [--frame_skip 2-4] [--sticky 0.25] [--view 1 3] [--duel]
 """
 import argparse
 import json
@@ -43,8 +46,38 @@ def timed(fn, iters, warmup=20):
     return a.elapsed_time(b) * 1e3 / iters
 
 
+def duel_table(envs, iters, repeats):
+    """--duel: BoxingDuelVec.step_into at G = E / 2 games next to BoxingVec.step_into at E
+    simulators (the same number of players, frames and history bytes), alternating."""
+    from ba3c_amd.boxing import BoxingVec
+    from ba3c_amd.duel import BoxingDuelVec
+    from ba3c_amd.rollout import FrameHistory
+    out = {}
+    for E in envs:
+        G = E // 2
+        g = torch.Generator(device="cuda").manual_seed(0)
+        actions = torch.randint(0, 18, (2 * G,), generator=g, device="cuda")
+        duel, hist_d = BoxingDuelVec(G, seed=0), FrameHistory(2 * G, 4, 1)
+        duel.reset_history(hist_d)
+        solo, hist_s = BoxingVec(2 * G, seed=0), FrameHistory(2 * G, 4, 1)
+        solo.reset_history(hist_s)
+        t_duel, t_solo = [], []
+        for _ in range(repeats):
+            t_duel.append(timed(lambda: duel.step_into(actions, hist_d), iters))
+            t_solo.append(timed(lambda: solo.step_into(actions, hist_s), iters))
+        traffic = 2 * (2 * G) * STATE_BYTES
+        out[str(G)] = {"players": 2 * G, "duel_step_into_us": [round(v, 2) for v in t_duel],
+                       "boxing_step_into_us": [round(v, 2) for v in t_solo], "state_bytes": traffic,
+                       "duel_GBps": round(traffic / min(t_duel) / 1e3, 1),
+                       "boxing_GBps": round(traffic / min(t_solo) / 1e3, 1),
+                       "duel_over_boxing": round(min(t_duel) / min(t_solo), 3)}
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--duel", action="store_true",
+                    help="also time two-player GridBoxing at G = E / 2 games against BoxingVec at E")
     ap.add_argument("--envs", type=int, nargs="+", default=[8192, 64])
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
@@ -142,6 +175,8 @@ def main(argv=None):
         if brk:
             out["envs"][str(E)]["breakout_fused_step_into_us"] = [round(v, 2) for v in brk]
             out["envs"][str(E)]["fused_over_breakout"] = round(min(fused) / min(brk), 3)
+    if args.duel:
+        out["duel"] = duel_table(args.envs, args.iters, args.repeats)
     if args.random:
         from ba3c_amd.evaluate import eval_with_envs, uniform_policy
         from ba3c_amd.model import Model
