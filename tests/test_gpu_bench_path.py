@@ -23,6 +23,7 @@ import pytest
 import torch
 
 from oracle import ba3c_oracle as O
+from mixed_frames import device_mixed_returns, mixed_frames, scaled_params
 from test_gpu_parity import GRAD_TOL, FWD_TOL, as64, case, dev, engine, gpu_decisions, rel
 
 pytestmark = pytest.mark.gpu
@@ -57,14 +58,20 @@ def test_bench_geometry_b160_matches_chunked_oracle():
     assert rel(probs.cpu().numpy(), t["logits"]) < FWD_TOL
 
 
-def test_conv2_geometries_are_bit_identical_across_small_batch_switch():
+@pytest.mark.parametrize("frames", ["random", "mixed"])
+def test_conv2_geometries_are_bit_identical_across_small_batch_switch(frames):
     """The same 128 images run once as a B=128 batch (2-/3-row-band conv2 kernels) and twice
     over as a B=256 batch (whole-map / full-band kernels).  The loss is a batch mean, so every
     backward value of the B=256 run is exactly half the B=128 one (1/256 = 1/128 / 2: powers of
-    two commute with every rounding); activations are identical."""
+    two commute with every rounding); activations are identical.  mixed: images, returns and
+    weight tensors whose scaled-fp16 exponents differ (tests/mixed_frames.py)."""
     cfgk = dict(A=4, C=4, F=512, S=1)
     params, state, action, R, _ = case(129, 128, wscale=2.0, **cfgk)
     eng = engine(max_batch=256, **cfgk)
+    if frames == "mixed":
+        params, state = scaled_params(129), mixed_frames(128, 129)[0]
+        eng.load_params(params)
+        R = device_mixed_returns(eng, dev(state), 129)
     eng.load_params(params)
     fwd_names, bwd_names = ("p1", "p2", "c1", "c2"), ("dp2", "dp1", "dp0")
     d = lambda x: dev(np.concatenate([x, x]))
