@@ -98,6 +98,8 @@ def load():
         "ba3c_kernel_merged": (i32, [P, i32]),
         "ba3c_kernel_family": (i32, [P, i32]),
         "ba3c_nstep_returns": (i32, [P, P, P, P, P, P, i32, i32, ctypes.c_double, P, P, P, P, P]),
+        "ba3c_lambda_returns": (i32, [P, P, P, P, P, P, i32, i32, ctypes.c_double, ctypes.c_double,
+                                      P, P, P, P, P]),
         "ba3c_gather_rows": (i32, [P, P, P, i32, i64, P]),
         "ba3c_history_push": (i32, [P, P, P, P, i32, i32, i32, i32]),
         "ba3c_breakout_step": (i32, [P, P, P, i32, i32, P, P, P, P, P]),

@@ -17,7 +17,7 @@ grayscale frames, integer rewards incl. values outside [-1, 1] that the returns 
 import numpy as np
 import torch
 
-from .rollout import BatchQueue, FrameHistory, RolloutBuffer
+from .rollout import GAMMA, LOCAL_TIME_MAX, BatchQueue, FrameHistory, RolloutBuffer
 
 
 class SyntheticAtari(object):
@@ -61,8 +61,12 @@ class ActorLearner(object):
     predictor: the reference's towerp0 reads the same variables, train.py:355-362)."""
 
     def __init__(self, trainer, n_envs, batch_size, seed=0, rs=None, on_train_step=None,
-                 dummy_predictor=False, env=None):
-        """env: the vector of simulators (None: SyntheticAtari, as before); an env with
+                 dummy_predictor=False, env=None, local_time_max=LOCAL_TIME_MAX, gamma=GAMMA,
+                 gae_lambda=1.0):
+        """local_time_max, gamma, gae_lambda: the rollout length, discount and GAE lambda of the
+        RolloutBuffer's returns (--local_time_max, --gamma, --gae_lambda; the defaults are the
+        reference's 5-step, 0.99, n-step recipe).
+        env: the vector of simulators (None: SyntheticAtari, as before); an env with
         `step_into(actions, hist)` (BreakoutVec, BoxingVec) is stepped through it, the
         frame-history push fused into the env's launch.
         on_train_step(trainer): called after every learner step (callbacks / metrics);
@@ -78,7 +82,8 @@ class ActorLearner(object):
         self.env = env
         self._fused = hasattr(env, "step_into")
         self.hist = FrameHistory(n_envs, hist_len=4, channels=1, device=eng.device)
-        self.buf = RolloutBuffer(n_envs, channels=4, device=eng.device)
+        self.buf = RolloutBuffer(n_envs, channels=4, local_time_max=local_time_max, gamma=gamma,
+                                 gae_lambda=gae_lambda, device=eng.device)
         self.queue = BatchQueue(batch_size)
         self.rs = rs if rs is not None else np.random.RandomState(seed)
         self.hist.push(self.env.frames(), torch.ones(n_envs, dtype=torch.bool, device=eng.device))

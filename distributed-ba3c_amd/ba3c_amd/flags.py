@@ -12,6 +12,9 @@ GRID_BREAKOUT = "GridBreakout-v0"
 GRID_BOXING = "GridBoxing-v0"
 # -e name -> (vector class, the game's number of actions, envs.get_player's game key)
 GAMES = {GRID_BREAKOUT: (BreakoutVec, 4, "breakout"), GRID_BOXING: (BoxingVec, 18, "boxing")}
+MAX_LOCAL_TIME = 128                  # ba3c_lambda_returns holds local_time_max + 1 <= 129 ring slots
+STATE_BYTES = 84 * 84 * 4             # one stacked state of the rollout ring
+MAX_RING_BYTES = 16 * 2 ** 30         # simulator_procs x (local_time_max + 1) states
 
 
 def string_to_bool(s):        # parse.py:5-6
@@ -75,6 +78,14 @@ def build_parser():
                    help="train -e GridBoxing-v0 by self-play: --simulator_procs players (an even "
                         "number) in --simulator_procs / 2 two-player games (ba3c_amd.duel); "
                         "--nr_eval still plays the scripted opponent")
+    p.add_argument("--local_time_max", type=int, default=5,
+                   help="decisions per rollout segment (train.py:102 LOCAL_TIME_MAX), 1..128")
+    p.add_argument("--gamma", type=float, default=0.99,
+                   help="discount per decision (train.py:94 GAMMA), in (0, 1]")
+    p.add_argument("--gae_lambda", type=float, default=1.0,
+                   help="lambda of the returns the learner fits (ba3c_amd.returns), in [0, 1]: "
+                        "1 is the reference's n-step return, below 1 the policy advantage is "
+                        "GAE(lambda) and the value target TD(lambda)")
     p.add_argument("--dummy", type=int, default=0)
     p.add_argument("--dummy_predictor", type=int, default=0)
     p.add_argument("--models_dir", default="models")
@@ -100,7 +111,9 @@ def resolve(args):
     (run_job.py:131); --adam_debug sets beta2 := beta1 (train.py:460-461); --use_sync needs
     --ngrads (run_job.py:55-57).  An on-device game (GAMES) needs --channels 1 and --num_actions
     >= its own number of actions; --nr_eval, --frame_skip and --sticky need one of them.
-    --self_play needs GridBoxing, an even --simulator_procs and neither frame skip nor sticky."""
+    --self_play needs GridBoxing, an even --simulator_procs and neither frame skip nor sticky.
+    --gae_lambda in [0, 1], --local_time_max in 1..128, --gamma in (0, 1], and the states ring
+    they imply at most 16 GiB; they apply to every -e, with and without --self_play."""
     if args.replace_with_conv is None:
         args.replace_with_conv = not args.use_normal_fc
     if args.adam_debug:
@@ -129,4 +142,16 @@ def resolve(args):
             raise SystemExit("--self_play counts players, two per game: --simulator_procs must be even")
         if skip is not None:
             raise SystemExit("--self_play has no --frame_skip / --sticky")
+    # written so that a NaN fails either range
+    if not 0.0 <= args.gae_lambda <= 1.0:
+        raise SystemExit("--gae_lambda %r: lambda must be in [0, 1]" % args.gae_lambda)
+    if not 1 <= args.local_time_max <= MAX_LOCAL_TIME:
+        raise SystemExit("--local_time_max %d: must be in 1..%d" % (args.local_time_max, MAX_LOCAL_TIME))
+    if not 0.0 < args.gamma <= 1.0:
+        raise SystemExit("--gamma %r: the discount must be in (0, 1]" % args.gamma)
+    ring = args.simulator_procs * (args.local_time_max + 1) * STATE_BYTES
+    if ring > MAX_RING_BYTES:
+        raise SystemExit("--simulator_procs %d x --local_time_max %d: the states ring would take "
+                         "%.1f GiB (limit 16 GiB)"
+                         % (args.simulator_procs, args.local_time_max, ring / 2.0 ** 30))
     return args

@@ -5,7 +5,7 @@ RL/simulator.py:160-185) for a vector of simulators, kept in HBM: `on_state` app
 simulator's new transition (state, sampled action, predictor value) as `_on_state` does,
 `on_reward` sets the newest transition's reward and — for every simulator whose episode ended
 or whose memory holds LOCAL_TIME_MAX + 1 transitions — runs `_parse_memory` on the GPU
-(`ba3c_nstep_returns`), gathering the emitted datapoints' states and actions
+(`ba3c_nstep_returns`, or `ba3c_lambda_returns` for a GAE lambda below 1), gathering the emitted datapoints' states and actions
 (`ba3c_gather_rows`) before their ring slots are reused.  `BatchQueue` is BatchData(B) over the
 datapoint stream (dataflow/common.py:64-99) without the host queue of EnqueueThread
 (train/trainer.py:116-155).  `FrameHistory` is HistoryFramePlayer (RL/history.py:12-55) on
@@ -47,12 +47,19 @@ class Datapoints(object):
 
 
 class RolloutBuffer(object):
+    """gae_lambda = 1.0 (the reference's n-step returns) parses with `ba3c_nstep_returns`, as
+    before; any other lambda in [0, 1] with `ba3c_lambda_returns` (ba3c_amd.returns states the
+    recursion)."""
+
     def __init__(self, n_envs, channels=4, local_time_max=LOCAL_TIME_MAX, gamma=GAMMA,
-                 device="cuda"):
+                 gae_lambda=1.0, device="cuda"):
         self.lib = _lib.load()
         self.E, self.T = int(n_envs), int(local_time_max) + 1
         self.C = int(channels)
         self.gamma = float(gamma)
+        self.gae_lambda = float(gae_lambda)
+        if not 0.0 <= self.gae_lambda <= 1.0:
+            raise ValueError("gae_lambda must be in [0, 1], got %r" % (gae_lambda,))
         dev = torch.device(device)
         self.device = dev
         E, T = self.E, self.T
@@ -94,10 +101,15 @@ class RolloutBuffer(object):
         ready = over | (self.length == self.T)
         plen = torch.where(ready, self.length, torch.zeros_like(self.length))
         over_u8 = over.to(torch.uint8)
-        _lib.check(self.lib.ba3c_nstep_returns(
-            _stream(), _ptr(self.rewards), _ptr(self.values), _ptr(self.start), _ptr(plen),
-            _ptr(over_u8), self.E, self.T, ctypes.c_double(self.gamma), _ptr(self._R),
-            _ptr(self._src), _ptr(self._init), _ptr(self._over), _ptr(self._count)))
+        rings = (_stream(), _ptr(self.rewards), _ptr(self.values), _ptr(self.start), _ptr(plen),
+                 _ptr(over_u8), self.E, self.T, ctypes.c_double(self.gamma))
+        outs = (_ptr(self._R), _ptr(self._src), _ptr(self._init), _ptr(self._over),
+                _ptr(self._count))
+        if self.gae_lambda == 1.0:
+            _lib.check(self.lib.ba3c_nstep_returns(*(rings + outs)))
+        else:
+            _lib.check(self.lib.ba3c_lambda_returns(
+                *(rings + (ctypes.c_double(self.gae_lambda),) + outs)))
         n = int(self._count.item())
         out = self._gather(n)
         # memory left behind: [last] when not over, [] when over

@@ -34,6 +34,8 @@ from collections import defaultdict
 import msgpack
 import numpy as np
 
+from .returns import lambda_step
+
 GAMMA = 0.99              # train.py:94
 LOCAL_TIME_MAX = 5        # train.py:102
 
@@ -310,7 +312,7 @@ class SimulatorMaster(threading.Thread):
             self.memory = []
 
     def __init__(self, pipe_c2s, pipe_s2c, simulator_procs, local_time_max=LOCAL_TIME_MAX,
-                 gamma=GAMMA):
+                 gamma=GAMMA, gae_lambda=1.0):
         super(SimulatorMaster, self).__init__()
         self.daemon = True
         self.c2s_socket = PullSocket(pipe_c2s)
@@ -319,6 +321,7 @@ class SimulatorMaster(threading.Thread):
         self.killed_threads = 0
         self.local_time_max = local_time_max
         self.gamma = gamma
+        self.gae_lambda = gae_lambda
         self.clients = defaultdict(self.ClientState)
         self.queue = []
         self.is_done = False
@@ -387,8 +390,10 @@ class SimulatorMaster(threading.Thread):
             self.queue.append(dp)
 
     def _parse_memory(self, init_r, ident, is_over, ts):
-        """train.py:418-437: n-step returns over the reversed memory, R = clip(r, -1, 1) +
-        GAMMA * R, bootstrapped from init_r."""
+        """train.py:418-437 over the reversed memory, bootstrapped from init_r, with the
+        lambda-return statement of ba3c_amd.returns: R = clip(r, -1, 1) + GAMMA * ((1 - lambda) *
+        V_next + lambda * R); at gae_lambda = 1 that is the reference's R = clip(r, -1, 1) +
+        GAMMA * R exactly."""
         client = self.clients[ident]
         mem = client.memory
         last = None
@@ -396,9 +401,10 @@ class SimulatorMaster(threading.Thread):
             last = mem[-1]
             mem = mem[:-1]
         mem = mem[::-1]
-        R = float(init_r)
+        R = v_next = float(init_r)
         for k in mem:
-            R = np.clip(k.reward, -1, 1) + self.gamma * R
+            R = lambda_step(k.reward, v_next, R, self.gamma, self.gae_lambda)
+            v_next = float(k.value)
             self._put([k.state, k.action, R, getattr(k, "ts", ts), init_r, is_over])
         client.memory = [last] if not is_over else []
 

@@ -8,7 +8,8 @@ predictor + BatchData, :520-534 — with the synthetic on-device environment, gy
 absent, or with `-e GridBreakout-v0` / `-e GridBoxing-v0` the on-device Breakout / Boxing of
 flags.GAMES (`--frame_skip` / `--sticky`: ALE's frame skip and sticky actions, for training and
 evaluation alike; `--self_play`: two-player GridBoxing, ba3c_amd.duel, every game's two sides
-both played by the learner) and, for `--nr_eval N`, the Evaluator callback every --steps_per_epoch steps), plus
+both played by the learner; `--local_time_max` / `--gamma` / `--gae_lambda`: the rollout length,
+discount and GAE lambda of the returns, ba3c_amd.returns) and, for `--nr_eval N`, the Evaluator callback every --steps_per_epoch steps), plus
 the DebugLogCallback metrics channels and PeriodicPerStepCallback(ModelSaver) (:608-630) and
 `--load` (SaverRestore, :706-707).
 
@@ -195,7 +196,9 @@ def _run(args, rank, world):
                                              frame_skip=args.frame_skip, sticky=args.sticky)
         al = ActorLearner(trainer, n_envs=args.simulator_procs, batch_size=args.batch_size,
                           seed=rank, rs=np.random.RandomState(rank), on_train_step=on_step,
-                          dummy_predictor=bool(args.dummy_predictor), env=env)
+                          dummy_predictor=bool(args.dummy_predictor), env=env,
+                          local_time_max=args.local_time_max, gamma=args.gamma,
+                          gae_lambda=args.gae_lambda)
         while trainer.global_step < max_steps:
             al.iterate()
         sim_steps = al.steps

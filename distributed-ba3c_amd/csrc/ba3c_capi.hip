@@ -1967,6 +1967,26 @@ int ba3c_nstep_returns(void* stream, const double* reward, const float* value,
   return BA3C_OK;
 }
 
+int ba3c_lambda_returns(void* stream, const double* reward, const float* value,
+                        const int32_t* start, const int32_t* length, const uint8_t* is_over,
+                        int32_t n_envs, int32_t slots, double gamma, double lambda, float* R,
+                        int32_t* src, float* init_R, uint8_t* over, int32_t* count) {
+  if (!reward || !value || !start || !length || !is_over || !R || !src || !init_R || !over || !count)
+    return fail(BA3C_ERR_INVALID, "null pointer");
+  if (n_envs < 0 || slots < 1 || slots > kLambdaMaxSlots ||
+      (int64_t)n_envs * slots > INT32_MAX)
+    return fail(BA3C_ERR_INVALID, "bad shape (slots must be 1..129)");
+  // written so that a NaN fails either test
+  if (!(lambda >= 0.0 && lambda <= 1.0)) return fail(BA3C_ERR_INVALID, "lambda must be in [0, 1]");
+  if (!(gamma > 0.0 && gamma <= 1.0)) return fail(BA3C_ERR_INVALID, "gamma must be in (0, 1]");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  ReturnsArgs a{reward, value, start, length, is_over, n_envs, slots, gamma, R, src, init_R, over, count};
+  const int groups = std::max(1, (n_envs + kLambdaEnvs - 1) / kLambdaEnvs);   // n_envs == 0: *count = 0
+  hipLaunchKernelGGL(lambda_returns_kernel, dim3(groups), dim3(256), 0, s, a, lambda);
+  HIP_TRY(hipGetLastError());
+  return BA3C_OK;
+}
+
 int ba3c_gather_rows(void* stream, const void* rows, const int32_t* idx, int32_t n,
                      int64_t row_bytes, void* out) {
   if (n < 0) return fail(BA3C_ERR_INVALID, "bad count");
@@ -1974,12 +1994,13 @@ int ba3c_gather_rows(void* stream, const void* rows, const int32_t* idx, int32_t
   if (!rows || !idx || !out) return fail(BA3C_ERR_INVALID, "null pointer");
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (row_bytes == 8) {
-    hipLaunchKernelGGL(gather_i64_kernel, dim3((n + 255) / 256), dim3(256), 0, s,
+    hipLaunchKernelGGL(gather_i64_kernel, dim3((unsigned)(((int64_t)n + 255) / 256)), dim3(256), 0, s,
                        static_cast<const int64_t*>(rows), idx, n, static_cast<int64_t*>(out));
   } else if (row_bytes > 0 && row_bytes % 16 == 0 && check_ptr(rows) && check_ptr(out)) {
     const int words = (int)(row_bytes / 16);
     const int gx = std::min(8, (words + 255) / 256);
-    hipLaunchKernelGGL(gather_rows16_kernel, dim3(gx, n), dim3(256), 0, s,
+    // gridDim.y is limited to 65535: the kernel folds the row index over it
+    hipLaunchKernelGGL(gather_rows16_kernel, dim3(gx, std::min(n, 65535)), dim3(256), 0, s,
                        static_cast<const uint4*>(rows), idx, n, words, static_cast<uint4*>(out));
   } else {
     return fail(BA3C_ERR_INVALID, "row_bytes must be 8 or a multiple of 16 (16-byte aligned rows)");

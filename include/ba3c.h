@@ -304,9 +304,26 @@ int ba3c_nstep_returns(void* stream, const double* reward, const float* value,
                        int32_t n_envs, int32_t slots, double gamma, float* R, int32_t* src,
                        float* init_R, uint8_t* over, int32_t* count);
 
+/* lambda-returns over the same memories: ring layout, outputs, emission order and the
+ * over / not-over rule are those of ba3c_nstep_returns; only the recursion differs.  Per
+ * simulator, in reverse time order over the emitted transitions, in float64:
+ *   R = clip(r,-1,1) + gamma * ((1 - lambda) * Vnext + lambda * R)
+ * where R and Vnext start at the bootstrap (the newest transition's value when not over, 0
+ * when over) and Vnext then is the value of the transition emitted before (the next one in
+ * time).  Every product and sum rounds once (no fused multiply-add), R is stored as float32.
+ * R - value is the GAE(lambda) advantage sum_k (gamma*lambda)^k delta_{t+k}; lambda = 1 is the
+ * recursion of ba3c_nstep_returns exactly, lambda = 0 is clip(r) + gamma * Vnext.
+ * 1 <= slots <= 129; lambda in [0, 1] and gamma in (0, 1] (NaN is rejected), checked with the
+ * pointers before any GPU call.  One workgroup per 32 simulators, none waiting for another:
+ * each sums the emitted counts before it for its output offset. */
+int ba3c_lambda_returns(void* stream, const double* reward, const float* value,
+                        const int32_t* start, const int32_t* length, const uint8_t* is_over,
+                        int32_t n_envs, int32_t slots, double gamma, double lambda, float* R,
+                        int32_t* src, float* init_R, uint8_t* over, int32_t* count);
+
 /* BatchData / EnqueueThread hand-off (dataflow/common.py:64-99, train/trainer.py:116-155):
- * out[i] = rows[idx[i]] for n rows of row_bytes (a multiple of 16, e.g. 84*84*C states, or
- * exactly 8: int64 actions). */
+ * out[i] = rows[idx[i]] for n rows (any 0 <= n <= INT32_MAX) of row_bytes (a multiple of 16,
+ * e.g. 84*84*C states, or exactly 8: int64 actions). */
 int ba3c_gather_rows(void* stream, const void* rows, const int32_t* idx, int32_t n,
                      int64_t row_bytes, void* out);
 

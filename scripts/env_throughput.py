@@ -14,10 +14,16 @@ the fused step in the same run, and its store rate (Hc*S * 252*S bytes per simul
 With --duel also two-player GridBoxing (`BoxingDuelVec.step_into`, ba3c_amd.duel) at G = E / 2
 games next to `BoxingVec.step_into` at E simulators (by default G = 4096 against E = 8192 and
 G = 32 against E = 64: the same players and bytes), timed alternately in the same run.
+With --returns also `ba3c_lambda_returns` (lambda = 0.95 and 1) next to `ba3c_nstep_returns` on
+identical full memories at (simulators, slots) = (100, 6), (1024, 33), (4096, 129), the median
+of 20 event-bracketed batches of 20 launches each, alternating; and ms per
+`ActorLearner.iterate` on GridBoxing at 100 simulators with the default returns and with
+20-step GAE(0.95) returns.
 Prints one JSON line.
 
     python scripts/env_throughput.py [--game boxing] [--envs 8192 64] [--iters 200] [--random 20]
                                      [--frame_skip 2-4] [--sticky 0.25] [--view 1 3] [--duel]
+                                     [--returns]
 """
 import argparse
 import json
@@ -74,8 +80,107 @@ def duel_table(envs, iters, repeats):
     return out
 
 
+def timed_median(fn, batches=20, per=20, warmup=20):
+    """Median over `batches` of the mean µs per call of `per` back-to-back calls between two
+    device events (events around batches, not single launches: DESIGN.md §5's event gap)."""
+    for _ in range(warmup):
+        fn()
+    out = []
+    for _ in range(batches):
+        out.append(timed(fn, per, warmup=0))
+    return sorted(out)[len(out) // 2]
+
+
+RETURNS_SHAPES = [(100, 6), (1024, 33), (4096, 129)]
+
+
+def returns_table(repeats):
+    """--returns: `ba3c_lambda_returns` at lambda = 0.95 and lambda = 1 next to
+    `ba3c_nstep_returns` on identical full memories (every simulator holds `slots` transitions,
+    one in three over), alternating; the lambda = 1 outputs are compared with the n-step ones."""
+    import ctypes
+
+    from ba3c_amd import _lib
+    lib = _lib.load()
+    P = lambda t: ctypes.c_void_p(t.data_ptr())
+    out = {}
+    for E, T in RETURNS_SHAPES:
+        g = torch.Generator(device="cuda").manual_seed(E)
+        reward = torch.randint(-2, 3, (E, T), generator=g, device="cuda").to(torch.float64)
+        value = torch.randn(E, T, generator=g, device="cuda") * 3
+        start = torch.randint(0, T, (E,), generator=g, device="cuda").to(torch.int32)
+        length = torch.full((E,), T, dtype=torch.int32, device="cuda")
+        over = (torch.arange(E, device="cuda") % 3 == 0).to(torch.uint8)
+        outs = {}
+
+        def leg(name, lam=None):
+            """Buffers and arguments built once: the timed call is the entry point alone."""
+            o = outs[(name, lam)] = [
+                torch.zeros(E * T, dtype=torch.float32, device="cuda"),
+                torch.zeros(E * T, dtype=torch.int32, device="cuda"),
+                torch.zeros(E * T, dtype=torch.float32, device="cuda"),
+                torch.zeros(E * T, dtype=torch.uint8, device="cuda"),
+                torch.zeros(1, dtype=torch.int32, device="cuda")]
+            a = [ctypes.c_void_p(torch.cuda.current_stream().cuda_stream), P(reward), P(value),
+                 P(start), P(length), P(over), E, T, ctypes.c_double(0.99)]
+            a += [] if lam is None else [ctypes.c_double(lam)]
+            a += [P(t) for t in o]
+            fn = getattr(lib, name)
+            return lambda: fn(*a)
+        legs = {"nstep_us": leg("ba3c_nstep_returns"),
+                "lambda_0.95_us": leg("ba3c_lambda_returns", 0.95),
+                "lambda_1_us": leg("ba3c_lambda_returns", 1.0)}
+        for fn in legs.values():
+            _lib.check(fn())
+        t = {k: [] for k in legs}
+        for _ in range(repeats):
+            for k, fn in legs.items():
+                t[k].append(timed_median(fn))
+        same = all(torch.equal(a, b) for a, b in zip(outs[("ba3c_nstep_returns", None)],
+                                                     outs[("ba3c_lambda_returns", 1.0)]))
+        row = {k: [round(v, 2) for v in vs] for k, vs in t.items()}
+        row["datapoints"] = int(outs[("ba3c_nstep_returns", None)][4].item())
+        row["lambda_1_equals_nstep"] = bool(same)
+        for k in ("lambda_0.95_us", "lambda_1_us"):
+            row[k.replace("_us", "_over_nstep")] = round(min(t[k]) / min(t["nstep_us"]), 3)
+        out["%dx%d" % (E, T)] = row
+    return out
+
+
+def iterate_table(settings, iters=420, warmup=42, E=100):
+    """--returns: ms per ActorLearner.iterate on GridBoxing at E simulators (README flags: B = 32,
+    F = 128, S = 4, Adam) per (local_time_max, gae_lambda) setting: a host clock around `iters`
+    iterations ending in a device synchronise (420 = a multiple of both rollout periods)."""
+    import time
+
+    from ba3c_amd.actor_learner import ActorLearner
+    from ba3c_amd.boxing import BoxingVec
+    from ba3c_amd.model import Model
+    from ba3c_amd.optimizer import AdamOptimizer
+    from ba3c_amd.trainer import Ba3cTrainer, TrainConfig
+    out = {}
+    for ltm, lam in settings:
+        m = Model(num_actions=18, fc_neurons=128, fc_splits=4, batch_size=32, max_batch=max(32, E), seed=0)
+        tr = Ba3cTrainer(TrainConfig(model=m, optimizer=AdamOptimizer(1e-3, 0.8, 0.75, 1e-8)))
+        al = ActorLearner(tr, n_envs=E, batch_size=32, seed=0, env=BoxingVec(E, seed=0),
+                          local_time_max=ltm, gae_lambda=lam)
+        al.run(warmup)
+        torch.cuda.synchronize()
+        steps0, t0 = al.train_steps, time.time()
+        al.run(iters)
+        torch.cuda.synchronize()
+        dt = time.time() - t0
+        out.setdefault("local_time_max=%d,gae_lambda=%g" % (ltm, lam), []).append({
+            "ms_per_iterate": round(dt * 1e3 / iters, 3), "iterations": iters,
+            "train_steps": al.train_steps - steps0})
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--returns", action="store_true",
+                    help="also time ba3c_lambda_returns next to ba3c_nstep_returns, and one "
+                         "ActorLearner iteration with 5-step n-step and 20-step GAE(0.95) returns")
     ap.add_argument("--duel", action="store_true",
                     help="also time two-player GridBoxing at G = E / 2 games against BoxingVec at E")
     ap.add_argument("--envs", type=int, nargs="+", default=[8192, 64])
@@ -177,6 +282,9 @@ def main(argv=None):
             out["envs"][str(E)]["fused_over_breakout"] = round(min(fused) / min(brk), 3)
     if args.duel:
         out["duel"] = duel_table(args.envs, args.iters, args.repeats)
+    if args.returns:
+        out["returns"] = returns_table(args.repeats)
+        out["iterate"] = iterate_table([(5, 1.0), (20, 0.95), (5, 1.0), (20, 0.95)])
     if args.random:
         from ba3c_amd.evaluate import eval_with_envs, uniform_policy
         from ba3c_amd.model import Model
