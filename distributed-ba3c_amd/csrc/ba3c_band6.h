@@ -97,24 +97,7 @@ struct Band6Args {
   const uint32_t* amax_in;
   const int* wexp;
   uint32_t* amax_out;
-  // ring walks only (conv_band6r_kernel): non-null = a dynamic image queue (one ticket word,
-  // zeroed by the step's weight-prep launch); null = static contiguous image ranges
-  unsigned* ticket;
 };
-
-// Dynamic image queue of the ring walks (BA3C_DYNQ, default on where a workgroup walks several
-// images): workgroup b starts with image b; thread 0 draws each further image (gx + ticket) with
-// one agent-scope atomic when the workgroup STARTS an image and parks it in an LDS slot one
-// band later, so the round trip hides behind the band's work; the workgroup reads it at the
-// image's end.  Every image's outputs depend only on
-// the image, so the results equal the static partition's bit for bit; what changes is that a
-// workgroup held off the chip (a collective's workgroups on its CU) no longer leaves its images
-// for the end of the launch.
-// (an increment, not an add: the compiler's atomic optimizer rewrites a uniform-address add into
-// a wave-aggregated one whose result is read back at once, a full vmcnt wait right at the draw)
-__device__ __forceinline__ unsigned draw_ticket(unsigned* t) {
-  return __builtin_amdgcn_atomic_inc32(t, 0xFFFFFFFFu, __ATOMIC_RELAXED, "agent");
-}
 
 // packed 16-bit halves: 0xFFFF where the half is zero, else 0 (code-mask of the pooled staging)
 __device__ __forceinline__ uint32_t mask16_eq0(uint32_t d) {
@@ -506,21 +489,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) c
 // the one-band kernel's, so the outputs are bit-identical.  (Round 2 ran the copy and the new-row
 // stores with no barrier in between: a cross-wave write-after-read race in LDS; fixed in r03.)
 template <class L, bool PRE_ = L::G::SRC == 1>
-__device__ __forceinline__ void band6r_body(const Band6Args& a, int bx, int gx, char* lds, int* tslot) {
+__device__ __forceinline__ void band6r_body(const Band6Args& a, int bx, int gx, char* lds) {
   static_assert(L::NPH == 1 && L::G::SROWS > L::G::RB, "ring walk: unphased layouts with a halo");
-  static_assert(L::G::NBANDS >= 3, "dynamic queue: the ticket is parked at band 1 and read after the last");
   using O = Band6Ops<L>;
   using G = typename L::G;
   constexpr int HALO = G::SROWS - G::RB;                    // KH - 1 rows carried over
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float us2 = L::NS == 2 ? exp2i(-a.wexp[0]) : 1.0f;
-  const bool dyn = a.ticket != nullptr;
   const int ipw = (a.batch + gx - 1) / gx;
-  int img0 = bx * ipw, img1 = min(a.batch, img0 + ipw);
-  if (dyn) {                  // first image bx (no draw: gx simultaneous same-address draws at
-    img0 = bx;                // the start serialise), then images gx + ticket
-    img1 = a.batch;
-  }
+  const int img0 = bx * ipw, img1 = min(a.batch, img0 + ipw);
   // PRE (input-gradient layouts, whose registers allow it): the next band's RB new rows are
   // loaded into registers before this band's MFMAs, so their global latency hides behind them
   constexpr bool PRE = PRE_;
@@ -529,22 +506,14 @@ __device__ __forceinline__ void band6r_body(const Band6Args& a, int bx, int gx, 
   float4 pv[PRE ? NNEW : 1];
   uint32_t pc[PRE ? NNEW : 1];
   unsigned long long pos = 0;
-  for (int img = img0; img < img1;) {
+  for (int img = img0; img < img1; ++img) {
     const int ka = L::NS == 2 ? amax_exp(a.amax_in[1 + img]) : 0;   // per-image operand scale
     const float asc = exp2i(ka), us1 = exp2i(-ka);
     float omax = 0.f;
-    unsigned nt = 0;
-    // the image after this one, drawn once the scale's load is consumed (the asm pins the
-    // order: a wait for that load at the branch join would otherwise also wait for the draw)
-    if (dyn) {
-      asm volatile("" ::"v"(asc) : "memory");
-      if (tid == 0) nt = draw_ticket(a.ticket);
-    }
     for (int bi = 0; bi < G::NBANDS; ++bi) {
       const int y0 = bi * G::RB;
       const int rows_out = min(G::RB, G::HO - y0);
       __syncthreads();                                      // previous band's LDS reads are done
-      if (dyn && tid == 0 && bi == 1) *tslot = (int)nt;     // (read after the image's last band)
       unsigned fbase = 0;
       if (bi > 0) {
         // carry the halo rows down: source rows RB .. SROWS-1 -> rows 0 .. HALO-1.  The new
@@ -585,7 +554,6 @@ __device__ __forceinline__ void band6r_body(const Band6Args& a, int bx, int gx, 
       O::compute(a, lds, wave, lane, img, y0, rows_out, us1, us2, pos, omax, [](int) {});
     }
     if (L::NS == 2) amax_publish(a.amax_out, img, omax, lane);
-    img = dyn ? gx + *tslot : img + 1;   // (written at band 1; bands >= 2 put barriers in between)
   }
   if (G::POOL && a.relu_count) relu_count_add_uniform(a.relu_count, pos, lane);
 }
@@ -600,7 +568,7 @@ __device__ __forceinline__ void band6r_body(const Band6Args& a, int bx, int gx, 
 // image is bit for bit the one store1 builds.
 
 template <class L>
-__device__ __forceinline__ void band6r_up_body(const Band6Args& a, int bx, int gx, char* lds, int* tslot) {
+__device__ __forceinline__ void band6r_up_body(const Band6Args& a, int bx, int gx, char* lds) {
   using O = Band6Ops<L>;
   using G = typename L::G;
   using SP = SplitP<L::NS>;
@@ -614,13 +582,8 @@ __device__ __forceinline__ void band6r_up_body(const Band6Args& a, int bx, int g
   constexpr int IT = (NPI + 255) / 256;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float us2 = exp2i(-a.wexp[0]);
-  const bool dyn = a.ticket != nullptr;
   const int ipw = (a.batch + gx - 1) / gx;
-  int img0 = bx * ipw, img1 = min(a.batch, img0 + ipw);
-  if (dyn) {                                                // first image bx, then gx + ticket
-    img0 = bx;
-    img1 = a.batch;
-  }
+  const int img0 = bx * ipw, img1 = min(a.batch, img0 + ipw);
 
   // pooled rows bi * RB / 2 .. of image img (new rows of band bi: un-pooled rows y0 .. y0 +
   // RB - 1 = staged rows HALO ..); rows past the map load as zero (value and code 0: the
@@ -673,20 +636,13 @@ __device__ __forceinline__ void band6r_up_body(const Band6Args& a, int bx, int g
   uint32_t pc[IT];
   if (img0 < img1) load_items(img0, 0, pv, pc);
   unsigned long long pos = 0;
-  for (int img = img0; img < img1;) {
+  for (int img = img0; img < img1; ++img) {
     const int ka = amax_exp(a.amax_in[1 + img]);            // per-image operand scale
     const float asc = exp2i(ka), us1 = exp2i(-ka);
     float omax = 0.f;
-    unsigned nt = 0;
-    if (dyn) {                                              // the image after this one (as above)
-      asm volatile("" ::"v"(asc) : "memory");
-      if (tid == 0) nt = draw_ticket(a.ticket);
-    }
-    int nimg = img + 1;
     for (int bi = 0; bi < G::NBANDS; ++bi) {
       const int y0 = bi * G::RB;
       __syncthreads();                                      // previous band's LDS reads are done
-      if (dyn && tid == 0 && bi == 1) *tslot = (int)nt;     // read after the store barrier below
       if (bi > 0) {
         // halo rows RB .. SROWS-1 -> 0 .. HALO-1; every wave's copy completes before any wave
         // stores new rows over the source rows
@@ -701,76 +657,25 @@ __device__ __forceinline__ void band6r_up_body(const Band6Args& a, int bx, int g
       }
       store_items(pv, pc, asc);
       __syncthreads();
-      if (dyn && bi == 1) nimg = gx + *tslot;
       {
         // prefetch the workgroup's next band (the next image's first band after the last)
         const int nb = bi + 1 < G::NBANDS ? bi + 1 : 0;
-        const int ni = bi + 1 < G::NBANDS ? img : nimg;
+        const int ni = bi + 1 < G::NBANDS ? img : img + 1;
         if (ni < img1) load_items(ni, nb, pv, pc);
       }
       O::compute(a, lds, wave, lane, img, y0, G::RB, us1, us2, pos, omax, [](int) {});
     }
     amax_publish(a.amax_out, img, omax, lane);
-    img = nimg;
   }
 }
 
 template <class L, bool PRE_ = L::G::SRC == 1>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) conv_band6r_kernel(const Band6Args a) {
   __shared__ uint4 lds4[L::LDS_BYTES / 16];
-  __shared__ int tslot[1];
   if constexpr (L::G::SRC == 1 && L::NS == 2)
-    band6r_up_body<L>(a, blockIdx.x, gridDim.x, reinterpret_cast<char*>(lds4), tslot);
+    band6r_up_body<L>(a, blockIdx.x, gridDim.x, reinterpret_cast<char*>(lds4));
   else
-    band6r_body<L, PRE_>(a, blockIdx.x, gridDim.x, reinterpret_cast<char*>(lds4), tslot);
-}
-
-// conv1's 2:4-sparse input gradient (ba3c_dgrad1s.h): geometry and the B operand of its
-// sparse logical K order, prepared by wprep job WJ_C1S
-struct D1S {
-  static constexpr int HO = 40, WO = 40, C = 32, O = 32, UP = 18;  // dX map / channels; pooled dY
-  static constexpr int RB = 4, NBANDS = HO / RB;                     // output rows per band
-  static constexpr int SR = RB + 4;                                  // staged dY rows
-  static constexpr int NW = 22;                                      // windows (w' = w + 2)
-  // PV: dword (window w', window w' + 1) per staged row, w' 0..20, channel; MV: the masked value
-  // of window w', w' 0..21, channel (single taps); the quad indices per POOLED row.  Pitches from
-  // a bank search over the A-read lane maps (conflict-free ds_read_b128)
-  static constexpr int PV_WS = 40, PV_RS = 864;
-  static constexpr int MV_WS = 16, MV_RS = 360;
-  static constexpr int PV_PLANE = SR * PV_RS, MV_PLANE = SR * MV_RS;  // dwords
-  static constexpr int IXF_RS = 21 * 8, IXS_RS = NW * 4;             // u16 per pooled row
-  static constexpr int MV_OFF = 2 * PV_PLANE * 4;                    // bytes
-  static constexpr int IXF_OFF = MV_OFF + 2 * MV_PLANE * 4;
-  static constexpr int IXS_OFF = IXF_OFF + (SR / 2) * IXF_RS * 2;
-  static constexpr int LDS_BYTES = IXS_OFF + (SR / 2) * IXS_RS * 2;
-  static constexpr int KSTEPS = 15;                                  // 5 tap rows x 3
-  static constexpr int WFRAG = 16;                                   // halves per lane and plane
-  static constexpr int WPLANE = 2 * KSTEPS * 2 * 64 * WFRAG;         // halves per plane (2 parities)
-  static constexpr int NITEM = (SR / 2) * NW * (O / 4);              // (pooled row, window, 4 ch)
-  static constexpr int IPT = (NITEM + 255) / 256;
-  static_assert(2 * LDS_BYTES <= 160 * 1024 && 21 * PV_WS <= PV_RS && NW * MV_WS <= MV_RS,
-                "d1s layout: two workgroups per CU");
-};
-
-// The weight of B element (parity eps, k-step s, column c, logical K) — the wprep job's value
-// (scripts/probes/sparse_dgrad_model.py bweight): W is conv1/W [5][5][C][O] (HWIO).
-__device__ __forceinline__ float d1s_weight(const float* __restrict__ w, int eps, int s, int c, int K) {
-  const int kh = s / 3, t = s - 3 * kh, q = K >> 2, p = K & 3;
-  if (t < 2) {                                     // aligned quad: channel 16 t + q, tap kw = p + eps
-    const int o = 16 * t + q, kw = p + eps;
-    return w[((size_t)((4 - kh) * 5 + (4 - kw)) * D1S::C + c) * D1S::O + o];
-  }
-  const int o = 2 * q + (p >> 1), cl = p & 1;      // single taps: channel pair, pixel column cl
-  if (eps == 0) return cl == 0 ? w[((size_t)((4 - kh) * 5 + 0) * D1S::C + c) * D1S::O + o] : 0.f;
-  return cl == 1 ? w[((size_t)((4 - kh) * 5 + 4) * D1S::C + c) * D1S::O + o] : 0.f;
-}
-// fragment element d of one plane: [eps][s][n-tile][lane][16]; B lane layout of the 16x16x64
-// sparse MFMA: column lane & 15, logical K 8 g + e (e < 8) / 32 + 8 g + e - 8 (g = lane >> 4)
-__device__ __forceinline__ float d1s_wprep_value(const float* __restrict__ w, int d) {
-  const int e = d & 15, lane = (d >> 4) & 63, nt = (d >> 10) & 1, rest = d >> 11;
-  const int s = rest % D1S::KSTEPS, eps = rest / D1S::KSTEPS, g = lane >> 4;
-  const int K = e < 8 ? 8 * g + e : 32 + 8 * g + (e - 8);
-  return d1s_weight(w, eps, s, 16 * nt + (lane & 15), K);
+    band6r_body<L, PRE_>(a, blockIdx.x, gridDim.x, reinterpret_cast<char*>(lds4));
 }
 
 // One launch per step for all weight preparation on the split path: job y < njobs writes the
@@ -782,7 +687,7 @@ __device__ __forceinline__ float d1s_wprep_value(const float* __restrict__ w, in
 struct WPrep6Args {
   WPrepArgs jobs;
   uint16_t* wt6;
-  int off[7];              // fp32 offset of job i; its splits start at NS * off[i]
+  int off[6];              // fp32 offset of job i; its splits start at NS * off[i]
   const float* w0;         // conv0/W (null: no conv0 job)
   uint4* wb0;
   unsigned long long* relu;  // training: ReLU-count slots zeroed here (no separate memset)
@@ -823,7 +728,7 @@ __device__ __forceinline__ void wprep6_body(const WPrep6Args& a, int bx, int by,
     auto amax4 = [](float m, const float4& v) {
       return fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
     };
-    const int n4 = (j.dgrad == 2 ? j.KH * j.KW * j.CI * j.CO : j.n) / 4;   // the source tensor
+    const int n4 = j.n / 4;
     float m0 = 0.f, m1 = 0.f, m2 = 0.f, m3 = 0.f;
     int i = threadIdx.x;
     for (; i + 768 < n4; i += 1024) {
@@ -844,15 +749,6 @@ __device__ __forceinline__ void wprep6_body(const WPrep6Args& a, int bx, int by,
     sc = exp2i(k);
   }
   uint16_t* dst = a.wt6 + 2 * (size_t)a.off[y];
-  if (j.dgrad == 2) {                  // conv1's sparse input-gradient fragments (ba3c_dgrad1s.h)
-    for (int d = bx * 256 + threadIdx.x; d < j.n; d += gx * 256) {
-      uint32_t hi, lo;
-      split2(d1s_wprep_value(j.w, d) * sc, hi, lo);
-      dst[d] = (uint16_t)hi;
-      dst[j.n + d] = (uint16_t)lo;
-    }
-    return;
-  }
   // destination d in the band kernels' MFMA B-fragment order [K / 32][N / 16][lane][8]: lane
   // (lq, li) holds column n = 16 nb + li, K = 32 k32 + 8 lq .. + 7 (Band6Ops::compute)
   const int K = j.KH * j.KW * (j.dgrad ? j.CO : j.CI);

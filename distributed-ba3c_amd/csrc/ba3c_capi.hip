@@ -23,7 +23,6 @@
 #include "ba3c_breakout.h"
 #include "ba3c_conv.h"
 #include "ba3c_conv3.h"
-#include "ba3c_dgrad1s.h"
 #include "ba3c_duel.h"
 #include "ba3c_envview.h"
 #include "ba3c_gemm6.h"
@@ -155,19 +154,6 @@ struct ba3c_handle {
   bool chain_on = true;
   unsigned* chain = nullptr;
   unsigned* spread = nullptr;   // CHAIN_SPREAD counters, CHAIN_STRIDE words apart (64-byte aligned)
-  // conv1's input gradient on 2:4-sparse MFMA (ba3c_dgrad1s.h) at the ring-walk batches
-  // (B >= 2 x CUs) with BA3C_C1D_SPARSE=1; default 0, the dense ring walk: the sparse kernel
-  // issues 40 % fewer matrix instructions but measured 0.40 against 0.33 ms (r05x-y: its L2
-  // weight-fragment stream and its staging, which two workgroups per CU do not hide, cost
-  // 0.07 and 0.13 ms)
-  bool c1s = false;
-  // BA3C_DYNQ=1: ring walks with several images per workgroup draw their images after the
-  // first from a dynamic queue (Band6Args::ticket) instead of static contiguous ranges;
-  // bit-identical either way.  Default 0: same-box r06g, the queue costs ~9 us per step with
-  // the chip to itself (conv1 fwd + dgrad), and with 16 CUs held for 50 us by a stand-in for
-  // RCCL (bench --occupy) conv1 dgrad's slowdown is the same 1.08 either way; it only pays when
-  // CUs are held for the whole launch (1.55 -> 1.14)
-  bool dynq = false;
   // BA3C_C3W_RIDE (large batches, conv2's gradients in one multi-job launch): conv3's weight
   // gradient as a third job of that launch instead of a launch of its own (two 256-thread
   // workgroups per slab, bit-identical slabs); 1: after conv2's jobs, 2: before them, 0: own
@@ -271,15 +257,13 @@ inline int conv3_wgrad_p(int B, int cus) { return std::min(B, std::min(C3W_P, cu
 constexpr int WG_P0S = 512;   // conv0s_wgrad_kernel: 52 KB LDS, two workgroups per CU
 constexpr int WT_C1F = 0, WT_C2F = WT_C1F + 800 * 32, WT_C3F = WT_C2F + 800 * 64,
               WT_C1D = WT_C3F + 576 * 64, WT_C2D = WT_C1D + 800 * 32, WT_C3D = WT_C2D + 1600 * 32,
-              WT_C1S = WT_C3D + 576 * 64, WT_C0F = WT_C1S + D1S::WPLANE,
+              WT_C0F = WT_C3D + 576 * 64,
               WT_C0S = WT_C0F + 32 * Conv0Geom::KDIM,            // uint4 [Conv0S::WB_U4]
               WT_TOTAL = WT_C0S + 4 * Conv0S::WB_U4;
+static_assert(WT_C0S % 4 == 0, "conv0's fragments are read as uint4: a 16-byte aligned offset");
 
 // max-|x| slot arrays (ba3c_split.h, fp16 family)
 enum { AM_P0 = 0, AM_P1 = 1, AM_DP0 = 2, AM_DP1 = 3, AM_DP2 = 4, AM_P2 = 5, AM_DY3 = 6, AMAX_N = 7 };
-// dynamic image-queue tickets of the ring walks (Band6Args::ticket), right after the max slots
-// so the step's weight-prep launch zeroes them with those
-enum { TK_C1F = 0, TK_C1D = 1, TK_N = 4 };
 struct Workspace {
   float *p0, *p1, *p2, *a3, *h, *fcpart, *dh, *dy3, *dp2, *dp1, *dp0, *dzv, *terms, *part0, *sumsq, *wt;
   // split-K / per-workgroup partial slabs of each weight gradient (reduced in one launch at the
@@ -292,11 +276,10 @@ struct Workspace {
   int* wexp;       // [8]: weight scale exponents (wprep jobs WJ_*, conv0 = WX_CONV0)
   size_t bytes;
   uint32_t* am(int t, const ba3c_handle* h) const { return amax + (size_t)t * (1 + h->cfg.max_batch); }
-  unsigned* ticket(int k, const ba3c_handle* h) const { return amax + (size_t)AMAX_N * (1 + h->cfg.max_batch) + k; }
 };
 // weight-preparation jobs (forward copies first: inference prepares only those) and the
 // index of each one's scale exponent in Workspace::wexp
-enum { WJ_C1F = 0, WJ_C2F = 1, WJ_C3F = 2, WJ_C1D = 3, WJ_C2D = 4, WJ_C3D = 5, WJ_C1S = 6, WJ_N = 7, WJ_FWD = 3,
+enum { WJ_C1F = 0, WJ_C2F = 1, WJ_C3F = 2, WJ_C1D = 3, WJ_C2D = 4, WJ_C3D = 5, WJ_N = 6, WJ_FWD = 3,
        WX_CONV0 = 7 };
 
 struct WgradPlan {
@@ -395,7 +378,7 @@ Workspace carve(const ba3c_handle* h, void* base, int B, bool train) {
   // The clip / optimizer per-chunk sum-of-squares partials come FIRST, at a batch-independent
   // offset: ba3c_clip_grads / ba3c_apply_update receive only the workspace base.
   w.sumsq = (float*)take((size_t)h->table.nchunks * 4);
-  w.amax = (uint32_t*)take(((size_t)AMAX_N * (1 + h->cfg.max_batch) + TK_N) * 4);
+  w.amax = (uint32_t*)take((size_t)AMAX_N * (1 + h->cfg.max_batch) * 4);
   w.wexp = (int*)take(8 * 4);
   w.p0 = (float*)take(Bz * P0 * 4);
   w.p1 = (float*)take(Bz * P1 * 4);
@@ -591,10 +574,7 @@ int launch_band6(ba3c_handle* h, hipStream_t s, int kid, const BandArgs& a, cons
       if (ringable && h->ring && a.batch >= pr && (a.batch % pr == 0 || a.batch >= 8 * pr)) {
         // (the forward keeps its double-buffered A fragments and no row prefetch: the
         // no-DBUF layout with the prefetch measured 0.36 -> 0.41 ms, r02ai)
-        Band6Args br = b;
-        if (h->dynq && a.batch > pr)    // several images per workgroup
-          br.ticket = w.ticket(kid == BA3C_K_CONV1_DGRAD ? TK_C1D : TK_C1F, h);
-        hipLaunchKernelGGL(conv_band6r_kernel<L>, dim3(2 * h->cus), dim3(256), 0, s, br);
+        hipLaunchKernelGGL(conv_band6r_kernel<L>, dim3(2 * h->cus), dim3(256), 0, s, b);
         HIP_TRY(hipGetLastError());
         return BA3C_OK;
       }
@@ -636,10 +616,7 @@ int reduce_wgrad6(ba3c_handle* h, hipStream_t s, const Wg6Args& a, int P, float*
 
 // Split-path weight preparation arguments (wprep6_kernel): every job, the conv0 fragments and
 // the zeroing of the ReLU counters / max slots.
-// conv1's sparse input gradient at this batch (the ring-walk batches)
-bool use_c1s(const ba3c_handle* h, int B) { return h->c1s && h->band && h->ring && B >= 2 * h->cus; }
-
-WPrep6Args wprep6_args(ba3c_handle* h, const float* prm, const Workspace& w, bool train, bool c1s = false) {
+WPrep6Args wprep6_args(ba3c_handle* h, const float* prm, const Workspace& w, bool train) {
   const float* W1 = prm + h->tensors[h->idx_conv[1]].offset;
   const float* W2 = prm + h->tensors[h->idx_conv[2]].offset;
   const float* W3 = prm + h->tensors[h->idx_conv[3]].offset;
@@ -651,16 +628,15 @@ WPrep6Args wprep6_args(ba3c_handle* h, const float* prm, const Workspace& w, boo
   a.job[WJ_C1D] = WPrepJob{W1, w.wt + WT_C1D, 5, 5, 32, 32, 1, 800 * 32};
   a.job[WJ_C2D] = WPrepJob{W2, w.wt + WT_C2D, 5, 5, 32, 64, 1, 1600 * 32};
   a.job[WJ_C3D] = WPrepJob{W3, w.wt + WT_C3D, 3, 3, 64, 64, 1, 576 * 64};
-  a.job[WJ_C1S] = WPrepJob{W1, w.wt + WT_C1S, 5, 5, 32, 32, 2, D1S::WPLANE};
-  a.njobs = train ? (c1s ? WJ_N : WJ_C1S) : WJ_FWD;
+  a.njobs = train ? WJ_N : WJ_FWD;
   pa.wt6 = w.wt6;
-  const int offs[WJ_N] = {WT_C1F, WT_C2F, WT_C3F, WT_C1D, WT_C2D, WT_C3D, WT_C1S};
+  const int offs[WJ_N] = {WT_C1F, WT_C2F, WT_C3F, WT_C1D, WT_C2D, WT_C3D};
   for (int j = 0; j < WJ_N; ++j) pa.off[j] = offs[j];
   pa.w0 = prm + h->tensors[h->idx_conv[0]].offset;
   pa.wb0 = reinterpret_cast<uint4*>(w.wt + WT_C0S);
   pa.relu = train ? w.relu : nullptr;
   pa.amax = w.amax;
-  pa.n_amax = AMAX_N * (1 + h->cfg.max_batch) + TK_N;   // the tickets too
+  pa.n_amax = AMAX_N * (1 + h->cfg.max_batch);
   pa.wexp = w.wexp;
   return pa;
 }
@@ -706,8 +682,8 @@ int launch_prep_conv0_multi(ba3c_handle* h, hipStream_t s, const float* prm, con
 
 // split planes of the band-conv weights for this step (forward; + rotated dgrad in training)
 // and, for C == 4, conv0's MFMA B fragments: one launch
-int launch_wprep(ba3c_handle* h, hipStream_t s, const float* prm, const Workspace& w, bool train, int B) {
-  WPrep6Args pa = wprep6_args(h, prm, w, train, use_c1s(h, B));
+int launch_wprep(ba3c_handle* h, hipStream_t s, const float* prm, const Workspace& w, bool train) {
+  WPrep6Args pa = wprep6_args(h, prm, w, train);
   const bool c0s = h->cfg.channels == 4;
   if (!c0s) pa.w0 = nullptr;
   hipLaunchKernelGGL(wprep6_kernel, dim3(64, pa.jobs.njobs + (c0s ? 1 : 0)), dim3(256), 0, s, pa);
@@ -776,7 +752,7 @@ int run_forward(ba3c_handle* h, hipStream_t s, const float* prm, const uint8_t* 
     if (mj) {
       CHECK(launch_prep_conv0_multi(h, s, prm, state, B, w, train));
     } else {
-      CHECK(launch_wprep(h, s, prm, w, train, B));
+      CHECK(launch_wprep(h, s, prm, w, train));
       if constexpr (CH == 4) {
         CHECK(launch_conv0_band(h, s, BandArgs{reinterpret_cast<const float*>(state), nullptr, nullptr, w.p0, c0,
                                                rc, B}, w));
@@ -856,7 +832,6 @@ int run_backward(ba3c_handle* h, hipStream_t s, const float* prm, const uint8_t*
   const float* W2c = prm + h->tensors[h->idx_conv[2]].offset;
   const float* W3c = prm + h->tensors[h->idx_conv[3]].offset;
   const float* Wfc = prm + h->tensors[h->idx_fc1].offset;
-  bool defer_w1 = false;   // conv1's weight gradient waits for conv0's (one paired launch)
   // The weight-gradient kernels (heads, fc1, conv3..conv1) run on the side stream `ws`,
   // each after the event that publishes its output gradient; the input-gradient chain and
   // conv0's weight gradient (own partials region) stay on `s`, which joins `ws` at the end.
@@ -1049,129 +1024,111 @@ int run_backward(ba3c_handle* h, hipStream_t s, const float* prm, const uint8_t*
   }
   if (phase == 2 && h->ev_mid) HIP_TRY(hipEventRecord(h->ev_mid, s));
   // conv2
-  if (mj) {
+  {
+    using W2 = typename LY::W2;
     const Wg6Args wa{w.p1, w.dp2, w.c2, w.part_2, B, w.am(AM_P1, h), w.am(AM_DP2, h)};
-    const dim3 wg = wgrad6_grid<typename LY::W2>(W6_P2, B);
-    const Band6Args da = band6_args<typename LY::C2DS>(h, BandArgs{w.dp2, w.c2, w.wt + WT_C2D, w.dp1, nullptr, nullptr, B},
-                                                      w, WT_C2D, SplitIO{AM_DP2, WJ_C2D, AM_DP1});
-    CHECK((launch_multi<true, Band6Job<typename LY::C2DS>, Wg6Job<typename LY::W2>>(
-        s, da, dim3(B * LY::C2DS::G::NBANDS), wa, wg)));
-    h->merged[BA3C_K_CONV2_DGRAD] |= 1u << BA3C_K_CONV2_WGRAD;
-    CHECK(reduce_wgrad6<typename LY::W2>(h, s, wa, (int)wg.x, grads + h->tensors[h->idx_conv[2]].offset));
-  } else if (mj_c2) {
-    const Wg6Args wa{w.p1, w.dp2, w.c2, w.part_2, B, w.am(AM_P1, h), w.am(AM_DP2, h)};
-    const dim3 wg = wgrad6_grid<typename LY::W2>(W6_P2, B);
-    const Band6Args da = band6_args<typename LY::C2D>(h, BandArgs{w.dp2, w.c2, w.wt + WT_C2D, w.dp1, nullptr, nullptr, B},
-                                                     w, WT_C2D, SplitIO{AM_DP2, WJ_C2D, AM_DP1});
-    const dim3 gd(B * LY::C2D::G::NBANDS), g3(c3w_gx, 2);
-    if (c3w_gx && h->c3ride == 2)
-      CHECK((launch_multi<true, Conv3WJob, Band6Job<typename LY::C2D>, Wg6Job<typename LY::W2>>(
-          s, c3w, g3, da, gd, wa, wg, h, BA3C_K_CONV2_DGRAD)));
-    else if (c3w_gx)
-      CHECK((launch_multi<true, Band6Job<typename LY::C2D>, Wg6Job<typename LY::W2>, Conv3WJob>(
-          s, da, gd, wa, wg, c3w, g3, h, BA3C_K_CONV2_DGRAD)));
-    else
-      CHECK((launch_multi<true, Band6Job<typename LY::C2D>, Wg6Job<typename LY::W2>>(
-          s, da, gd, wa, wg, 0, dim3(0, 1, 1), h, BA3C_K_CONV2_DGRAD)));
-    h->merged[BA3C_K_CONV2_DGRAD] |= 1u << BA3C_K_CONV2_WGRAD;
-    if (c3w_gx) h->merged[BA3C_K_CONV2_DGRAD] |= 1u << BA3C_K_CONV3_WGRAD;
-    CHECK(reduce_wgrad6<typename LY::W2>(h, s, wa, (int)wg.x, grads + h->tensors[h->idx_conv[2]].offset));
-  } else {
-    if (h->band) {
-      CHECK(launch_wgrad6<typename LY::W2>(h, ws, BA3C_K_CONV2_WGRAD,
-                                          Wg6Args{w.p1, w.dp2, w.c2, w.part_2, B, w.am(AM_P1, h), w.am(AM_DP2, h)},
-                                          W6_P2, grads + h->tensors[h->idx_conv[2]].offset));
+    const BandArgs ba{w.dp2, w.c2, w.wt + WT_C2D, w.dp1, nullptr, nullptr, B};
+    const SplitIO io{AM_DP2, WJ_C2D, AM_DP1};
+    float* dW2 = grads + h->tensors[h->idx_conv[2]].offset;
+    if (mj || mj_c2) {
+      // input and weight gradient in one launch: the small-batch geometry, or the whole-map one
+      const dim3 wg = wgrad6_grid<W2>(W6_P2, B);
+      if (mj) {
+        CHECK((launch_multi<true, Band6Job<typename LY::C2DS>, Wg6Job<W2>>(
+            s, band6_args<typename LY::C2DS>(h, ba, w, WT_C2D, io), dim3(B * LY::C2DS::G::NBANDS), wa, wg)));
+      } else {
+        using C2D = typename LY::C2D;
+        const Band6Args da = band6_args<C2D>(h, ba, w, WT_C2D, io);
+        const dim3 gd(B * C2D::G::NBANDS), g3(c3w_gx, 2);
+        if (c3w_gx && h->c3ride == 2)
+          CHECK((launch_multi<true, Conv3WJob, Band6Job<C2D>, Wg6Job<W2>>(s, c3w, g3, da, gd, wa, wg, h,
+                                                                         BA3C_K_CONV2_DGRAD)));
+        else if (c3w_gx)
+          CHECK((launch_multi<true, Band6Job<C2D>, Wg6Job<W2>, Conv3WJob>(s, da, gd, wa, wg, c3w, g3, h,
+                                                                         BA3C_K_CONV2_DGRAD)));
+        else
+          CHECK((launch_multi<true, Band6Job<C2D>, Wg6Job<W2>>(s, da, gd, wa, wg, 0, dim3(0, 1, 1), h,
+                                                              BA3C_K_CONV2_DGRAD)));
+        if (c3w_gx) h->merged[BA3C_K_CONV2_DGRAD] |= 1u << BA3C_K_CONV3_WGRAD;
+      }
+      h->merged[BA3C_K_CONV2_DGRAD] |= 1u << BA3C_K_CONV2_WGRAD;
+      CHECK(reduce_wgrad6<W2>(h, s, wa, (int)wg.x, dW2));
     } else {
-      WgradPlan pl = plan_wgrad(800, 64, B * 196, 128, 64);
-      ConvWgrad<false, 18, 18, 32, 5, 5, 64, true> g{w.p1, w.dp2, w.c2, w.part_2, 1.0f, pl.M, pl.N, pl.K, pl.kchunk};
-      CHECK((launch_gemm<128, 64, 4, 1>(h, ws, BA3C_K_CONV2_WGRAD, g, pl.S)));
-      CHECK(conv_reduce(pl, 2, 32, 32, w.part_2));
+      if (h->band) {
+        CHECK(launch_wgrad6<W2>(h, ws, BA3C_K_CONV2_WGRAD, wa, W6_P2, dW2));
+      } else {
+        WgradPlan pl = plan_wgrad(800, 64, B * 196, 128, 64);
+        ConvWgrad<false, 18, 18, 32, 5, 5, 64, true> g{w.p1, w.dp2, w.c2, w.part_2, 1.0f, pl.M, pl.N, pl.K, pl.kchunk};
+        CHECK((launch_gemm<128, 64, 4, 1>(h, ws, BA3C_K_CONV2_WGRAD, g, pl.S)));
+        CHECK(conv_reduce(pl, 2, 32, 32, w.part_2));
+      }
+      if (h->band) {
+        if (B <= SMALL_B)
+          CHECK(launch_band6<typename LY::C2DS>(h, s, BA3C_K_CONV2_DGRAD, ba, w, WT_C2D, io));
+        else
+          CHECK(launch_band6<typename LY::C2D>(h, s, BA3C_K_CONV2_DGRAD, ba, w, WT_C2D, io));
+      } else {
+        ConvDgrad<18, 18, 32, 5, 5, 64, true> d{w.dp2, w.c2, W2c, w.dp1, B * 324, 32, 1600, 0};
+        CHECK((launch_gemm<128, 32, 4, 1>(h, s, BA3C_K_CONV2_DGRAD, d, 1)));
+      }
+      CHECK(fork());
     }
-    if (h->band) {
-      const BandArgs ba{w.dp2, w.c2, w.wt + WT_C2D, w.dp1, nullptr, nullptr, B};
-      const SplitIO io{AM_DP2, WJ_C2D, AM_DP1};
-      if (B <= SMALL_B)
-        CHECK(launch_band6<typename LY::C2DS>(h, s, BA3C_K_CONV2_DGRAD, ba, w, WT_C2D, io));
-      else
-        CHECK(launch_band6<typename LY::C2D>(h, s, BA3C_K_CONV2_DGRAD, ba, w, WT_C2D, io));
-    } else {
-      ConvDgrad<18, 18, 32, 5, 5, 64, true> d{w.dp2, w.c2, W2c, w.dp1, B * 324, 32, 1600, 0};
-      CHECK((launch_gemm<128, 32, 4, 1>(h, s, BA3C_K_CONV2_DGRAD, d, 1)));
-    }
-    CHECK(fork());
   }
   // conv1
-  if (mj) {
-    const Wg6Args wa{w.p0, w.dp1, w.c1, w.part_1, B, w.am(AM_P0, h), w.am(AM_DP1, h)};
-    const dim3 wg = wgrad6_grid<typename LY::W1>(conv1_wgrad_p(B), B);
-    const Band6Args da = band6_args<typename LY::C1D>(h, BandArgs{w.dp1, w.c1, w.wt + WT_C1D, w.dp0, nullptr, nullptr, B},
-                                                     w, WT_C1D, SplitIO{AM_DP1, WJ_C1D, AM_DP0});
-    CHECK((launch_multi<true, Band6Job<typename LY::C1D>, Wg6Job<typename LY::W1>>(
-        s, da, dim3(B * LY::C1D::G::NBANDS), wa, wg)));
-    h->merged[BA3C_K_CONV1_DGRAD] |= 1u << BA3C_K_CONV1_WGRAD;
-    CHECK(reduce_wgrad6<typename LY::W1>(h, s, wa, (int)wg.x, grads + h->tensors[h->idx_conv[1]].offset));
-  } else {
-    bool done = false, paired = false;
-    {
-      const bool pairgeo = h->band && h->ring && conv1_pair_geometry(B, h->cus);
-      if (pairgeo && h->c1pair == 2 && CH == 4) {
-        done = defer_w1 = true;                             // beside conv0's weight gradient below
-      }
-      // conv1 input and weight gradients in one launch, one workgroup of each per CU (each job
-      // walks twice the images of its separate launch)
-      if (!done && pairgeo && h->c1pair == 1) {
-        using GW = typename LY::W1W;
-        const Wg6Args wa{w.p0, w.dp1, w.c1, w.part_1, B, w.am(AM_P0, h), w.am(AM_DP1, h)};
-        const Band6Args da = band6_args<typename LY::C1D>(h, BandArgs{w.dp1, w.c1, w.wt + WT_C1D, w.dp0, nullptr, nullptr, B},
-                                                         w, WT_C1D, SplitIO{AM_DP1, WJ_C1D, AM_DP0});
-        CHECK((launch_multi<true, Band6RJob<typename LY::C1D>, Wg6WJob<GW>>(
-            s, da, dim3(h->cus), wa, dim3(h->cus), 0, dim3(0, 1, 1), h, BA3C_K_CONV1_DGRAD)));
+  using W1 = typename LY::W1;
+  const Wg6Args wa1{w.p0, w.dp1, w.c1, w.part_1, B, w.am(AM_P0, h), w.am(AM_DP1, h)};
+  float* dW1 = grads + h->tensors[h->idx_conv[1]].offset;
+  // large batches: its whole-channel weight gradient waits for conv0's (one paired launch below),
+  // or shares the input gradient's launch, one workgroup of each per CU (each job walks twice the
+  // images of its separate launch)
+  const bool pairgeo = !mj && h->band && h->ring && conv1_pair_geometry(B, h->cus);
+  const bool defer_w1 = pairgeo && h->c1pair == 2 && CH == 4;
+  const bool paired = pairgeo && !defer_w1 && h->c1pair == 1;
+  {
+    const BandArgs ba{w.dp1, w.c1, w.wt + WT_C1D, w.dp0, nullptr, nullptr, B};
+    const SplitIO io{AM_DP1, WJ_C1D, AM_DP0};
+    if (mj) {
+      // small batches: input and weight gradient in one launch
+      const dim3 wg = wgrad6_grid<W1>(conv1_wgrad_p(B), B);
+      CHECK((launch_multi<true, Band6Job<typename LY::C1D>, Wg6Job<W1>>(
+          s, band6_args<typename LY::C1D>(h, ba, w, WT_C1D, io), dim3(B * LY::C1D::G::NBANDS), wa1, wg)));
+      h->merged[BA3C_K_CONV1_DGRAD] |= 1u << BA3C_K_CONV1_WGRAD;
+      CHECK(reduce_wgrad6<W1>(h, s, wa1, (int)wg.x, dW1));
+    } else {
+      // the weight gradient: deferred, paired, whole-channel kernel, wgrad6, or the GEMM engine
+      if (defer_w1) {
+        // beside conv0's weight gradient below
+      } else if (paired) {
+        CHECK((launch_multi<true, Band6RJob<typename LY::C1D>, Wg6WJob<typename LY::W1W>>(
+            s, band6_args<typename LY::C1D>(h, ba, w, WT_C1D, io), dim3(h->cus), wa1, dim3(h->cus), 0,
+            dim3(0, 1, 1), h, BA3C_K_CONV1_DGRAD)));
         h->merged[BA3C_K_CONV1_DGRAD] |= 1u << BA3C_K_CONV1_WGRAD;
-        CHECK(reduce_wgrad6<typename LY::W1>(h, s, wa, h->cus, grads + h->tensors[h->idx_conv[1]].offset));
-        done = paired = true;
-      }
-      if (!done && h->band && B >= W6W_MIN_B) {
-        using GW = typename LY::W1W;
-        const Wg6Args wa{w.p0, w.dp1, w.c1, w.part_1, B, w.am(AM_P0, h), w.am(AM_DP1, h)};
+        CHECK(reduce_wgrad6<W1>(h, s, wa1, h->cus, dW1));
+      } else if (h->band && B >= W6W_MIN_B) {
         const int P = conv1_w6w_p(B, h->cus);
         {
           ProbeScope ps(h, ws, BA3C_K_CONV1_WGRAD);
-          hipLaunchKernelGGL(wgrad6w_kernel<GW>, dim3(P), dim3(256), 0, ws, wa);
+          hipLaunchKernelGGL(wgrad6w_kernel<typename LY::W1W>, dim3(P), dim3(256), 0, ws, wa1);
         }
         HIP_TRY(hipGetLastError());
-        CHECK(reduce_wgrad6<typename LY::W1>(h, ws, wa, P, grads + h->tensors[h->idx_conv[1]].offset));
-        done = true;
+        CHECK(reduce_wgrad6<W1>(h, ws, wa1, P, dW1));
+      } else if (h->band) {
+        CHECK(launch_wgrad6<W1>(h, ws, BA3C_K_CONV1_WGRAD, wa1, conv1_wgrad_p(B), dW1));
+      } else {
+        WgradPlan pl = plan_wgrad(800, 32, B * 1296, 128, 32);
+        ConvWgrad<false, 40, 40, 32, 5, 5, 32, true> g{w.p0, w.dp1, w.c1, w.part_1, 1.0f, pl.M, pl.N, pl.K, pl.kchunk};
+        CHECK((launch_gemm<128, 32, 4, 1>(h, ws, BA3C_K_CONV1_WGRAD, g, pl.S)));
+        CHECK(conv_reduce(pl, 1, 32, 32, w.part_1));
       }
-    }
-    if (done) {
-    } else if (h->band) {
-      CHECK(launch_wgrad6<typename LY::W1>(h, ws, BA3C_K_CONV1_WGRAD,
-                                          Wg6Args{w.p0, w.dp1, w.c1, w.part_1, B, w.am(AM_P0, h), w.am(AM_DP1, h)},
-                                          conv1_wgrad_p(B), grads + h->tensors[h->idx_conv[1]].offset));
-    } else {
-      WgradPlan pl = plan_wgrad(800, 32, B * 1296, 128, 32);
-      ConvWgrad<false, 40, 40, 32, 5, 5, 32, true> g{w.p0, w.dp1, w.c1, w.part_1, 1.0f, pl.M, pl.N, pl.K, pl.kchunk};
-      CHECK((launch_gemm<128, 32, 4, 1>(h, ws, BA3C_K_CONV1_WGRAD, g, pl.S)));
-      CHECK(conv_reduce(pl, 1, 32, 32, w.part_1));
-    }
-    if (paired) {
-      // both gradients ran in the multi-job launch above
-    } else if (use_c1s(h, B)) {
-      // 2:4-sparse MFMA (ba3c_dgrad1s.h): two workgroups per CU, persistent over bands
-      const Band6Args b = band6_args<typename LY::C1D>(h, BandArgs{w.dp1, w.c1, nullptr, w.dp0, nullptr, nullptr, B},
-                                                       w, WT_C1S, SplitIO{AM_DP1, WJ_C1S, AM_DP0});
-      {
-        ProbeScope ps(h, s, BA3C_K_CONV1_DGRAD);
-        hipLaunchKernelGGL(dgrad1s_kernel, dim3(2 * h->cus), dim3(256), 0, s, b);
+      // then the input gradient
+      if (paired) {
+        // ran in the multi-job launch above
+      } else if (h->band) {
+        CHECK(launch_band6<typename LY::C1D>(h, s, BA3C_K_CONV1_DGRAD, ba, w, WT_C1D, io, true));
+      } else {
+        ConvDgrad<40, 40, 32, 5, 5, 32, true> d{w.dp1, w.c1, W1c, w.dp0, B * 1600, 32, 800, 0};
+        CHECK((launch_gemm<128, 32, 4, 1>(h, s, BA3C_K_CONV1_DGRAD, d, 1)));
       }
-      HIP_TRY(hipGetLastError());
-    } else if (h->band) {
-      const BandArgs ba{w.dp1, w.c1, nullptr, w.dp0, nullptr, nullptr, B};
-      CHECK(launch_band6<typename LY::C1D>(h, s, BA3C_K_CONV1_DGRAD, ba, w, WT_C1D, SplitIO{AM_DP1, WJ_C1D, AM_DP0},
-                                           true));
-    } else {
-      ConvDgrad<40, 40, 32, 5, 5, 32, true> d{w.dp1, w.c1, W1c, w.dp0, B * 1600, 32, 800, 0};
-      CHECK((launch_gemm<128, 32, 4, 1>(h, s, BA3C_K_CONV1_DGRAD, d, 1)));
     }
   }
   // conv0 (no input gradient: the frames are not trainable)
@@ -1183,13 +1140,12 @@ int run_backward(ba3c_handle* h, hipStream_t s, const float* prm, const uint8_t*
     if (defer_w1) {
       // conv1's whole-channel weight gradient (MFMA-bound) beside conv0's (VALU-bound): one
       // workgroup of each per CU, one launch (ba3c_conv0.hip)
-      const Wg6Args wa{w.p0, w.dp1, w.c1, w.part_1, B, w.am(AM_P0, h), w.am(AM_DP1, h)};
       {
         ProbeScope ps(h, s, BA3C_K_CONV0_WGRAD);
-        HIP_TRY(launch_wgrad01_pair(s, wa, h->cus, a0, P));
+        HIP_TRY(launch_wgrad01_pair(s, wa1, h->cus, a0, P));
       }
       h->merged[BA3C_K_CONV0_WGRAD] |= 1u << BA3C_K_CONV1_WGRAD;
-      CHECK(reduce_wgrad6<typename LY::W1>(h, s, wa, h->cus, grads + h->tensors[h->idx_conv[1]].offset));
+      CHECK(reduce_wgrad6<W1>(h, s, wa1, h->cus, dW1));
     } else {
       ProbeScope ps(h, s, BA3C_K_CONV0_WGRAD);
       HIP_TRY(launch_conv0s_wgrad(dim3(P), s, a0));
@@ -1416,39 +1372,32 @@ int ba3c_create(const ba3c_config* cfg, ba3c_handle** out) {
   // are rejected rather than coerced, so an A/B run measures what it asked for)
   struct Switch {
     const char* name;
-    int lo, hi;
+    const char* digits;   // the accepted values
+    int value;            // the default, then what the environment sets
+    void (*set)(ba3c_handle*, int);
   };
-  static const Switch kSwitches[] = {{"BA3C_GENERIC", 0, 1},  {"BA3C_C1PAIR", 0, 2},   {"BA3C_SCALARS_RIDE", 0, 1},
-                                     {"BA3C_OVERLAP", 0, 2},  {"BA3C_MULTI", 0, 1},    {"BA3C_MULTI_BIG", 0, 3},
-                                     {"BA3C_FUSED_UPDATE", 0, 1}, {"BA3C_RING", 0, 1}, {"BA3C_CHAIN", 0, 1},
-                                     {"BA3C_C1D_SPARSE", 0, 1}, {"BA3C_DYNQ", 0, 1},
-                                     {"BA3C_C3W_RIDE", 0, 2}};
-  constexpr int NSW = 12;
-  int sw[NSW];
-  const int defaults[NSW] = {0, 2, 1, 2, 1, 3, 1, 1, 1, 0, 0, 0};
-  for (int i = 0; i < NSW; ++i) {
-    sw[i] = defaults[i];
-    const char* e = getenv(kSwitches[i].name);
+  Switch switches[] = {
+      {"BA3C_GENERIC", "01", 0, [](ba3c_handle* h, int v) { h->band = v == 0; }},
+      {"BA3C_C1PAIR", "012", 2, [](ba3c_handle* h, int v) { h->c1pair = v; }},
+      {"BA3C_SCALARS_RIDE", "01", 1, [](ba3c_handle* h, int v) { h->scalars_ride = v != 0; }},
+      {"BA3C_OVERLAP", "012", 2, [](ba3c_handle* h, int v) { h->overlap = v; }},
+      {"BA3C_MULTI", "01", 1, [](ba3c_handle* h, int v) { h->multi = v != 0; }},
+      {"BA3C_MULTI_BIG", "0123", 3, [](ba3c_handle* h, int v) { h->multi_big = v; }},
+      {"BA3C_FUSED_UPDATE", "01", 1, [](ba3c_handle* h, int v) { h->fused_update = v != 0; }},
+      {"BA3C_RING", "01", 1, [](ba3c_handle* h, int v) { h->ring = v != 0; }},
+      {"BA3C_CHAIN", "01", 1, [](ba3c_handle* h, int v) { h->chain_on = v != 0; }},
+      {"BA3C_C3W_RIDE", "012", 0, [](ba3c_handle* h, int v) { h->c3ride = v; }},
+  };
+  for (Switch& k : switches) {
+    const char* e = getenv(k.name);
     if (!e) continue;
-    if (!(e[0] >= '0' && e[0] <= '9' && e[1] == 0) || e[0] - '0' < kSwitches[i].lo || e[0] - '0' > kSwitches[i].hi)
-      return fail(BA3C_ERR_INVALID, std::string(kSwitches[i].name) + "=" + e + ": expected one digit in [" +
-                                        std::to_string(kSwitches[i].lo) + ", " + std::to_string(kSwitches[i].hi) + "]");
-    sw[i] = e[0] - '0';
+    if (!e[0] || e[1] || !strchr(k.digits, e[0]))
+      return fail(BA3C_ERR_INVALID, std::string(k.name) + "=" + e + ": expected one digit of " + k.digits);
+    k.value = e[0] - '0';
   }
   ba3c_handle* h = new ba3c_handle();
   h->cfg = c;
-  h->band = sw[0] == 0;
-  h->c1pair = sw[1];
-  h->scalars_ride = sw[2] != 0;
-  h->overlap = sw[3];
-  h->multi = sw[4] != 0;
-  h->multi_big = sw[5];
-  h->fused_update = sw[6] != 0;
-  h->ring = sw[7] != 0;
-  h->chain_on = sw[8] != 0;
-  h->c1s = sw[9] != 0;
-  h->dynq = sw[10] != 0;
-  h->c3ride = sw[11];
+  for (const Switch& k : switches) k.set(h, k.value);
   h->g6 = h->band;
   {
     int dev = 0, n = 0;

@@ -71,10 +71,10 @@ struct Conv0Geom {
 struct WPrepJob {
   const float* w;
   float* wt;
-  int KH, KW, CI, CO, dgrad, n;   // n = total elements; dgrad 2: conv1's sparse input gradient
+  int KH, KW, CI, CO, dgrad, n;   // n = total elements
 };
 struct WPrepArgs {
-  WPrepJob job[7];
+  WPrepJob job[6];
   int njobs;
 };
 

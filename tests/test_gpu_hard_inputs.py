@@ -183,11 +183,8 @@ def test_saturated_policy_matches_oracle(head_scale):
 
 @pytest.mark.parametrize("frames", ["random", "atari"])
 def test_ring_walk_at_bench_batch_matches_one_band_kernels(monkeypatch, frames):
-    """B=2048: ipw = 4 images per ring-walk workgroup (the bench's own geometry).  conv1's
-    input gradient on both sides is the dense band kernel (BA3C_C1D_SPARSE=0): the sparse one
-    sums in another order and is held to the dense one in tests/test_gpu_graph.py."""
+    """B=2048: ipw = 4 images per ring-walk workgroup (the bench's own geometry)."""
     B = 2048
-    monkeypatch.setenv("BA3C_C1D_SPARSE", "0")
     rs = np.random.RandomState(79)
     if frames == "random":
         state = rs.randint(0, 256, size=(B, 84, 84, 4)).astype(np.uint8)
@@ -245,12 +242,8 @@ def test_large_batch_launch_structures_match_default(monkeypatch, var, base, mod
     same order (one per CU in the pair geometry), so the gradients, scalars and dP0 are
     bit-identical — B=1024, 4 images per ring-walk workgroup.  BA3C_SCALARS_RIDE: the TfDictOp
     scalar reduction in its own launch after the heads (0) or as one workgroup of conv3's
-    input-gradient launch (1, default) — the same body, the same scalars.  Mode 1 runs conv1's
-    dense input gradient inside the paired launch, so both sides use the dense one there
-    (BA3C_C1D_SPARSE=0; the sparse kernel is held to the dense one in test_gpu_graph.py)."""
+    input-gradient launch (1, default) — the same body, the same scalars."""
     B = 1024
-    if var == "BA3C_C1PAIR" and mode == "1":
-        monkeypatch.setenv("BA3C_C1D_SPARSE", "0")
     rs = np.random.RandomState(83)
     state = dev(rs.randint(0, 256, size=(B, 84, 84, 4)).astype(np.uint8))
     action = torch.from_numpy(rs.randint(0, 4, size=B).astype(np.int64)).cuda()

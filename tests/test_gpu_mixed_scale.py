@@ -150,7 +150,7 @@ def _train_and_keep(eng, state, action, R, names):
 
 
 @pytest.mark.parametrize("B", [32, 160, 1024])
-def test_maps_of_an_image_do_not_depend_on_its_slot(monkeypatch, B):
+def test_maps_of_an_image_do_not_depend_on_its_slot(B):
     """The same batch in two orders.  The same B means the same kernels and the same 1/B; only
     the slot, the workgroup and the ring position of an image change — and the kind of its
     neighbours: perm[n] = B - 1 - 3 n (mod B), a reversal with stride 3, puts an image of
@@ -159,8 +159,6 @@ def test_maps_of_an_image_do_not_depend_on_its_slot(monkeypatch, B):
     slots onto their own kind — rolled by 3, slot 1 onto itself.)  Every map of run 2 equals
     run 1's at the permuted index bit for bit.  Weight gradients are sums in another order
     and are not compared."""
-    if B == 1024:
-        monkeypatch.setenv("BA3C_C1D_SPARSE", "0")    # as the ring tests: the dense conv1 dgrad
     state, kinds = mixed_frames(B, 17)
     perm = (B - 1 - 3 * np.arange(B)) % B
     assert np.array_equal(np.sort(perm), np.arange(B)) and np.all(kinds[perm] != kinds)
@@ -182,7 +180,6 @@ def test_ring_walk_on_mixed_images_matches_one_band_kernels(monkeypatch):
     workgroup) on mixed images: the walk prefetches the next image's raw rows while it still
     holds the current image's scale, and here the two always differ."""
     B = 1024
-    monkeypatch.setenv("BA3C_C1D_SPARSE", "0")
     state, _ = mixed_frames(B, 79)
     action = dev(np.random.RandomState(79).randint(0, 4, size=B).astype(np.int64))
     state = dev(state)
