@@ -108,6 +108,7 @@ def load():
         "ba3c_boxing_render": (i32, [P, P, i32, P, P]),
         "ba3c_boxing_duel_step": (i32, [P, P, P, i32, i32, P, P, P, P, P]),
         "ba3c_boxing_duel_render": (i32, [P, P, i32, P, P]),
+        "ba3c_boxing_duel_decide": (i32, [P, P, P, P, i32, i32, i32, i32, i32, i32, i32, P, P, P, P, P]),
         "ba3c_breakout_step_skip": (i32, [P, P, P, P, i32, i32, i32, i32, i32, P, P, P, P, P]),
         "ba3c_boxing_step_skip": (i32, [P, P, P, P, i32, i32, i32, i32, i32, P, P, P, P, P]),
         "ba3c_breakout_view": (i32, [P, P, i32, P, i32, P, P, i32, P]),

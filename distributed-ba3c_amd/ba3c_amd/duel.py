@@ -4,11 +4,13 @@ are driven by actions and each side receives its own observation, for self-play 
 (`match`, `python -m ba3c_amd.duel`).  This module holds the rules ONCE: `step_numpy`,
 `render_numpy` and `mirror_rows` (the oracle of the HIP kernel in csrc/ba3c_duel.h) over
 GridBoxing's constants, and `BoxingDuelVec`, G games = 2G players on the device with
-BoxingVec's interface.
+BoxingVec's interface (`BoxingDuelDecisionVec`: the same under frame skip, sticky actions and
+drawn starts).
 
 Row: GridBoxing's, `game[e] = [ax, ay, bx, by, a_cd, b_cd, a_score, b_score, t, rng, 0, ...]`,
-16 int32, side B in the scripted opponent's columns.  `rng` is carried unchanged: the duel draws
-nothing.  A fresh episode is GridBoxing's: (20, 42, 58, 42), the rest zero.
+16 int32, side B in the scripted opponent's columns.  `rng` is carried unchanged: a step draws
+nothing.  A fresh episode is GridBoxing's: (20, 42, 58, 42), the rest zero (or a drawn row, see
+"Drawn starts" below, the only rule that draws from `rng`).
 
 Players: G games have 2G players.  Player p = e is side A of game e, player p = G + e is side B
 of game e; every per-player array (actions in; reward, over, ep_score, frame, state out) has 2G
@@ -48,12 +50,53 @@ and every clamp range [4, 74] is its own image under x -> 78 - x.)  Neither side
 Observations: side A's frame is boxing.render_numpy(row), side B's is
 boxing.render_numpy(mirror_rows(row)); there are no new render rules.  A step returns the frame
 AFTER the step; on `over` that is the new episode's first frame, and both histories restart.
+
+Drawn starts: a setting start = (h_lo, h_hi), 4 <= h_lo <= h_hi <= 19, is the range of the
+HALF-gap between the boxers of a fresh episode.  (19, 19) is the fixed start above and draws
+nothing: rng stays untouched.  Any other setting makes the fresh row from the row's own rng, which
+no other rule of the duel reads or writes:
+
+    rng = lcg(rng); r = rng >> 16
+    h = h_lo + r % (h_hi - h_lo + 1);  y = 14 + 2 * ((r >> 8) % 29)
+    row = (39 - h, y, 39 + h, y, 0, 0, 0, 0, 0, rng, 0...)
+
+h >= 4 keeps the 6 px bodies apart; the boxers are within reach (gap 2h <= 14) iff h <= 7; y
+runs over the even rows 14..70.  Users give the gap in pixels, 2h: even numbers 8..38, 38 being
+the fixed start (`start_from_gap`).  Every drawn row is its own image under mirror_rows
+(78 - (39 - h) = 39 + h, the y's are equal, the rest is zero), and rng is the same field on both
+sides of the mirror, so step(mirror(g)) draws the same h and y as step(g) and lands on the same
+self-mirrored row: the mirror invariant stays exact.  `initial_rows` applies the same draw to
+initial_game's rows, so first episodes are drawn too.
+
+One decision (`decide_numpy`): frame skip and sticky actions as ba3c_amd.frameskip states them,
+per side.  aux[e] = [rng_k, rng_a, rng_b, prev_a, prev_b, 0, 0, 0], 8 int32: the skip's generator,
+one generator per side for its sticky draws and each side's last effective action, all on
+frameskip's LCG.  With parameters lo, hi, q16 (frameskip's ranges) and start, in this order:
+
+    a, b = the two actions, each 0 (NOOP) unless in [0, 32)
+    rng_k = lcg(rng_k); k = lo + ((rng_k >> 16) % (hi - lo + 1))
+    R = 0
+    for j in range(k):
+        rng_a = lcg(rng_a); prev_a = prev_a if ((rng_a >> 8) & 0xFFFF) < q16 else a
+        rng_b = lcg(rng_b); prev_b = prev_b if ((rng_b >> 8) & 0xFFFF) < q16 else b
+        r, over, ep = step(prev_a, prev_b), whose fresh row is start's
+        R += r
+        if over: prev_a = prev_b = 0; break                # the remaining sub-steps are dropped
+    reward_A = R; reward_B = -R; over and ep_score as the last executed step's
+
+The frame (and the history push) is the one after the last executed sub-step.  `limit` counts
+game steps.  With (1, 1, 0) and the fixed start a decision is exactly step.  The skip is shared,
+so it has ONE generator; the sticky draws are per side, so each side has its own, and
+`mirror_aux` (swap rng_a / rng_b and prev_a / prev_b, keep rng_k) extends the mirror invariant to
+decisions: decide(mirror(g), mirror_aux(x), (b, a)) == mirror(decide(g, x, (a, b))), rewards and
+ep_scores negated.  Had both sides drawn from one generator, the order of the two draws would
+have told them apart.
 """
 import ctypes
 
 import numpy as np
 
-from . import boxing
+from . import boxing, frameskip
 from .boxing import (AX, AX0, AY, AY0, A_CD, A_SCORE, CLOCK, COOLDOWN, DEFAULT_LIMIT, DOWN_MASK, FIRE_MASK,
                      H, KNOCK, KO, LEFT_MASK, NOOP, NUM_ACTIONS, OX, OX0, OY, OY0, O_CD, O_SCORE, PALETTE,
                      RIGHT_MASK, RNG, T, UP_MASK, W, X_MAX, X_MIN, Y_MAX, Y_MIN, _clamp, _pts,
@@ -62,6 +105,12 @@ from .boxing import (AX, AX0, AY, AY0, A_CD, A_SCORE, CLOCK, COOLDOWN, DEFAULT_L
 STEP = 2                                 # both sides move 2 px per step
 MIRROR = 78                              # x -> 78 - x: body top-lefts 4..74 map onto themselves
 BX, BY, B_CD, B_SCORE = OX, OY, O_CD, O_SCORE
+CENTRE = 39                              # a drawn row is (39 - h, y, 39 + h, y): its own mirror image
+H_MIN, H_MAX = 4, 19                     # half-gaps: bodies apart .. the fixed start
+FIXED_START = (H_MAX, H_MAX)             # (20, 42, 58, 42), no draw
+Y_DRAWS = 29                             # y = 14 + 2 * (0..28): the even rows 14..70
+AUX_INTS = 8
+RNG_K, RNG_A, RNG_B, PREV_A, PREV_B = range(5)
 
 
 def mirror_rows(game):
@@ -83,10 +132,85 @@ def _decode(a):
     return right - left, down - up, fire == 1
 
 
-def step_numpy(game, actions, limit=DEFAULT_LIMIT):
+def check_start(start):
+    """(h_lo, h_hi) of a `start=` argument (None: the fixed start), checked; raises ValueError."""
+    if start is None:
+        return FIXED_START
+    if not isinstance(start, (tuple, list)) or len(start) != 2:
+        raise ValueError("start %r: expected (h_lo, h_hi)" % (start,))
+    lo, hi = int(start[0]), int(start[1])
+    if not H_MIN <= lo <= hi <= H_MAX:
+        raise ValueError("start half-gap %r-%r: needs %d <= lo <= hi <= %d" % (lo, hi, H_MIN, H_MAX))
+    return lo, hi
+
+
+def parse_gap(s):
+    """A string "GAP" / "LO-HI" (pixels) -> (lo, hi), inclusive; the range is start_from_gap's."""
+    parts = [int(p) for p in str(s).split("-")]                # "-8", "a": ValueError
+    if len(parts) not in (1, 2):
+        raise ValueError("start gap %r: expected GAP or LO-HI" % (s,))
+    return parts[0], parts[-1]
+
+
+def start_from_gap(gap):
+    """The user-facing unit -> `start=`: a gap in pixels (an int, a (lo, hi) pair or a string
+    "GAP" / "LO-HI"; even numbers 8..38) -> (h_lo, h_hi), or None for 38, the fixed start."""
+    if isinstance(gap, str):
+        gap = parse_gap(gap)
+    if not isinstance(gap, (tuple, list)):
+        gap = (gap, gap)
+    lo, hi = int(gap[0]), int(gap[-1])
+    if len(gap) != 2 or lo % 2 or hi % 2 or not 2 * H_MIN <= lo <= hi <= 2 * H_MAX:
+        raise ValueError("start gap %r: needs even pixels with %d <= lo <= hi <= %d"
+                         % (gap, 2 * H_MIN, 2 * H_MAX))
+    return None if (lo, hi) == (2 * H_MAX, 2 * H_MAX) else (lo // 2, hi // 2)
+
+
+def draw_start(rng, start):
+    """The draw of a fresh row: rng (int64 array of uint32 values) -> (rng', h, y)."""
+    lo, hi = start
+    rng = frameskip.lcg(rng)
+    r = rng >> 16
+    return rng, lo + r % (hi - lo + 1), Y_MIN + 2 * ((r >> 8) % Y_DRAWS)
+
+
+def initial_rows(n_games, seed=0, start=None):
+    """[G,16] int32 rows of fresh games: boxing.initial_game's, and under a drawn start the
+    first episodes' rows are drawn as every later one's."""
+    game = initial_game(n_games, seed)
+    start = check_start(start)
+    if start != FIXED_START:
+        rng, h, y = draw_start(game[:, RNG].astype(np.int64) & 0xFFFFFFFF, start)
+        game[:, AX], game[:, AY], game[:, BX], game[:, BY] = CENTRE - h, y, CENTRE + h, y
+        game[:, RNG] = rng.astype(np.uint32).view(np.int32)
+    return game
+
+
+def initial_aux(n_games, seed=0):
+    """[G,8] int32 aux rows of fresh games: three of frameskip's generators, prev = NOOP."""
+    G = int(n_games)
+    aux = np.zeros((G, AUX_INTS), np.int32)
+    e = np.arange(G, dtype=np.int64)
+    for col, first in ((RNG_A, 0), (RNG_B, G), (RNG_K, 2 * G)):
+        v = ((np.int64(seed) * 1000 + first + e) ^ frameskip.SEED_XOR) & 0xFFFFFFFF
+        aux[:, col] = v.astype(np.uint32).view(np.int32)
+    return aux
+
+
+def mirror_aux(aux):
+    """The aux rows as side B holds them: the sides' generators and prevs exchanged."""
+    x = np.asarray(aux)
+    m = np.zeros_like(x)
+    m[..., RNG_K], m[..., RNG_A], m[..., RNG_B] = x[..., RNG_K], x[..., RNG_B], x[..., RNG_A]
+    m[..., PREV_A], m[..., PREV_B] = x[..., PREV_B], x[..., PREV_A]
+    return m
+
+
+def step_numpy(game, actions, limit=DEFAULT_LIMIT, start=None):
     """One step of every row of `game` ([G,16] int32, updated in place) under `actions` [2G]
-    (player order).  Returns (reward float64 [2G], over bool [2G], ep_score int32 [2G], 0 where
-    not over)."""
+    (player order); start: the fresh rows' (h_lo, h_hi), None for the fixed start.  Returns
+    (reward float64 [2G], over bool [2G], ep_score int32 [2G], 0 where not over)."""
+    start = check_start(start)
     G = game.shape[0]
     act = np.asarray(actions).astype(np.int64).reshape(2 * G)
     g = game.astype(np.int64)
@@ -117,13 +241,60 @@ def step_numpy(game, actions, limit=DEFAULT_LIMIT):
     ep = np.where(over, a_score - b_score, 0)
 
     fresh = (AX0, AY0, OX0, OY0, 0, 0, 0, 0, 0)
+    if start != FIXED_START:                               # the only draw from the row's rng
+        rng = g[:, RNG] & 0xFFFFFFFF
+        drawn, h, y = draw_start(rng, start)
+        fresh = (CENTRE - h, y, CENTRE + h, y, 0, 0, 0, 0, 0)
+        game[:, RNG] = np.where(over, drawn, rng).astype(np.uint32).view(np.int32)
     cols = (ax, ay, bx, by, a_cd, b_cd, a_score, b_score, t)
     for i, (v, f) in enumerate(zip(cols, fresh)):
         game[:, i] = np.where(over, f, v).astype(np.int32)
-    game[:, RNG + 1:] = 0                                  # rng (column 9) is carried unchanged
+    game[:, RNG + 1:] = 0                                  # rng (column 9) is otherwise carried unchanged
     reward = (pa - pb).astype(np.float64)
     return (np.concatenate([reward, -reward]), np.concatenate([over, over]),
             np.concatenate([ep, -ep]).astype(np.int32))
+
+
+def decide_numpy(game, aux, actions, limit=DEFAULT_LIMIT, lo=1, hi=1, q16=0, start=None):
+    """One decision of every row of `game` ([G,16] int32) and `aux` ([G,8] int32), both updated
+    in place, under `actions` [2G] (player order).  Returns step_numpy's triple: the rewards are
+    summed over the executed sub-steps."""
+    frameskip.check(lo, hi, q16)
+    start = check_start(start)
+    G = game.shape[0]
+    act = np.asarray(actions).astype(np.int64).reshape(2 * G)
+    act = np.where((act >= 0) & (act < frameskip.ACTION_BOUND), act, 0)
+    chosen = (act[:G], act[G:])
+    rng_k = frameskip.lcg(aux[:, RNG_K].astype(np.int64) & 0xFFFFFFFF)
+    k = lo + ((rng_k >> 16) % (hi - lo + 1))
+    rng = [aux[:, c].astype(np.int64) & 0xFFFFFFFF for c in (RNG_A, RNG_B)]
+    prev = [aux[:, c].astype(np.int64) for c in (PREV_A, PREV_B)]
+    R = np.zeros(G, np.float64)
+    over = np.zeros(G, bool)
+    ep_score = np.zeros(G, np.int64)
+    for j in range(hi):
+        live = (j < k) & ~over
+        if not live.any():
+            break
+        eff = [None, None]
+        for s in range(2):                                 # each side draws from its own generator
+            rng[s] = np.where(live, frameskip.lcg(rng[s]), rng[s])
+            eff[s] = np.where(((rng[s] >> 8) & 0xFFFF) < q16, prev[s], chosen[s])
+        kept = game.copy()
+        r, o, ep = step_numpy(game, np.concatenate(eff), limit, start)
+        game[~live] = kept[~live]         # k exhausted or episode ended: that row did not step
+        ended = live & o[:G]
+        R += np.where(live, r[:G], 0.0)
+        over |= ended
+        ep_score = np.where(ended, ep[:G], ep_score)
+        for s in range(2):
+            prev[s] = np.where(ended, 0, np.where(live, eff[s], prev[s]))
+    aux[:] = 0
+    for c, v in ((RNG_K, rng_k), (RNG_A, rng[0]), (RNG_B, rng[1])):
+        aux[:, c] = v.astype(np.uint32).view(np.int32)
+    aux[:, PREV_A], aux[:, PREV_B] = prev[0].astype(np.int32), prev[1].astype(np.int32)
+    return (np.concatenate([R, -R]), np.concatenate([over, over]),
+            np.concatenate([ep_score, -ep_score]).astype(np.int32))
 
 
 def render_numpy(game):
@@ -137,11 +308,16 @@ class BoxingDuelVec(object):
     `A`, `frames()`, `reset_history`, `step(actions) -> frames, reward, over`,
     `step_into(actions, hist)`, `last_over`, `last_ep_score`, `game`, `ep_score`), all over the
     E players in player order; `game` is [G,16].  Every step is one HIP launch
-    (ba3c_boxing_duel_step).  No frame skip and no sticky actions."""
+    (ba3c_boxing_duel_step).  No frame skip, no sticky actions, the fixed start: those are
+    BoxingDuelDecisionVec's."""
 
     A = NUM_ACTIONS
+    skip = start = aux = None              # the one-step launch: no decision setting, no aux rows
 
     def __init__(self, n_games, seed=0, limit=DEFAULT_LIMIT, device="cuda"):
+        self._init(n_games, seed, limit, device)
+
+    def _init(self, n_games, seed, limit, device):
         import torch
 
         from . import _lib
@@ -155,7 +331,9 @@ class BoxingDuelVec(object):
             raise ValueError("n_games and limit must be >= 1")
         self.device = torch.device(device)
         dev = self.device
-        self.game = torch.from_numpy(initial_game(self.G, seed)).to(dev)
+        if self.skip is not None:
+            self.aux = torch.from_numpy(initial_aux(self.G, seed)).to(dev)
+        self.game = torch.from_numpy(initial_rows(self.G, seed, self.start)).to(dev)
         self.reward = torch.zeros(self.E, dtype=torch.float64, device=dev)
         self.over = torch.zeros(self.E, dtype=torch.uint8, device=dev)
         self.ep_score = torch.zeros(self.E, dtype=torch.int32, device=dev)
@@ -190,11 +368,14 @@ class BoxingDuelVec(object):
     def _step(self, actions, frame, state):
         a = actions.to(device=self.device, dtype=self._torch.int64).contiguous()
         assert a.shape == (self.E,)
+        self._launch(a, frame, state)
+        return self.reward, self.over.view(self._torch.bool)
+
+    def _launch(self, a, frame, state):
         self._check(self.lib.ba3c_boxing_duel_step(
             self._stream(), self._ptr(self.game), self._ptr(a), self.G, self.limit,
             self._ptr(self.reward), self._ptr(self.over), self._ptr(self.ep_score),
             self._ptr(frame), self._ptr(state)))
-        return self.reward, self.over.view(self._torch.bool)
 
     def step(self, actions):
         """-> (frames [E,84,84,1] uint8, reward float64 [E], over bool [E]); the tensors are
@@ -208,12 +389,25 @@ class BoxingDuelVec(object):
         self._check_hist(hist)
         return self._step(actions, None, hist.state)
 
-    def view(self, scale=1, sel=None, hud=None):
+    def mirrored_game(self):
+        """mirror_rows of `game` as a new tensor on the device (a few tensor ops)."""
+        m = self.game[:, [BX, BY, AX, AY, B_CD, A_CD, B_SCORE, A_SCORE] + list(range(T, 16))]
+        m[:, AX] = MIRROR - m[:, AX]
+        m[:, BX] = MIRROR - m[:, BX]
+        m[:, RNG + 1:] = 0
+        return m.contiguous()
+
+    def view(self, scale=1, sel=None, hud=None, side="a"):
         """The colour view of the current GAMES, the world as side A sees it
         (ba3c_amd.view.view_numpy of the rows with GridBoxing's palette): torch.uint8
-        [n, Hc*scale, 84*scale, 3] through ba3c_boxing_view; sel: game indices (None: all G)."""
+        [n, Hc*scale, 84*scale, 3] through ba3c_boxing_view; sel: game indices (None: all G).
+        side="b": the world as side B sees it, the same view of the mirrored rows."""
         from .view import device_view
-        return device_view(self, self.lib.ba3c_boxing_view, PALETTE, scale, sel, hud, n_rows=self.G)
+        if side not in ("a", "b"):
+            raise ValueError("side must be 'a' or 'b'")
+        rows = self.mirrored_game() if side == "b" else None
+        return device_view(self, self.lib.ba3c_boxing_view, PALETTE, scale, sel, hud, n_rows=self.G,
+                           rows=rows)
 
     @property
     def last_over(self):
@@ -224,6 +418,31 @@ class BoxingDuelVec(object):
         """(ep_score int32 [E], over bool [E]) of the last step: ep_score[p] is player p's score
         of the finished episode where over[p], stale elsewhere."""
         return self.ep_score, self.last_over
+
+
+class BoxingDuelDecisionVec(BoxingDuelVec):
+    """BoxingDuelVec whose step is one DECISION of `decide_numpy`: `frame_skip` / `sticky`
+    (ba3c_amd.frameskip's arguments, per side) and `start`, a drawn start's (h_lo, h_hi).  One
+    HIP launch per decision (ba3c_boxing_duel_decide), aux rows [G,8] in `aux`, the setting in
+    `skip` (lo, hi, q16) and `start`.  With the defaults it is a BoxingDuelVec: no `aux`, the
+    same rows, the same entry points, as BoxingVec is under ba3c_amd.frameskip."""
+
+    def __init__(self, n_games, seed=0, limit=DEFAULT_LIMIT, device="cuda", frame_skip=1, sticky=0.0,
+                 start=None):
+        skip = frameskip.setting(frame_skip, sticky)
+        start = check_start(start)
+        if skip is not None or start != FIXED_START:
+            self.skip, self.start = skip or (1, 1, 0), start
+        self._init(n_games, seed, limit, device)
+
+    def _launch(self, a, frame, state):
+        if self.skip is None:
+            return BoxingDuelVec._launch(self, a, frame, state)
+        (lo, hi, q16), (h_lo, h_hi) = self.skip, self.start
+        self._check(self.lib.ba3c_boxing_duel_decide(
+            self._stream(), self._ptr(self.game), self._ptr(self.aux), self._ptr(a), self.G,
+            self.limit, lo, hi, q16, h_lo, h_hi, self._ptr(self.reward), self._ptr(self.over),
+            self._ptr(self.ep_score), self._ptr(frame), self._ptr(state)))
 
 
 class _PolicySide(object):
@@ -239,15 +458,11 @@ class _PolicySide(object):
         self.greedy = greedy
 
 
-def match(side_a, side_b, n_games, episodes, seed=0, limit=DEFAULT_LIMIT, device=None):
-    """Play side_a (side A of every game) against side_b on `n_games` games until `episodes`
-    games have finished; those finishing in the same step as the last one are counted too (as
-    eval_with_envs counts them).  A side is an engine or a policy(state) -> probs [G, A]
-    callable; each decides from its own half of the stacked state along evaluation's path
-    (greedy, eps = 0.001, PreventStuckPlayer(30, 1) per player) with its own RandomState derived
-    from `seed`.  Returns a dict: episodes, wins / draws / losses of side A (the sign of its
-    ep_score), mean_score / max_score of side A's ep_score, and scores, one per episode in the
-    order they finished."""
+def _play(side_a, side_b, n_games, episodes, seed, limit, device, frame_skip, sticky, start, watch=None):
+    """The decision path `match` and `record_match` share.  watch (None for a match) is told of
+    the env before the first decision (`begin(env)`), of every decision while the env still holds
+    the rows it was made for (`decided(env, outs)`, outs = each side's (probs, value, act)) and
+    of every step (`stepped(env, reward, over_h)`, side A's halves on the host).  -> scores."""
     import torch
 
     from .evaluate import EvalPlayers
@@ -265,18 +480,45 @@ def match(side_a, side_b, n_games, episodes, seed=0, limit=DEFAULT_LIMIT, device
         else:
             assert G <= side.max_batch and side.num_actions >= NUM_ACTIONS
             players.append(EvalPlayers(side, G, rs))
-    env = BoxingDuelVec(G, seed=seed, limit=limit, device=device)
+    env = BoxingDuelDecisionVec(G, seed=seed, limit=limit, device=device, frame_skip=frame_skip,
+                                sticky=sticky, start=start)
     hist = FrameHistory(env.E, hist_len=4, channels=1, device=env.device)
     env.reset_history(hist)
+    if watch is not None:
+        watch.begin(env)
     scores = []
     while len(scores) < episodes:
-        acts = [p.decide(s)[2] for p, s in zip(players, (hist.state[:G], hist.state[G:]))]
-        _, over = env.step_into(torch.cat(acts), hist)
+        outs = [p.decide(s) for p, s in zip(players, (hist.state[:G], hist.state[G:]))]
+        if watch is not None:
+            watch.decided(env, outs)
+        reward, over = env.step_into(torch.cat([o[2] for o in outs]), hist)
         players[0].ended(over[:G])
         players[1].ended(over[G:])
         over_h = over[:G].cpu().numpy()
+        if watch is not None:
+            watch.stepped(env, reward[:G].cpu().numpy(), over_h)
         if over_h.any():
             scores += env.ep_score[:G].cpu().numpy()[over_h].tolist()
+    return scores
+
+
+def match(side_a, side_b, n_games, episodes, seed=0, limit=DEFAULT_LIMIT, device=None, frame_skip=1,
+          sticky=0.0, start=None):
+    """Play side_a (side A of every game) against side_b on `n_games` games until `episodes`
+    games have finished; those finishing in the same step as the last one are counted too (as
+    eval_with_envs counts them).  A side is an engine or a policy(state) -> probs [G, A]
+    callable; each decides from its own half of the stacked state along evaluation's path
+    (greedy, eps = 0.001, PreventStuckPlayer(30, 1) per player, counting chosen actions, one per
+    decision) with its own RandomState derived from `seed`.  frame_skip / sticky / start:
+    BoxingDuelDecisionVec's.  Returns a dict: episodes, wins / draws / losses of side A (the sign of its
+    ep_score), mean_score / max_score of side A's ep_score, and scores, one per episode in the
+    order they finished."""
+    return match_result(_play(side_a, side_b, n_games, episodes, seed, limit, device, frame_skip, sticky,
+                              start))
+
+
+def match_result(scores):
+    """`match`'s dict of side A's episode scores."""
     s = np.array(scores, np.int64)
     return {"episodes": len(scores), "wins": int((s > 0).sum()), "draws": int((s == 0).sum()),
             "losses": int((s < 0).sum()), "mean_score": float(s.mean()), "max_score": int(s.max()),
@@ -297,9 +539,19 @@ def main(argv=None):
     p.add_argument("--episodes", type=int, default=100)
     p.add_argument("--games", type=int, default=20, help="games played at once")
     p.add_argument("--limit", type=int, default=DEFAULT_LIMIT, help="LimitLengthPlayer's game steps")
-    args = resolve(p.parse_args(argv))
+    p.add_argument("--record", default=None, metavar="DIR",
+                   help="record the match (ba3c_amd.record.record_match): one .npz (and .gif) per "
+                        "episode in DIR")
+    p.add_argument("--scale", type=int, default=3, help="--record: pixel scale of the frames, 1..8")
+    p.add_argument("--every", type=int, default=1, help="--record: keep every N-th decision's frame")
+    p.add_argument("--max_frames", type=int, default=2000, help="--record: frames kept per episode")
+    p.add_argument("--side", default="a", choices=["a", "b"],
+                   help="--record: whose view and whose policy output the frames show")
+    args = resolve(p.parse_args(argv), duel_tool=True)
     if args.environment != GRID_BOXING or args.self_play:
         raise SystemExit("a match is played on -e %s, without --self_play" % GRID_BOXING)
+    if not 1 <= args.scale <= 8 or args.every < 1 or args.max_frames < 0:
+        raise SystemExit("--scale must be in [1, 8], --every >= 1 and --max_frames >= 0")
     if bool(args.load_b) == bool(args.random_b):
         raise SystemExit("pass side B: exactly one of --load_b CHECKPOINT and --random_b")
     if args.episodes < 1 or args.games < 1:
@@ -314,8 +566,20 @@ def main(argv=None):
         args_b = copy.copy(args)
         args_b.load = args.load_b
         side_b = build(args_b)[0].engine
-    out = match(side_a, side_b, args.games, args.episodes, seed=0 if args.seed is None else args.seed,
-                limit=args.limit)
+    how = dict(seed=0 if args.seed is None else args.seed, limit=args.limit, frame_skip=args.frame_skip,
+               sticky=args.sticky, start=start_from_gap(args.duel_start))
+    if args.record:
+        import os
+
+        from .record import record_match
+        traces = record_match(side_a, side_b, args.episodes, args.games, scale=args.scale, every=args.every,
+                              max_frames=args.max_frames, side=args.side, **how)
+        out = match_result([t.score for t in traces])
+        out["files"] = []
+        for i, t in enumerate(traces):
+            out["files"] += t.save(os.path.join(args.record, "match_%03d" % i))
+    else:
+        out = match(side_a, side_b, args.games, args.episodes, **how)
     out = dict(side_a=args.load, side_b=args.load_b or "random", games=args.games, **out)
     print(json.dumps(out), flush=True)
     return out

@@ -4,7 +4,7 @@ its single-node launcher (`python -m ba3c_amd.train`) consume.  Slurm / TF-serve
 flags are accepted and ignored."""
 import argparse
 
-from . import frameskip
+from . import duel, frameskip
 from .boxing import BoxingVec
 from .breakout import BreakoutVec
 
@@ -28,6 +28,14 @@ def frame_skip_arg(s):
     except ValueError:
         raise argparse.ArgumentTypeError("expected K or LO-HI, got %r" % s)
     return lo if "-" not in str(s) else (lo, hi)
+
+
+def duel_start_arg(s):
+    """--duel_start GAP -> (GAP, GAP), --duel_start LO-HI -> (LO, HI); the range is checked by resolve."""
+    try:
+        return duel.parse_gap(s)
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected GAP or LO-HI, got %r" % s)
 
 
 def build_parser():
@@ -78,6 +86,16 @@ def build_parser():
                    help="train -e GridBoxing-v0 by self-play: --simulator_procs players (an even "
                         "number) in --simulator_procs / 2 two-player games (ba3c_amd.duel); "
                         "--nr_eval still plays the scripted opponent")
+    p.add_argument("--duel_frame_skip", type=frame_skip_arg, default=1,
+                   help="--self_play's --frame_skip: game steps per decision of the two-player "
+                        "games, K or LO-HI (--nr_eval then plays the scripted opponent under it too)")
+    p.add_argument("--duel_sticky", type=float, default=0.0,
+                   help="--self_play's --sticky: each side repeats its own previous step's action "
+                        "with this probability")
+    p.add_argument("--duel_start", type=duel_start_arg, default=(38, 38),
+                   help="two-player GridBoxing: the gap in pixels between the boxers of a fresh "
+                        "episode, GAP or LO-HI for a uniform draw per episode; even numbers 8..38 "
+                        "(38: the fixed start; 14 and below: within reach); needs --self_play")
     p.add_argument("--local_time_max", type=int, default=5,
                    help="decisions per rollout segment (train.py:102 LOCAL_TIME_MAX), 1..128")
     p.add_argument("--gamma", type=float, default=0.99,
@@ -106,12 +124,16 @@ def build_parser():
     return p
 
 
-def resolve(args):
+def resolve(args, duel_tool=False):
     """Apply the reference's implicit rules: --use_normal_fc disables replace_with_conv
     (run_job.py:131); --adam_debug sets beta2 := beta1 (train.py:460-461); --use_sync needs
     --ngrads (run_job.py:55-57).  An on-device game (GAMES) needs --channels 1 and --num_actions
     >= its own number of actions; --nr_eval, --frame_skip and --sticky need one of them.
-    --self_play needs GridBoxing, an even --simulator_procs and neither frame skip nor sticky.
+    --self_play needs GridBoxing, an even --simulator_procs and neither --frame_skip nor --sticky:
+    its two-player games take --duel_frame_skip / --duel_sticky, which like --duel_start need
+    --self_play (duel_tool: the match tool, which plays two-player games without it and under
+    --frame_skip / --sticky).  args.play_frame_skip / args.play_sticky are the run's setting
+    either way, for the games and for --nr_eval alike.
     --gae_lambda in [0, 1], --local_time_max in 1..128, --gamma in (0, 1], and the states ring
     they imply at most 16 GiB; they apply to every -e, with and without --self_play."""
     if args.replace_with_conv is None:
@@ -141,7 +163,22 @@ def resolve(args):
         if args.simulator_procs % 2:
             raise SystemExit("--self_play counts players, two per game: --simulator_procs must be even")
         if skip is not None:
-            raise SystemExit("--self_play has no --frame_skip / --sticky")
+            raise SystemExit("--self_play has no --frame_skip / --sticky: its games take "
+                             "--duel_frame_skip / --duel_sticky")
+    try:
+        duel_skip = frameskip.setting(args.duel_frame_skip, args.duel_sticky)
+    except ValueError as e:
+        raise SystemExit("--duel_frame_skip / --duel_sticky: %s" % e)
+    if duel_skip is not None and not args.self_play:
+        raise SystemExit("--duel_frame_skip / --duel_sticky are two-player GridBoxing's: they need --self_play")
+    args.play_frame_skip, args.play_sticky = ((args.duel_frame_skip, args.duel_sticky) if args.self_play
+                                              else (args.frame_skip, args.sticky))
+    try:
+        start = duel.start_from_gap(args.duel_start)
+    except ValueError as e:
+        raise SystemExit("--duel_start: %s" % e)
+    if start is not None and not (args.self_play or duel_tool):
+        raise SystemExit("--duel_start is two-player GridBoxing's: it needs --self_play")
     # written so that a NaN fails either range
     if not 0.0 <= args.gae_lambda <= 1.0:
         raise SystemExit("--gae_lambda %r: lambda must be in [0, 1]" % args.gae_lambda)

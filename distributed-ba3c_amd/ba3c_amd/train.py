@@ -8,7 +8,8 @@ predictor + BatchData, :520-534 — with the synthetic on-device environment, gy
 absent, or with `-e GridBreakout-v0` / `-e GridBoxing-v0` the on-device Breakout / Boxing of
 flags.GAMES (`--frame_skip` / `--sticky`: ALE's frame skip and sticky actions, for training and
 evaluation alike; `--self_play`: two-player GridBoxing, ba3c_amd.duel, every game's two sides
-both played by the learner; `--local_time_max` / `--gamma` / `--gae_lambda`: the rollout length,
+both played by the learner, with `--duel_frame_skip` / `--duel_sticky` per side and `--duel_start`, the gap
+between the boxers of a fresh episode; `--local_time_max` / `--gamma` / `--gae_lambda`: the rollout length,
 discount and GAE lambda of the returns, ba3c_amd.returns) and, for `--nr_eval N`, the Evaluator callback every --steps_per_epoch steps), plus
 the DebugLogCallback metrics channels and PeriodicPerStepCallback(ModelSaver) (:608-630) and
 `--load` (SaverRestore, :706-707).
@@ -162,7 +163,8 @@ def _run(args, rank, world):
     if args.nr_eval and rank == 0:
         from .evaluate import Evaluator
         evaluator = Evaluator(trainer.engine, args.nr_eval, client, seed=1000 + rank,
-                              game=args.environment, frame_skip=args.frame_skip, sticky=args.sticky)
+                              game=args.environment, frame_skip=args.play_frame_skip,
+                              sticky=args.play_sticky)
 
     def on_step(tr):
         metrics(tr)
@@ -188,8 +190,10 @@ def _run(args, rank, world):
         env = None
         if args.self_play:
             # --simulator_procs players in half as many two-player games; both sides learn
-            from .duel import BoxingDuelVec
-            env = BoxingDuelVec(args.simulator_procs // 2, seed=rank, device=trainer.engine.device)
+            from .duel import BoxingDuelDecisionVec, start_from_gap
+            env = BoxingDuelDecisionVec(args.simulator_procs // 2, seed=rank, device=trainer.engine.device,
+                                        frame_skip=args.play_frame_skip, sticky=args.play_sticky,
+                                        start=start_from_gap(args.duel_start))
         elif args.environment in GAMES:
             env = GAMES[args.environment][0](args.simulator_procs, seed=rank,
                                              device=trainer.engine.device,

@@ -122,11 +122,12 @@ def hud_from_policy(probs, actions, value):
     return hud
 
 
-def device_view(vec, fn, palette, scale=1, sel=None, hud=None, n_rows=None):
+def device_view(vec, fn, palette, scale=1, sel=None, hud=None, n_rows=None, rows=None):
     """`BreakoutVec.view` / `BoxingVec.view`: one launch of `fn` (the game's ba3c_*_view) over
     vec.game -> torch.uint8 [n, Hc*scale, 84*scale, 3] on the device.  The palette is uploaded
     by the first call and kept on `vec`; nothing else of `vec` is written.  n_rows: the rows of
-    vec.game where that is not vec.E (BoxingDuelVec: two players per row)."""
+    vec.game where that is not vec.E (BoxingDuelVec: two players per row); rows: a device tensor
+    shaped like vec.game to draw in its place (BoxingDuelVec's mirrored rows)."""
     torch = vec._torch
     S = check_scale(scale)
     if vec._palette is None:
@@ -146,6 +147,6 @@ def device_view(vec, fn, palette, scale=1, sel=None, hud=None, n_rows=None):
     hc = W + (HUD_H if hud is not None else 0)
     out = torch.empty((n, hc * S, W * S, 3), dtype=torch.uint8, device=vec.device)
     ptr = vec._ptr
-    vec._check(fn(vec._stream(), ptr(vec.game), n_rows, ptr(sel), n, ptr(vec._palette), ptr(hud), S,
+    vec._check(fn(vec._stream(), ptr(vec.game if rows is None else rows), n_rows, ptr(sel), n, ptr(vec._palette), ptr(hud), S,
                   ptr(out)))
     return out

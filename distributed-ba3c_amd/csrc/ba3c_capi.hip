@@ -2025,6 +2025,33 @@ int ba3c_boxing_duel_step(void* stream, int32_t* game, const int64_t* action, in
   return BA3C_OK;
 }
 
+// One decision of ba3c_amd/duel.py (decide_numpy) for every game (duel_decide_kernel).
+int ba3c_boxing_duel_decide(void* stream, int32_t* game, int32_t* aux, const int64_t* action, int32_t n_games,
+                            int32_t limit, int32_t skip_lo, int32_t skip_hi, int32_t sticky_q16,
+                            int32_t start_lo, int32_t start_hi, double* reward, uint8_t* over,
+                            int32_t* ep_score, uint8_t* frame, uint8_t* state) {
+  if (!game || !action) return fail(BA3C_ERR_INVALID, "null game / action pointer");
+  if (!aux) return fail(BA3C_ERR_INVALID, "null aux pointer");
+  if (!reward || !over || !ep_score) return fail(BA3C_ERR_INVALID, "null output pointer");
+  if (n_games < 1 || limit < 1) return fail(BA3C_ERR_INVALID, "n_games and limit must be >= 1");
+  if (!check_ptr(game) || (state && !check_ptr(state)) || (reinterpret_cast<uintptr_t>(frame) & 3))
+    return fail(BA3C_ERR_INVALID, "game / state must be 16-byte and frame 4-byte aligned");
+  if (!check_ptr(aux)) return fail(BA3C_ERR_INVALID, "aux must be 16-byte aligned");
+  if (skip_lo < 1 || skip_hi < skip_lo || skip_hi > 16)
+    return fail(BA3C_ERR_INVALID, "frame skip must satisfy 1 <= skip_lo <= skip_hi <= 16");
+  if (sticky_q16 < 0 || sticky_q16 > 65536)
+    return fail(BA3C_ERR_INVALID, "sticky_q16 must be in [0, 65536]");
+  if (start_lo < 4 || start_hi < start_lo || start_hi > 19)
+    return fail(BA3C_ERR_INVALID, "start half-gap must satisfy 4 <= start_lo <= start_hi <= 19");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DuelArgs a{game, action, n_games, limit, reward, over, ep_score, frame, state};
+  DuelDecideArgs k{aux, skip_lo, (uint32_t)(skip_hi - skip_lo + 1), (uint32_t)sticky_q16,
+                   start_lo, (uint32_t)(start_hi - start_lo + 1)};
+  hipLaunchKernelGGL(duel_decide_kernel, dim3(n_games), dim3(256), 0, s, a, k);
+  HIP_TRY(hipGetLastError());
+  return BA3C_OK;
+}
+
 int ba3c_boxing_duel_render(void* stream, const int32_t* game, int32_t n_games, uint8_t* frame,
                             uint8_t* state) {
   if (!game) return fail(BA3C_ERR_INVALID, "null game pointer");

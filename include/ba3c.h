@@ -433,6 +433,37 @@ int ba3c_boxing_duel_step(void* stream, int32_t* game, const int64_t* action, in
 int ba3c_boxing_duel_render(void* stream, const int32_t* game, int32_t n_games, uint8_t* frame,
                             uint8_t* state);
 
+/* One DECISION of every two-player game per call: frame skip and sticky actions per side, and
+ * episodes that start from a drawn row.  ba3c_amd/duel.py (decide_numpy, "Drawn starts") states
+ * the semantics and is the oracle.  aux[e] = [rng_k, rng_a, rng_b, prev_a, prev_b, 0, 0, 0]
+ * (eight int32, 16-byte aligned rows): three LCG streams (the games' multiplier and increment),
+ * one for the skip and one per side for its sticky draws, and each side's last effective action.
+ * Per game, in this order:
+ *   a, b = action[e], action[n_games + e], each 0 unless in [0, 32)
+ *   rng_k = lcg(rng_k); k = skip_lo + (rng_k >> 16) % (skip_hi - skip_lo + 1)
+ *   k times: rng_a = lcg(rng_a); prev_a = prev_a if ((rng_a >> 8) & 0xFFFF) < sticky_q16 else a;
+ *            rng_b, prev_b likewise from b; one step of ba3c_boxing_duel_step's rules under
+ *            (prev_a, prev_b); on over: prev_a = prev_b = 0, the remaining sub-steps are dropped
+ * A fresh episode is GridBoxing's (20, 42, 58, 42) when start_lo == start_hi == 19, and draws
+ * nothing; otherwise it is drawn from the ROW's rng, which no other rule touches:
+ *   rng = lcg(rng); r = rng >> 16; h = start_lo + r % (start_hi - start_lo + 1);
+ *   y = 14 + 2 * ((r >> 8) % 29); (ax, ay, bx, by) = (39 - h, y, 39 + h, y)
+ * a row that is its own mirror image, so neither side is favoured.  reward[e] is the sum of side
+ * A's rewards over the executed sub-steps and reward[n_games + e] its negative; over / ep_score
+ * report the episode that ended; frame / state receive ONE frame per player, the one after the
+ * last executed sub-step, as ba3c_boxing_duel_step writes them.  `limit` counts game steps.
+ * With skip 1-1, sticky_q16 0 and start 19-19 a decision is exactly ba3c_boxing_duel_step.
+ *
+ * It refuses what ba3c_boxing_duel_step refuses, a null or not 16-byte aligned aux, a skip
+ * outside 1 <= skip_lo <= skip_hi <= 16, a sticky_q16 outside [0, 65536] and a start outside
+ * 4 <= start_lo <= start_hi <= 19, all on the host before touching the device; it never
+ * synchronises and never allocates.  One launch, one 256-thread workgroup per game, the k steps
+ * in registers. */
+int ba3c_boxing_duel_decide(void* stream, int32_t* game, int32_t* aux, const int64_t* action,
+                            int32_t n_games, int32_t limit, int32_t skip_lo, int32_t skip_hi,
+                            int32_t sticky_q16, int32_t start_lo, int32_t start_hi, double* reward,
+                            uint8_t* over, int32_t* ep_score, uint8_t* frame, uint8_t* state);
+
 /* ---- Frame skip and sticky actions for the on-device games ------------------------------- */
 
 /* One DECISION per call instead of one game step: ALE's `-v0` behaviour of a frame skip drawn

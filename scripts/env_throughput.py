@@ -14,6 +14,11 @@ the fused step in the same run, and its store rate (Hc*S * 252*S bytes per simul
 With --duel also two-player GridBoxing (`BoxingDuelVec.step_into`, ba3c_amd.duel) at G = E / 2
 games next to `BoxingVec.step_into` at E simulators (by default G = 4096 against E = 8192 and
 G = 32 against E = 64: the same players and bytes), timed alternately in the same run.
+With --duel the decision launch (`ba3c_boxing_duel_decide`: frame skip, sticky actions per side, drawn
+starts) is timed next to `ba3c_boxing_duel_step` too, alternating in the same run: at (1, 1, 0) with
+the fixed start against one step, one k = 4 launch against four back-to-back one-step launches,
+and the setting of --frame_skip / --sticky / --duel_start (default 2-4, 0.25, 8-14) for the
+record; --duel_only skips the single-player tables.
 With --returns also `ba3c_lambda_returns` (lambda = 0.95 and 1) next to `ba3c_nstep_returns` on
 identical full memories at (simulators, slots) = (100, 6), (1024, 33), (4096, 129), the median
 of 20 event-bracketed batches of 20 launches each, alternating; and ms per
@@ -23,7 +28,7 @@ Prints one JSON line.
 
     python scripts/env_throughput.py [--game boxing] [--envs 8192 64] [--iters 200] [--random 20]
                                      [--frame_skip 2-4] [--sticky 0.25] [--view 1 3] [--duel]
-                                     [--returns]
+                                     [--duel_start 8-14] [--duel_only] [--returns]
 """
 import argparse
 import json
@@ -77,6 +82,46 @@ def duel_table(envs, iters, repeats):
                        "duel_GBps": round(traffic / min(t_duel) / 1e3, 1),
                        "boxing_GBps": round(traffic / min(t_solo) / 1e3, 1),
                        "duel_over_boxing": round(min(t_duel) / min(t_solo), 3)}
+    return out
+
+
+def duel_decision_table(envs, iters, repeats, skip, start):
+    """--duel: BoxingDuelDecisionVec on the decision launch next to the one-step launch at the
+    same G, alternating.  skip (lo, hi, q16) and start (h_lo, h_hi): the setting timed for the record."""
+    from ba3c_amd.duel import FIXED_START, BoxingDuelDecisionVec, BoxingDuelVec
+    from ba3c_amd.rollout import FrameHistory
+    out = {}
+
+    def vec(G, skip, start):
+        v = BoxingDuelDecisionVec(G, seed=0, frame_skip=2)    # on the decision launch, then the setting
+        v.skip, v.start = skip, start
+        h = FrameHistory(2 * G, 4, 1)
+        v.reset_history(h)
+        return v, h
+    for E in envs:
+        G = E // 2
+        g = torch.Generator(device="cuda").manual_seed(0)
+        actions = torch.randint(0, 18, (2 * G,), generator=g, device="cuda")
+        step, hist_s = BoxingDuelVec(G, seed=0), FrameHistory(2 * G, 4, 1)
+        step.reset_history(hist_s)
+        legs = {"decide_1_1_0": vec(G, (1, 1, 0), FIXED_START), "decide_4_4_0": vec(G, (4, 4, 0), FIXED_START),
+                "decide_setting": vec(G, skip, start)}
+
+        def four():
+            for _ in range(4):
+                step.step_into(actions, hist_s)
+        t = {k: [] for k in list(legs) + ["step", "four_steps"]}
+        for _ in range(repeats):
+            t["step"].append(timed(lambda: step.step_into(actions, hist_s), iters))
+            for k, (v, h) in legs.items():
+                t[k].append(timed(lambda: v.step_into(actions, h), iters))
+            t["four_steps"].append(timed(four, iters))
+        row = {k + "_us": [round(x, 2) for x in v] for k, v in t.items()}
+        row.update(setting={"skip": list(skip), "start": list(start)},
+                   decide_over_step=round(min(t["decide_1_1_0"]) / min(t["step"]), 3),
+                   k4_over_four_steps=round(min(t["decide_4_4_0"]) / min(t["four_steps"]), 3),
+                   setting_over_step=round(min(t["decide_setting"]) / min(t["step"]), 3))
+        out[str(G)] = row
     return out
 
 
@@ -191,6 +236,8 @@ def main(argv=None):
     ap.add_argument("--frame_skip", default="1")
     ap.add_argument("--sticky", type=float, default=0.0)
     ap.add_argument("--view", type=int, nargs="+", default=[])
+    ap.add_argument("--duel_start", default=None, help="--duel: the start gap of the setting timed")
+    ap.add_argument("--duel_only", action="store_true", help="--duel: skip the single-player tables")
     args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "needs the GPU: a CPU run measures nothing"
     from ba3c_amd.actor_learner import SyntheticAtari
@@ -224,7 +271,7 @@ def main(argv=None):
         out["fill_GBps"] = round(fill.numel() / us / 1e3, 1)
         del fill
 
-    for E in args.envs:
+    for E in ([] if args.duel and args.duel_only else args.envs):
         g = torch.Generator(device="cuda").manual_seed(0)
         actions = torch.randint(0, A, (E,), generator=g, device="cuda")
         env, hist = Vec(E, seed=0), FrameHistory(E, 4, 1)
@@ -281,7 +328,11 @@ def main(argv=None):
             out["envs"][str(E)]["breakout_fused_step_into_us"] = [round(v, 2) for v in brk]
             out["envs"][str(E)]["fused_over_breakout"] = round(min(fused) / min(brk), 3)
     if args.duel:
+        from ba3c_amd.duel import FIXED_START, start_from_gap
         out["duel"] = duel_table(args.envs, args.iters, args.repeats)
+        start = start_from_gap(args.duel_start or "8-14") or FIXED_START
+        out["duel_decision"] = duel_decision_table(args.envs, args.iters, args.repeats,
+                                                   skip or (2, 4, 16384), start)
     if args.returns:
         out["returns"] = returns_table(args.repeats)
         out["iterate"] = iterate_table([(5, 1.0), (20, 0.95), (5, 1.0), (20, 0.95)])
