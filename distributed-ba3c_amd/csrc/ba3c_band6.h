@@ -488,13 +488,24 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) c
 // bands, 50 % for conv1 dgrad's 4-row ones).  Per band the LDS image and the MFMA stream are
 // the one-band kernel's, so the outputs are bit-identical.  (Round 2 ran the copy and the new-row
 // stores with no barrier in between: a cross-wave write-after-read race in LDS; fixed in r03.)
-template <class L, bool PRE_ = L::G::SRC == 1>
+// FRESH: the staged map's per-image maxima were published earlier in this same launch (the
+// fused conv0 + conv1 forward, ba3c_conv0.hip), so they are read with agent-scope loads: a
+// plain load may be served by the scalar cache or L1 from a line fetched for a neighbouring
+// image's slot before this image's maximum existed.
+template <class L, bool PRE_ = L::G::SRC == 1, bool FRESH_ = false>
 __device__ __forceinline__ void band6r_body(const Band6Args& a, int bx, int gx, char* lds) {
   static_assert(L::NPH == 1 && L::G::SROWS > L::G::RB, "ring walk: unphased layouts with a halo");
   using O = Band6Ops<L>;
   using G = typename L::G;
   constexpr int HALO = G::SROWS - G::RB;                    // KH - 1 rows carried over
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int tid0 = threadIdx.x;
+  if constexpr (FRESH_) {
+    // (that launch may call the body in a loop: the per-thread staging offsets are recomputed
+    // per call, not hoisted out of the caller's loop into registers that spill)
+    asm volatile("" : "+v"(tid0));
+    __builtin_assume(tid0 >= 0 && tid0 < 256);
+  }
+  const int tid = tid0, lane = tid & 63, wave = tid >> 6;
   const float us2 = L::NS == 2 ? exp2i(-a.wexp[0]) : 1.0f;
   const int ipw = (a.batch + gx - 1) / gx;
   const int img0 = bx * ipw, img1 = min(a.batch, img0 + ipw);
@@ -507,7 +518,8 @@ __device__ __forceinline__ void band6r_body(const Band6Args& a, int bx, int gx, 
   uint32_t pc[PRE ? NNEW : 1];
   unsigned long long pos = 0;
   for (int img = img0; img < img1; ++img) {
-    const int ka = L::NS == 2 ? amax_exp(a.amax_in[1 + img]) : 0;   // per-image operand scale
+    // per-image operand scale
+    const int ka = L::NS == 2 ? amax_exp(FRESH_ ? ld_agent_u32(a.amax_in + 1 + img) : a.amax_in[1 + img]) : 0;
     const float asc = exp2i(ka), us1 = exp2i(-ka);
     float omax = 0.f;
     for (int bi = 0; bi < G::NBANDS; ++bi) {
@@ -557,6 +569,12 @@ __device__ __forceinline__ void band6r_body(const Band6Args& a, int bx, int gx, 
   }
   if (G::POOL && a.relu_count) relu_count_add_uniform(a.relu_count, pos, lane);
 }
+
+// conv1's forward (40x40x32 -> 36x36x32, pooled to 18x18; 6-row bands): the geometry and the
+// scaled-fp16 layout of its band kernels, shared by ba3c_capi.hip and the fused conv0 + conv1
+// forward launch in ba3c_conv0.hip
+using GConv1F = BandGeom<40, 40, 32, 32, 5, 5, 6, true, 0, 4>;
+using Conv1FLay = Band6<GConv1F, 160, 128, 7, 0, 2, true>;
 
 // zero-padded un-pooled dY staged from the POOLED map (ring walk of an input-gradient layout,
 // scaled fp16 family).  Band6Ops::store1 builds every staged float4 from the pooled float4 of

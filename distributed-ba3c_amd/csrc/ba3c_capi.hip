@@ -119,6 +119,10 @@ struct ba3c_handle {
   // conv1 fwd / dgrad (multi-band layouts) as ring-walk persistent kernels at batches that
   // give every workgroup whole images (conv_band6r_kernel; BA3C_RING=0: one band per workgroup)
   bool ring = true;
+  // at those batches (C == 4) conv0's forward and conv1's ring walk run as one persistent
+  // launch, each workgroup taking its own images through both layers (fwd01_kernel,
+  // ba3c_conv0.hip; BA3C_FWD01=0: the two launches)
+  bool fwd01 = true;
   int cus = 256;      // compute units of the device (persistent grids)
   bool g6 = true;     // implicit-GEMM launches (conv3, fc1, heads; C=12 conv0) on bf16x6 split
                       // MFMA (ba3c_gemm6.h; off with BA3C_GENERIC=1: fp32 MFMA)
@@ -200,7 +204,7 @@ namespace {
 // ---- workspace layout -----------------------------------------------------------------
 // band-conv geometries (ba3c_conv.h): forward conv1/conv2 with pooling, and the input
 // gradients of conv1/conv2 as VALID convs over the 4-padded un-pooled output gradient
-using GConv1F = BandGeom<40, 40, 32, 32, 5, 5, 6, true, 0, 4>;
+// (conv1's forward geometry GConv1F and its layout Conv1FLay: ba3c_band6.h)
 using GConv2F = BandGeom<18, 18, 32, 64, 5, 5, 14, true, 0, 4>;
 using GConv1D = BandGeom<44, 44, 32, 32, 5, 5, 4, false, 1, 8, 4, 4, 18, 18, 36, 36>;
 using GConv2D = BandGeom<22, 22, 64, 32, 5, 5, 6, false, 1, 8, 4, 4, 7, 7, 14, 14>;
@@ -222,7 +226,7 @@ using GConv2FS = BandGeom<18, 18, 32, 64, 5, 5, 2, true, 0, 4>;
 using GConv2DS = BandGeom<22, 22, 64, 32, 5, 5, 3, false, 1, 8, 4, 4, 7, 7, 14, 14>;
 // split-kernel layouts (scaled fp16 hi/lo planes)
 struct Lay {
-  using C1F = Band6<GConv1F, 160, 128, 7, 0, 2, true>;
+  using C1F = Conv1FLay;
   using C2F = Band6<GConv2F, 160, 64, 7, 0, 2>;   // (double-buffered: 256 VGPRs, neutral, r04)
   using C1D = Band6<GConv1D, 160, 0, 5, 0, 2, true, true>;   // 4x4 tiles: RP = 128 mod 256 B
   using C2D = Band6<GConv2DW, 160, 128, 11, 32, 2, false, false, true>;   // padding skip, no A double buffer
@@ -749,8 +753,24 @@ int run_forward(ba3c_handle* h, hipStream_t s, const float* prm, const uint8_t* 
   } else {
     // small batches: weight prep beside conv0's forward (one launch fewer on the critical path)
     const bool mj = h->multi && B <= OVERLAP_B && CH == 4;
+    // batches at which conv1's forward runs as the ring walk (launch_band6): conv0's and
+    // conv1's forward as ONE persistent launch, each workgroup taking its own images through
+    // both layers (fwd01_kernel, ba3c_conv0.hip; BA3C_FWD01=0: two launches)
+    const int pr = 2 * h->cus;
+    const bool f01 = CH == 4 && !mj && h->fwd01 && h->ring && B >= pr && (B % pr == 0 || B >= 8 * pr);
     if (mj) {
       CHECK(launch_prep_conv0_multi(h, s, prm, state, B, w, train));
+    } else if (f01) {
+      CHECK(launch_wprep(h, s, prm, w, train));
+      const Conv0SArgs a0{state, reinterpret_cast<const uint4*>(w.wt + WT_C0S), w.p0, c0, rc, B,
+                          w.wexp + WX_CONV0, w.am(AM_P0, h)};
+      const Band6Args a1 = band6_args<typename LY::C1F>(h, BandArgs{w.p0, nullptr, nullptr, w.p1, c1, rc, B}, w,
+                                                        WT_C1F, io1);
+      {
+        ProbeScope ps(h, s, BA3C_K_CONV0_FWD);
+        HIP_TRY(launch_fwd01(pr, s, a0, a1));
+      }
+      h->merged[BA3C_K_CONV0_FWD] |= 1u << BA3C_K_CONV1_FWD;
     } else {
       CHECK(launch_wprep(h, s, prm, w, train));
       if constexpr (CH == 4) {
@@ -762,8 +782,9 @@ int run_forward(ba3c_handle* h, hipStream_t s, const float* prm, const uint8_t* 
         CHECK((launch_gemm<128, 32, 4, 1>(h, s, BA3C_K_CONV0_FWD, cv0, 1)));
       }
     }
-    CHECK((launch_band6<typename LY::C1F>(h, s, BA3C_K_CONV1_FWD, BandArgs{w.p0, nullptr, nullptr, w.p1, c1, rc, B},
-                                          w, WT_C1F, io1, true)));
+    if (!f01)
+      CHECK((launch_band6<typename LY::C1F>(h, s, BA3C_K_CONV1_FWD, BandArgs{w.p0, nullptr, nullptr, w.p1, c1, rc, B},
+                                            w, WT_C1F, io1, true)));
     const BandArgs a2{w.p1, nullptr, nullptr, w.p2, c2, rc, B};
     if (B <= SMALL_B)
       CHECK(launch_band6<typename LY::C2FS>(h, s, BA3C_K_CONV2_FWD, a2, w, WT_C2F, io2));
@@ -1387,6 +1408,7 @@ int ba3c_create(const ba3c_config* cfg, ba3c_handle** out) {
       {"BA3C_RING", "01", 1, [](ba3c_handle* h, int v) { h->ring = v != 0; }},
       {"BA3C_CHAIN", "01", 1, [](ba3c_handle* h, int v) { h->chain_on = v != 0; }},
       {"BA3C_C3W_RIDE", "012", 0, [](ba3c_handle* h, int v) { h->c3ride = v; }},
+      {"BA3C_FWD01", "01", 1, [](ba3c_handle* h, int v) { h->fwd01 = v != 0; }},
   };
   for (Switch& k : switches) {
     const char* e = getenv(k.name);

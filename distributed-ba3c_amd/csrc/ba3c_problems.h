@@ -57,6 +57,9 @@ __device__ __forceinline__ void st_agent_u32(uint32_t* p, uint32_t v) {
 __device__ __forceinline__ void st_agent_u64(unsigned long long* p, unsigned long long v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+__device__ __forceinline__ uint32_t ld_agent_u32(const uint32_t* p) {
+  return __hip_atomic_load(const_cast<uint32_t*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 
 // One wave waits until a chained launch's signal count reaches `need` (bounded: gives up with
 // bit 0 of *err set rather than hang the device).

@@ -291,7 +291,11 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* base) {
 
 // bx / gx: first band and persistent stride (blockIdx.x / gridDim.x of a plain launch);
 // lds: conv0s_fwd_lds_bytes() bytes
-template <bool TRAIN>
+// REENTER: the caller runs the body in a loop with other work in between (the fused conv0 + conv1
+// forward): the thread index goes through an empty asm, so the per-thread staging offsets are
+// recomputed per call instead of being hoisted out of that loop into registers that stay live
+// (and spill) through the other work
+template <bool TRAIN, bool REENTER = false>
 __device__ __forceinline__ void conv0s_fwd_body_t(const Conv0SArgs& a, int bx, int gx, char* lds);
 
 __device__ __forceinline__ void conv0s_fwd_body(const Conv0SArgs& a, int bx, int gx, char* lds) {
@@ -300,12 +304,17 @@ __device__ __forceinline__ void conv0s_fwd_body(const Conv0SArgs& a, int bx, int
   else conv0s_fwd_body_t<false>(a, bx, gx, lds);
 }
 
-template <bool TRAIN>
+template <bool TRAIN, bool REENTER>
 __device__ __forceinline__ void conv0s_fwd_body_t(const Conv0SArgs& a, int bx, int gx, char* lds) {
   using G = Conv0S;
   using SP = SplitP<2>;
+  int tid0 = threadIdx.x;
+  if constexpr (REENTER) {
+    asm volatile("" : "+v"(tid0));
+    __builtin_assume(tid0 >= 0 && tid0 < 256);
+  }
   // wave index in an SGPR: the wave's LDS areas and output rows are scalar arithmetic
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int tid = tid0, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nbands = a.batch * G::NBANDS;
 
   // ---- rows [y0, y0 + SROWS) of a band: one thread per 16-byte ENTRY (r, x) = [pixel (r, x)

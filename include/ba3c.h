@@ -285,7 +285,18 @@ int ba3c_kernel_family(const ba3c_handle* h, int32_t kernel_id);
 /* Kernels that ran inside kernel `kernel_id`'s launch in the last training pass (multi-job
  * launches: the probe of `kernel_id` brackets them too, and they record no launch of their own),
  * as a bitmask of kernel ids; 0 when the launch ran only that kernel, -1 on a bad id.  For
- * roofline accounting only (no reference counterpart). */
+ * roofline accounting only (no reference counterpart).
+ *
+ * One forward launch merges kernels as well, in ba3c_train_grads and ba3c_forward alike: with
+ * channels == 4, at the batches where conv1's forward runs as the ring walk (batch >= 2 x CUs
+ * and (batch % (2 x CUs) == 0 or batch >= 16 x CUs)), conv0's and conv1's forward are ONE
+ * persistent launch of 2 x CUs workgroups.  Each workgroup takes its own contiguous images
+ * through conv0 and then conv1, image by image, and waits for no other workgroup; the results
+ * are bit for bit those of the two launches.  It is timed under BA3C_K_CONV0_FWD, whose mask
+ * then holds BA3C_K_CONV1_FWD's bit (after ba3c_forward too), and BA3C_K_CONV1_FWD records no
+ * launch.  BA3C_FWD01=0 in the environment of ba3c_create keeps the two launches (any value but
+ * 0 or 1 is rejected, like the other launch-structure switches); every other batch,
+ * BA3C_RING=0 and BA3C_GENERIC=1 run them as before. */
 int ba3c_kernel_merged(const ba3c_handle* h, int32_t kernel_id);
 
 /* ---- data formats either side of the path ---------------- */
