@@ -207,7 +207,7 @@ class Ba3cEngine(object):
 
     def set_phase2_event(self, event):
         """Record `event` (a hipevent.HipEvent, or None) in every later phase-2 pass after conv3's
-        input-gradient launch, and its weight gradient's unless BA3C_C3W_RIDE is set."""
+        input- and weight-gradient launches."""
         _lib.check(self.lib.ba3c_set_phase2_event(self.h, event._ev if event is not None else None))
 
     def clip_grads(self, grads=None):

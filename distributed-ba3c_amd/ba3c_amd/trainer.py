@@ -181,8 +181,8 @@ class Ba3cTrainer(object):
         tl = self.timeline.new_step() if self.timeline is not None else None
         mark = (lambda k: tl[k].record()) if tl is not None else (lambda k: None)
         if self._mid is None and eng.grads.is_cuda:
-            # recorded by every phase-2 pass after conv3's input-gradient launch, and its weight
-            # gradient's unless BA3C_C3W_RIDE is set (ba3c_set_phase2_event)
+            # recorded by every phase-2 pass after conv3's input- and weight-gradient launches
+            # (ba3c_set_phase2_event)
             self._mid = hipevent.HipEvent(hipevent.HIP_EVENT_DISABLE_TIMING
                                           | hipevent.HIP_EVENT_RELEASE_TO_DEVICE)
             eng.set_phase2_event(self._mid)

@@ -15,6 +15,7 @@
 #include <cstring>
 #include <optional>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/ba3c.h"
@@ -28,6 +29,7 @@
 #include "ba3c_gemm6.h"
 #include "ba3c_launch.h"
 #include "ba3c_multi.h"
+#include "ba3c_plan.h"
 #include "ba3c_problems.h"
 #include "ba3c_rollout.h"
 #include "ba3c_small.h"
@@ -100,70 +102,29 @@ struct ba3c_handle {
   int idx_piW, idx_pib, idx_vW, idx_vb;
   int per, wstride;
   TensorTable table;
-  // split-MFMA kernels (band convolutions, conv0, weight gradients, the bf16x6 GEMM engine);
-  // BA3C_GENERIC=1: every convolution and GEMM on the fp32-MFMA GEMM engine instead (a
-  // parity configuration with exact fp32 products)
+  Switches sw;        // the launch-structure switches (ba3c_plan.h), fixed at create; device_errors
+                      // may clear sw.chain
+  // !sw.generic: split-MFMA kernels (band convolutions, conv0, weight gradients, the bf16x6 GEMM
+  // engine); BA3C_GENERIC=1: every convolution and GEMM on the fp32-MFMA GEMM engine instead
   bool band = true;
-  // large batches: conv1's weight gradient shares a launch with (2, default) conv0's weight
-  // gradient, (1) conv1's input gradient, or (0) runs alone (BA3C_C1PAIR)
-  int c1pair = 2;
   uint32_t merged[BA3C_NUM_KERNELS] = {};   // ba3c_kernel_merged, per training pass
-  // large-batch (B > OVERLAP_B) scalar reduction deferred from run_heads onto conv3's
-  // input-gradient launch as one extra workgroup (default; also across the phase-1/phase-2
-  // split of the N>1 step); when no launch takes it, finish() launches it at the end of phase
-  // 0 or phase 2.  BA3C_SCALARS_RIDE=0: its own launch after the heads.
-  // r04 same-box A/B: step 1.954 -> 1.935 ms
-  bool scalars_ride = true;
+  // the large-batch scalar reduction when run_heads deferred it (sw.scalars_ride) onto conv3's
+  // input-gradient launch (also across the phase-1/phase-2 split of the N>1 step); when no
+  // launch takes it, finish() launches it at the end of phase 0 or phase 2
   bool pend_scalars = false;
   ScalarsJob::Args scalars_args{};
-  // conv1 fwd / dgrad (multi-band layouts) as ring-walk persistent kernels at batches that
-  // give every workgroup whole images (conv_band6r_kernel; BA3C_RING=0: one band per workgroup)
-  bool ring = true;
-  // at those batches (C == 4) conv0's forward and conv1's ring walk run as one persistent
-  // launch, each workgroup taking its own images through both layers (fwd01_kernel,
-  // ba3c_conv0.hip; BA3C_FWD01=0: the two launches)
-  bool fwd01 = true;
   int cus = 256;      // compute units of the device (persistent grids)
   bool g6 = true;     // implicit-GEMM launches (conv3, fc1, heads; C=12 conv0) on bf16x6 split
                       // MFMA (ba3c_gemm6.h; off with BA3C_GENERIC=1: fp32 MFMA)
-  // backward weight gradients on a side stream (created on the first training call that is
-  // not being captured): 0 never (BA3C_OVERLAP=0), 1 always (BA3C_OVERLAP=1), 2 (default) for
-  // batches <= OVERLAP_B only.  Large batches: r01t/u measured +0.5% step throughput (561k vs
-  // 557k samples/s) because conv1's dgrad and wgrad kernels each fill the chip, and concurrent
-  // kernels make the per-kernel durations (roofline, rocprof) meaningless.  Small batches: each
-  // backward kernel is a few latency-bound workgroups, so the weight-gradient chain runs in
-  // the input-gradient chain's shadow.
-  int overlap = 2;
-  // batches <= OVERLAP_B on the split path: each layer's input- and weight-gradient kernels
-  // run as ONE multi-job launch (ba3c_multi.h) on the main stream instead of on two streams
-  // joined by events (r02k trace at B=32: 6-11 us of idle queue per fork / join).
-  // BA3C_MULTI=0: side stream as before.
-  bool multi = true;
-  // Backward pairs run as multi-job launches at batches > OVERLAP_B too (BA3C_MULTI_BIG bits:
-  // 1 fc1 + heads — r02x at B=2048, 84 -> 64 us for the three products; 2 conv2 — r02aa, 300 ->
-  // 292 us).  conv3's pair measured slower there (116 -> 134 us), and conv1's products stay
-  // on their own (the dominant kernel's roofline probe needs conv1 dgrad alone).
-  int multi_big = 3;
-  // fused-clip optimizer applies as one clip_update_kernel launch (ba3c_small.h) when the chunk
-  // count fits one workgroup per CU; its grid-barrier words live in `bar` (device, zeroed at
-  // create).  BA3C_FUSED_UPDATE=0: sumsq_kernel + update_kernel.
-  bool fused_update = true;
   // clip_update_kernel's tagged partials (nchunks words) + error flag: device, zeroed at create;
   // clip_range_kernel's (a generation space of their own) follow them
   unsigned long long* utag = nullptr;
   unsigned long long* ctag = nullptr;
   // chained multi-job launches (ba3c_multi.h: an in-launch dependency instead of a kernel
   // boundary): CHAIN_SITES x 4 words + an error word after the tags (null: no device memory,
-  // unchained launches).  BA3C_CHAIN=0: unchained.
-  bool chain_on = true;
+  // unchained launches)
   unsigned* chain = nullptr;
   unsigned* spread = nullptr;   // CHAIN_SPREAD counters, CHAIN_STRIDE words apart (64-byte aligned)
-  // BA3C_C3W_RIDE (large batches, conv2's gradients in one multi-job launch): conv3's weight
-  // gradient as a third job of that launch instead of a launch of its own (two 256-thread
-  // workgroups per slab, bit-identical slabs); 1: after conv2's jobs, 2: before them, 0: own
-  // launch (default: r06n, conv2's launch grows by conv3's whole 22 us either way, since both
-  // fill every workgroup slot; the step gains 0-3 us, within box noise)
-  int c3ride = 0;
   // ba3c_train_grads_phase(phase 3): the pass's weight-gradient reduction is left pending and
   // the next fused-clip apply on the handle runs it as the signalling job of a chained launch
   // (reduce -> clip + update, one launch fewer); any other entry point launches it first
@@ -178,13 +139,13 @@ struct ba3c_handle {
   bool held = false;
   hipStream_t held_stream = nullptr;
   ReduceJobs held_jobs{};
-  // recorded on the pass's stream after conv3's input-gradient launch of every phase-2 pass,
-  // and its weight gradient's unless BA3C_C3W_RIDE is set (ba3c_set_phase2_event; null: none)
+  // recorded on the pass's stream after conv3's input- and weight-gradient launches of every
+  // phase-2 pass (ba3c_set_phase2_event; null: none)
   hipEvent_t ev_mid = nullptr;
   hipStream_t side = nullptr;
   hipEvent_t ev_fork[4] = {}, ev_join = nullptr;
-  // weight-gradient reductions of the running backward pass, launched together at its end
-  bool defer_reduce = false;
+  // weight-gradient reductions of the backward pass (BackwardPass), launched together at its
+  // end, or kept for a pending (phase 3) launch
   ReduceJobs rjobs{};
   // RCCL communicator of the C-ABI gradient exchange (ba3c_comm_init; null: none)
   ncclComm_t comm = nullptr;
@@ -219,8 +180,6 @@ using GConv2D = BandGeom<22, 22, 64, 32, 5, 5, 6, false, 1, 8, 4, 4, 7, 7, 14, 1
 //       whole-map kernels — at B=32 those are 32 workgroups on 256 CUs, one latency-bound
 //       wave of work.  Every output's K order (phase, tap, channel chunk, product) is the same
 //       in both geometries, so results are bit-identical across the switch.
-constexpr int SMALL_B = 128;
-constexpr int OVERLAP_B = 128;   // default side-stream weight gradients up to this batch
 using GConv2DW = BandGeom<22, 22, 64, 32, 5, 5, 18, false, 1, 8, 4, 4, 7, 7, 14, 14>;
 using GConv2FS = BandGeom<18, 18, 32, 64, 5, 5, 2, true, 0, 4>;
 using GConv2DS = BandGeom<22, 22, 64, 32, 5, 5, 3, false, 1, 8, 4, 4, 7, 7, 14, 14>;
@@ -236,29 +195,9 @@ struct Lay {
   using W2 = Wg6Geom<18, 18, 32, 64, 14, 16, 32, 96, 160, 2>;
   using W1W = Wg6WGeom<40, 40, 32, 32, 4, 160, 160>;   // conv1, B >= W6W_MIN_B (66.2 KB LDS)
 };
-// persistent grid bound of conv1's partial slabs
-constexpr int WG_P1 = 512;
-constexpr int W6_P1 = 256, W6_P2 = 128;   // x (c-groups x o-groups) = 512 workgroups
-// conv1 weight-gradient workgroups: ~4 bands each, at least 64 (at B=32 one band per
-// workgroup made 256 partial slabs of 100 KB — 26 MB written and read back by the reduction
-// for 3.3 MB of input).  A function of B alone, so every launch path sums the same slabs.
-#ifndef BA3C_C1W_BPW
-#define BA3C_C1W_BPW 3        // conv1 weight-gradient bands per workgroup below the ring sizes (r03: 4 -> 3, B=32 0.1966 -> 0.1925 ms)
-#endif
-inline int conv1_wgrad_p(int B) { return std::max(64, std::min(W6_P1, B * 9 / BA3C_C1W_BPW)); }
-// conv1 weight gradient with all 32 input channels per workgroup (wgrad6w_kernel) from this
-// batch on: whole images per workgroup, two workgroups per CU, one slab each
-constexpr int W6W_MIN_B = 512, W6W_P = 512;
-static_assert(W6W_P <= WG_P1, "conv1 partial slabs: the allocation covers WG_P1 slabs");
-// its slab count: one per CU (whole images, B / CUs each) where the input gradient can run beside
-// it in one launch (conv1_pair), else up to W6W_P; a function of B and the CU count alone, so
-// the paired and the separate launches sum the same slabs bit for bit
-inline bool conv1_pair_geometry(int B, int cus) { return B >= 2 * W6W_MIN_B && B % cus == 0 && cus <= WG_P1; }
-inline int conv1_w6w_p(int B, int cus) { return conv1_pair_geometry(B, cus) ? cus : std::min(W6W_P, B); }
-constexpr int FW_P0S = 512;   // conv0s_fwd_kernel: persistent, two workgroups per CU
-constexpr int C3W_P = 256;    // conv3_wgrad_kernel: one 512-thread workgroup (and slab) per CU, at most
-inline int conv3_wgrad_p(int B, int cus) { return std::min(B, std::min(C3W_P, cus)); }
-constexpr int WG_P0S = 512;   // conv0s_wgrad_kernel: 52 KB LDS, two workgroups per CU
+// the layout numbers of the slab-count functions (ba3c_plan.h)
+static_assert(Lay::W1::NBANDS == W1_NBANDS && Conv0S::NBANDS == C0F_NBANDS && Conv0W<2>::NBANDS == C0W_NBANDS,
+              "ba3c_plan.h: bands per image");
 constexpr int WT_C1F = 0, WT_C2F = WT_C1F + 800 * 32, WT_C3F = WT_C2F + 800 * 64,
               WT_C1D = WT_C3F + 576 * 64, WT_C2D = WT_C1D + 800 * 32, WT_C3D = WT_C2D + 1600 * 32,
               WT_C0F = WT_C3D + 576 * 64,
@@ -459,23 +398,25 @@ int launch_gemm(ba3c_handle* h, hipStream_t s, int kid, const P& p, int splits) 
   return BA3C_OK;
 }
 
-int launch_reduce(ba3c_handle* h, hipStream_t s, const float* part, int S, const ReduceMap& mp) {
-  if (h->defer_reduce) {
-    ReduceJobs& j = h->rjobs;
-    if (j.n >= MAX_RJOBS) return fail(BA3C_ERR_INVALID, "too many deferred reductions");
-    j.part[j.n] = part;
-    j.S[j.n] = S;
-    j.mp[j.n] = mp;
-    const int no = mp.kind == 0 ? (mp.M / mp.cin) * mp.cinpad * mp.N : mp.M * mp.N;
-    j.vec[j.n] = reduce_vec_ok(mp) ? 1 : 0;
-    j.blk0[j.n + 1] = j.blk0[j.n] + (no + (j.vec[j.n] ? 255 : 63)) / (j.vec[j.n] ? 256 : 64);
-    ++j.n;
-    return BA3C_OK;
-  }
-  const int MN = mp.M * mp.N;
+// Every weight-gradient reduction of a backward pass is a job of one launch at its end
+// (launch_reduce_all): add one.
+int add_reduce(ba3c_handle* h, const float* part, int S, const ReduceMap& mp) {
+  ReduceJobs& j = h->rjobs;
+  if (j.n >= MAX_RJOBS) return fail(BA3C_ERR_INVALID, "too many deferred reductions");
+  j.part[j.n] = part;
+  j.S[j.n] = S;
+  j.mp[j.n] = mp;
+  const int no = mp.kind == 0 ? (mp.M / mp.cin) * mp.cinpad * mp.N : mp.M * mp.N;
+  j.vec[j.n] = reduce_vec_ok(mp) ? 1 : 0;
+  j.blk0[j.n + 1] = j.blk0[j.n] + (no + (j.vec[j.n] ? 255 : 63)) / (j.vec[j.n] ? 256 : 64);
+  ++j.n;
+  return BA3C_OK;
+}
+
+int launch_reduce_all(ba3c_handle* h, hipStream_t s, const ReduceJobs& jobs) {
   {
     ProbeScope ps(h, s, BA3C_K_WGRAD_REDUCE);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((MN + 63) / 64), dim3(64 * RED_G), 0, s, part, S, mp);
+    hipLaunchKernelGGL(wgrad_reduce_all_kernel, dim3(jobs.blk0[jobs.n]), dim3(64 * RED_G), 0, s, jobs);
   }
   HIP_TRY(hipGetLastError());
   return BA3C_OK;
@@ -499,12 +440,8 @@ Band6Args band6_args(ba3c_handle* h, const BandArgs& a, const Workspace& w, int 
                    w.am(io.amax_in, h), w.wexp + io.wjob, io.amax_out >= 0 ? w.am(io.amax_out, h) : nullptr};
 }
 
-// One launch of up to three independent jobs (ba3c_multi.h); W2: the two-workgroups-per-CU
-// register budget of the band / weight-gradient kernels; T512: 512-thread jobs.
-template <bool W2, class J0, class J1, class J2 = NoJob, bool T512 = false>
-int launch_multi(hipStream_t s, const typename J0::Args& a0, dim3 g0, const typename J1::Args& a1, dim3 g1,
-                 const typename J2::Args& a2 = typename J2::Args{}, dim3 g2 = dim3(0, 1, 1),
-                 ba3c_handle* h = nullptr, int kid = -1) {
+// the jobs' grids and block ranges in a multi-job launch
+MultiGrid multi_grid(dim3 g0, dim3 g1, dim3 g2) {
   MultiGrid g;
   const dim3 gs[3] = {g0, g1, g2};
   int end = 0;
@@ -514,6 +451,17 @@ int launch_multi(hipStream_t s, const typename J0::Args& a0, dim3 g0, const type
     end += (int)(gs[j].x * gs[j].y * gs[j].z);
     g.end[j] = end;
   }
+  return g;
+}
+
+// One launch of up to three independent jobs (ba3c_multi.h); W2: the two-workgroups-per-CU
+// register budget of the band / weight-gradient kernels; T512: 512-thread jobs.
+template <bool W2, class J0, class J1, class J2 = NoJob, bool T512 = false>
+int launch_multi(hipStream_t s, const typename J0::Args& a0, dim3 g0, const typename J1::Args& a1, dim3 g1,
+                 const typename J2::Args& a2 = typename J2::Args{}, dim3 g2 = dim3(0, 1, 1),
+                 ba3c_handle* h = nullptr, int kid = -1) {
+  const MultiGrid g = multi_grid(g0, g1, g2);
+  const int end = g.end[2];
   if (end == 0) return BA3C_OK;
   // the timing probe brackets the whole launch under job 0's kernel id
   std::optional<ProbeScope> probe;
@@ -532,21 +480,14 @@ int launch_multi(hipStream_t s, const typename J0::Args& a0, dim3 g0, const type
 // for them (those in `late` inside their body); `site` picks the launch site's counter words.
 // Callers check chain_ok() first.
 constexpr int CHAIN_PREP_CONV0 = 0, CHAIN_REDUCE_UPDATE = 1;
-bool chain_ok(const ba3c_handle* h) { return h->chain_on && h->chain != nullptr; }
+bool chain_ok(const ba3c_handle* h) { return h->sw.chain && h->chain != nullptr; }
 
 template <bool W2, class J0, class J1, class J2 = NoJob>
 int launch_chain(hipStream_t s, int site, int nsig, int wmask, int late, const typename J0::Args& a0, dim3 g0,
                  const typename J1::Args& a1, dim3 g1, const typename J2::Args& a2 = typename J2::Args{},
                  dim3 g2 = dim3(0, 1, 1), ba3c_handle* h = nullptr, int kid = -1, bool spread = false) {
-  MultiGrid g;
-  const dim3 gs[3] = {g0, g1, g2};
-  int end = 0;
-  for (int j = 0; j < 3; ++j) {
-    g.gx[j] = (int)gs[j].x;
-    g.gy[j] = (int)gs[j].y;
-    end += (int)(gs[j].x * gs[j].y * gs[j].z);
-    g.end[j] = end;
-  }
+  const MultiGrid g = multi_grid(g0, g1, g2);
+  const int end = g.end[2];
   if (end == 0) return BA3C_OK;
   int nwait = 0;
   for (int j = 0; j < 3; ++j)
@@ -563,19 +504,17 @@ int launch_chain(hipStream_t s, int site, int nsig, int wmask, int late, const t
   return BA3C_OK;
 }
 
-// band conv on split MFMA; `ringable`: a multi-band layout that may run as the ring-walk
-// persistent kernel (whole images per workgroup) at large batches
+// band conv on split MFMA; `ring` (LaunchPlan::ring_fwd / ring_dgrad): a multi-band layout runs
+// as the ring-walk persistent kernel (whole images per workgroup)
 template <class L>
 int launch_band6(ba3c_handle* h, hipStream_t s, int kid, const BandArgs& a, const Workspace& w,
-                 int wt_off, SplitIO io, bool ringable = false) {
+                 int wt_off, SplitIO io, bool ring = false) {
   const Band6Args b = band6_args<L>(h, a, w, wt_off, io);
   const int nbands = a.batch * L::G::NBANDS;
   {
     ProbeScope ps(h, s, kid);
     if constexpr (L::NPH == 1 && L::G::NBANDS > 1 && L::G::SROWS > L::G::RB) {
-      // whole images per workgroup: only where they split (nearly) evenly over 2 x CUs
-      const int pr = 2 * h->cus;
-      if (ringable && h->ring && a.batch >= pr && (a.batch % pr == 0 || a.batch >= 8 * pr)) {
+      if (ring) {
         // (the forward keeps its double-buffered A fragments and no row prefetch: the
         // no-DBUF layout with the prefetch measured 0.36 -> 0.41 ms, r02ai)
         hipLaunchKernelGGL(conv_band6r_kernel<L>, dim3(2 * h->cus), dim3(256), 0, s, b);
@@ -595,7 +534,7 @@ dim3 wgrad6_grid(int pmax, int batch) {
   return dim3(std::min(pmax, batch * G::NBANDS), G::NCG * G::NOG);
 }
 template <class G>
-int reduce_wgrad6(ba3c_handle* h, hipStream_t s, const Wg6Args& a, int P, float* dst);
+int reduce_wgrad6(ba3c_handle* h, const Wg6Args& a, int P, float* dst);
 template <class G>
 int launch_wgrad6(ba3c_handle* h, hipStream_t s, int kid, const Wg6Args& a, int pmax, float* dst) {
   const dim3 grid = wgrad6_grid<G>(pmax, a.batch);
@@ -604,10 +543,10 @@ int launch_wgrad6(ba3c_handle* h, hipStream_t s, int kid, const Wg6Args& a, int 
     hipLaunchKernelGGL(wgrad6_kernel<G>, grid, dim3(256), 0, s, a);
   }
   HIP_TRY(hipGetLastError());
-  return reduce_wgrad6<G>(h, s, a, (int)grid.x, dst);
+  return reduce_wgrad6<G>(h, a, (int)grid.x, dst);
 }
 template <class G>
-int reduce_wgrad6(ba3c_handle* h, hipStream_t s, const Wg6Args& a, int P, float* dst) {
+int reduce_wgrad6(ba3c_handle* h, const Wg6Args& a, int P, float* dst) {
   ReduceMap mp{};
   mp.kind = 0;
   mp.M = G::M;
@@ -615,7 +554,7 @@ int reduce_wgrad6(ba3c_handle* h, hipStream_t s, const Wg6Args& a, int P, float*
   mp.cin = G::CIN;
   mp.cinpad = G::CIN;
   mp.dst = dst;
-  return launch_reduce(h, s, a.part, P, mp);
+  return add_reduce(h, a.part, P, mp);
 }
 
 // Split-path weight preparation arguments (wprep6_kernel): every job, the conv0 fragments and
@@ -658,7 +597,7 @@ int launch_prep_conv0_multi(ba3c_handle* h, hipStream_t s, const float* prm, con
   rest.amax = nullptr;
   const Conv0SArgs sa{state, reinterpret_cast<const uint4*>(w.wt + WT_C0S), w.p0, train ? w.c0 : nullptr,
                       train ? w.relu : nullptr, B, w.wexp + WX_CONV0, w.am(AM_P0, h)};
-  const int nconv0 = std::min(FW_P0S, B * Conv0S::NBANDS);
+  const int nconv0 = conv0_fwd_p(B);
   if (chain_ok(h) && nconv0 <= h->cus) {
     // one launch: the zeroing workgroups signal; conv0's forward (at most one workgroup per
     // CU) splits its own weight fragments and waits for the zeroing before its first
@@ -680,7 +619,7 @@ int launch_prep_conv0_multi(ba3c_handle* h, hipStream_t s, const float* prm, con
   // two workgroups per CU (the register budget of conv0's plain kernel): without the bound the
   // compiler gave the fused body 216 VGPRs + 52 AGPRs, one wave per SIMD, so at B=32 the 160 conv0
   // and 192 weight-prep workgroups did not fit the 256 CUs in one round
-  return launch_multi<true, Conv0SJob, WPrep6Job>(s, sa, dim3(std::min(FW_P0S, B * Conv0S::NBANDS)), rest,
+  return launch_multi<true, Conv0SJob, WPrep6Job>(s, sa, dim3(nconv0), rest,
                                                   dim3(64, rest.jobs.njobs));
 }
 
@@ -699,7 +638,7 @@ int launch_conv0_band(ba3c_handle* h, hipStream_t s, const BandArgs& a, const Wo
   const Conv0SArgs sa{reinterpret_cast<const uint8_t*>(a.src), reinterpret_cast<const uint4*>(w.wt + WT_C0S),
                       a.out, a.out_code, a.relu_count, a.batch, w.wexp + WX_CONV0, w.am(AM_P0, h)};
   ProbeScope ps(h, s, BA3C_K_CONV0_FWD);
-  const dim3 grid(std::min(FW_P0S, a.batch * Conv0S::NBANDS));
+  const dim3 grid(conv0_fwd_p(a.batch));
   HIP_TRY(launch_conv0s_fwd(grid, s, sa));   // ba3c_conv0.hip
   return BA3C_OK;
 }
@@ -726,12 +665,12 @@ int launch_conv3(ba3c_handle* h, hipStream_t s, int kid, const Conv3Args& a) {
 #define BA3C_FC_DEPTH 2       // k-tile ring depth of fc1's forward at full grids (A/B)
 #endif
 
-// Split kernels (h->band): conv0 (C == 4) and the conv1 / conv2 band convolutions on scaled
+// Split kernels (pl.split): conv0 (C == 4) and the conv1 / conv2 band convolutions on scaled
 // fp16 hi/lo MFMA (ba3c_split.h, ba3c_band6.h); C == 12's conv0, conv3 and fc1 on the bf16x6
 // GEMM engine.  BA3C_GENERIC=1: every layer on the fp32-MFMA GEMM engine.
 template <int CH>
-int run_forward(ba3c_handle* h, hipStream_t s, const float* prm, const uint8_t* state, int B,
-                const Workspace& w, bool train) {
+int run_forward(ba3c_handle* h, hipStream_t s, const LaunchPlan& pl, const float* prm, const uint8_t* state,
+                int B, const Workspace& w, bool train) {
   using LY = Lay;
   const int F = h->cfg.fc_neurons;
   const float* W0 = prm + h->tensors[h->idx_conv[0]].offset;
@@ -743,24 +682,24 @@ int run_forward(ba3c_handle* h, hipStream_t s, const float* prm, const uint8_t* 
   uint8_t* c1 = train ? w.c1 : nullptr;
   uint8_t* c2 = train ? w.c2 : nullptr;
   const SplitIO io1{AM_P0, WJ_C1F, AM_P1}, io2{AM_P1, WJ_C2F, AM_P2};
-  if (!h->band) {
+  if (!pl.split) {
     ConvFwd<true, 84, 84, CH, 16, 5, 5, 32, 0> cv0{state, W0, w.p0, c0, rc, 1.0f / 255.0f, B * 6400, 32, 25 * CH, 0};
     CHECK((launch_gemm<128, 32, 4, 1>(h, s, BA3C_K_CONV0_FWD, cv0, 1)));
     ConvFwd<false, 40, 40, 32, 32, 5, 5, 32, 0> cv1{w.p0, W1, w.p1, c1, rc, 1.0f, B * 1296, 32, 800, 0};
     CHECK((launch_gemm<128, 32, 4, 1>(h, s, BA3C_K_CONV1_FWD, cv1, 1)));
     ConvFwd<false, 18, 18, 32, 32, 5, 5, 64, 0> cv2{w.p1, W2, w.p2, c2, rc, 1.0f, B * 196, 64, 800, 0};
     CHECK((launch_gemm<128, 64, 4, 1>(h, s, BA3C_K_CONV2_FWD, cv2, 1)));
+    ConvFwd<false, 7, 7, 64, 64, 3, 3, 64, 2> c3{w.p2, W3, w.a3, nullptr, rc, 1.0f, B * 25, 64, 576, 0};
+    // K = 576 in two halves of 9 k-tiles summed in the workgroup (KS = 2) at every batch, so
+    // each output's rounding is the same whatever batch it runs in
+    CHECK((launch_gemm<64, 64, 2, 2, decltype(c3), 2>(h, s, BA3C_K_CONV3_FWD, c3, 1)));
   } else {
-    // small batches: weight prep beside conv0's forward (one launch fewer on the critical path)
-    const bool mj = h->multi && B <= OVERLAP_B && CH == 4;
-    // batches at which conv1's forward runs as the ring walk (launch_band6): conv0's and
-    // conv1's forward as ONE persistent launch, each workgroup taking its own images through
-    // both layers (fwd01_kernel, ba3c_conv0.hip; BA3C_FWD01=0: two launches)
-    const int pr = 2 * h->cus;
-    const bool f01 = CH == 4 && !mj && h->fwd01 && h->ring && B >= pr && (B % pr == 0 || B >= 8 * pr);
-    if (mj) {
+    if (pl.prep_multi) {
+      // small batches: weight prep beside conv0's forward (one launch fewer on the critical path)
       CHECK(launch_prep_conv0_multi(h, s, prm, state, B, w, train));
-    } else if (f01) {
+    } else if (pl.fwd01) {
+      // the ring batches: conv0's and conv1's forward as ONE persistent launch, each workgroup
+      // taking its own images through both layers (fwd01_kernel, ba3c_conv0.hip)
       CHECK(launch_wprep(h, s, prm, w, train));
       const Conv0SArgs a0{state, reinterpret_cast<const uint4*>(w.wt + WT_C0S), w.p0, c0, rc, B,
                           w.wexp + WX_CONV0, w.am(AM_P0, h)};
@@ -768,7 +707,7 @@ int run_forward(ba3c_handle* h, hipStream_t s, const float* prm, const uint8_t* 
                                                         WT_C1F, io1);
       {
         ProbeScope ps(h, s, BA3C_K_CONV0_FWD);
-        HIP_TRY(launch_fwd01(pr, s, a0, a1));
+        HIP_TRY(launch_fwd01(2 * h->cus, s, a0, a1));
       }
       h->merged[BA3C_K_CONV0_FWD] |= 1u << BA3C_K_CONV1_FWD;
     } else {
@@ -782,24 +721,17 @@ int run_forward(ba3c_handle* h, hipStream_t s, const float* prm, const uint8_t* 
         CHECK((launch_gemm<128, 32, 4, 1>(h, s, BA3C_K_CONV0_FWD, cv0, 1)));
       }
     }
-    if (!f01)
+    if (!pl.fwd01)
       CHECK((launch_band6<typename LY::C1F>(h, s, BA3C_K_CONV1_FWD, BandArgs{w.p0, nullptr, nullptr, w.p1, c1, rc, B},
-                                            w, WT_C1F, io1, true)));
+                                            w, WT_C1F, io1, pl.ring_fwd)));
     const BandArgs a2{w.p1, nullptr, nullptr, w.p2, c2, rc, B};
-    if (B <= SMALL_B)
+    if (pl.conv2_small)
       CHECK(launch_band6<typename LY::C2FS>(h, s, BA3C_K_CONV2_FWD, a2, w, WT_C2F, io2));
     else
       CHECK(launch_band6<typename LY::C2F>(h, s, BA3C_K_CONV2_FWD, a2, w, WT_C2F, io2));
-  }
-  if (h->band) {
     // whole-image workgroups at every batch: an image's a3 does not depend on its batch
     CHECK(launch_conv3<false>(h, s, BA3C_K_CONV3_FWD, Conv3Args{w.p2, w.wt6 + 2 * (size_t)WT_C3F, w.wexp + WJ_C3F,
                                                                   w.a3, rc, nullptr, B, nullptr}));
-  } else {
-    ConvFwd<false, 7, 7, 64, 64, 3, 3, 64, 2> c3{w.p2, W3, w.a3, nullptr, rc, 1.0f, B * 25, 64, 576, 0};
-    // K = 576 in two halves of 9 k-tiles summed in the workgroup (KS = 2) at every batch, so
-    // each output's rounding is the same whatever batch it runs in
-    CHECK((launch_gemm<64, 64, 2, 2, decltype(c3), 2>(h, s, BA3C_K_CONV3_FWD, c3, 1)));
   }
   // split-K: K = 1600 in FC_SPLIT fixed chunks (a 128x64 tile over all of K is one
   // workgroup's 50 serial k-tiles: latency-bound at any batch); the chunk sums (+ legacy bias,
@@ -829,7 +761,7 @@ int run_forward(ba3c_handle* h, hipStream_t s, const float* prm, const uint8_t* 
 // Create the side stream + fork/join events on the first training call made outside a
 // graph capture (stream creation is not a capturable operation).
 int ensure_side_stream(ba3c_handle* h, hipStream_t s) {
-  if (h->overlap == 0 || h->side) return BA3C_OK;
+  if (h->sw.overlap == 0 || h->side) return BA3C_OK;
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   HIP_TRY(hipStreamIsCapturing(s, &cs));
   if (cs != hipStreamCaptureStatusNone) return BA3C_OK;
@@ -839,57 +771,69 @@ int ensure_side_stream(ba3c_handle* h, hipStream_t s) {
   return BA3C_OK;
 }
 
-// phase 0: the whole backward pass.  phase 1: the heads and fc1 products and their
-// reductions (those gradients are final when it returns); phase 2: conv3..conv0 and theirs.
-// Phases 1 + 2 compute exactly phase 0; between them a data-parallel caller can all-reduce
-// the fc1 + heads bucket (most of the parameters) while the conv layers run.
+// One backward pass on the caller's stream.  phase 0: the whole pass.  phase 1: the heads and
+// fc1 products and their reductions (those gradients are final when it returns); phase 2:
+// conv3..conv0 and theirs.  Phases 1 + 2 compute exactly phase 0; between them a data-parallel
+// caller can all-reduce the fc1 + heads bucket (most of the parameters) while the conv layers
+// run.  phase 4: phase 1 with its reduction held (ba3c_launch_held).
+// The weight-gradient kernels (heads, fc1, conv3..conv1) run on `ws`: the side stream where
+// the plan asks for it, each after the event that publishes its output gradient (the side
+// stream joins a graph capture of `s` through the fork events), else `s`.  The input-gradient
+// chain and conv0's weight gradient (own partials region) stay on `s`, which joins `ws` at the
+// end.  Under pl.mj* a layer's input- and weight-gradient kernels are one multi-job launch on
+// `s` instead (no side stream, no events).  Each layer: the split path, then the BA3C_GENERIC
+// engine path (fp32-MFMA GEMMs).
 template <int CH>
-int run_backward(ba3c_handle* h, hipStream_t s, const float* prm, const uint8_t* state, int B,
-                 const Workspace& w, float* grads, int phase = 0) {
+struct BackwardPass {
   using LY = Lay;
-  const int F = h->cfg.fc_neurons, A = h->cfg.num_actions;
-  const bool legacy = !h->cfg.replace_with_conv;
-  const float* W1c = prm + h->tensors[h->idx_conv[1]].offset;
-  const float* W2c = prm + h->tensors[h->idx_conv[2]].offset;
-  const float* W3c = prm + h->tensors[h->idx_conv[3]].offset;
-  const float* Wfc = prm + h->tensors[h->idx_fc1].offset;
-  // The weight-gradient kernels (heads, fc1, conv3..conv1) run on the side stream `ws`,
-  // each after the event that publishes its output gradient; the input-gradient chain and
-  // conv0's weight gradient (own partials region) stay on `s`, which joins `ws` at the end.
-  hipStream_t ws = s;
+  using W1 = typename LY::W1;
+  ba3c_handle* h;
+  hipStream_t s, ws;
+  const LaunchPlan& pl;
+  const Workspace& w;
+  const float* prm;
+  const uint8_t* state;
+  float* grads;
+  int B, phase;
   int nfork = 0;
-  auto fork = [&]() -> int {
+
+  // every weight-gradient reduction is deferred into one launch at the end (h->rjobs: a phase-3
+  // pass leaves it there for the next fused apply)
+  BackwardPass(ba3c_handle* h_, hipStream_t s_, const LaunchPlan& pl_, const Workspace& w_, const float* prm_,
+               const uint8_t* state_, float* grads_, int B_, int phase_)
+      : h(h_), s(s_), ws(pl_.side_stream && h_->side ? h_->side : s_), pl(pl_), w(w_), prm(prm_), state(state_),
+        grads(grads_), B(B_), phase(phase_) {
+    h->rjobs.n = 0;
+    h->rjobs.blk0[0] = 0;
+  }
+
+  const float* param(int t) const { return prm + h->tensors[t].offset; }
+  float* grad(int t) const { return grads + h->tensors[t].offset; }
+  Wg6Args wa1() const { return Wg6Args{w.p0, w.dp1, w.c1, w.part_1, B, w.am(AM_P0, h), w.am(AM_DP1, h)}; }
+
+  int run() {
+    CHECK(fork());
+    if (phase != 2) CHECK(fc_and_heads());
+    if (phase == 1 || phase == 4) return finish();
+    CHECK(conv3());
+    if (phase == 2 && h->ev_mid) HIP_TRY(hipEventRecord(h->ev_mid, s));
+    CHECK(conv2());
+    CHECK(conv1());
+    CHECK(conv0());
+    // all (remaining) weight-gradient reductions: one launch, every gradient element written once
+    return finish();
+  }
+
+  int fork() {
     if (ws == s) return BA3C_OK;
     HIP_TRY(hipEventRecord(h->ev_fork[nfork], s));
     HIP_TRY(hipStreamWaitEvent(ws, h->ev_fork[nfork], 0));
     ++nfork;
     return BA3C_OK;
-  };
-  // small batches on the split path: each layer's input- and weight-gradient kernels as one
-  // multi-job launch on `s` (no side stream, no events); otherwise the side stream joins a
-  // graph capture of `s` through the fork events
-  const bool mjok = h->multi && h->overlap != 1 && h->band && CH == 4;
-  const bool mj = mjok && B <= OVERLAP_B;
-  const bool mj_fc = mj || (mjok && (h->multi_big & 1));
-  const bool mj_c2 = !mj && mjok && (h->multi_big & 2);   // large-batch conv2 pair (A/B: BA3C_MULTI_BIG=3)
+  }
 
-  static_assert(OVERLAP_B <= SMALL_B, "multi-job conv2 input gradient is the small-batch geometry");
-  if (!mj && h->side && (h->overlap == 1 || B <= OVERLAP_B)) ws = h->side;
-  const bool big = B > OVERLAP_B;   // multi-job gemm jobs: 2-deep k-tile rings (full grids)
-  const bool fc1big = mj_fc && big;   // fc1w_plan
-  // every weight-gradient reduction is deferred into one launch at the end (RAII: an early
-  // error return leaves the handle in immediate mode)
-  struct DeferGuard {
-    ba3c_handle* h;
-    explicit DeferGuard(ba3c_handle* h_) : h(h_) {
-      h->defer_reduce = true;
-      h->rjobs.n = 0;
-      h->rjobs.blk0[0] = 0;
-    }
-    ~DeferGuard() { h->defer_reduce = false; }
-  } defer_guard(h);
   // join the side stream and run the deferred reductions of this phase in one launch
-  auto finish = [&]() -> int {
+  int finish() {
     if (h->pend_scalars && phase != 1 && phase != 4) {   // no launch took the deferred scalar reduction
       // (phase 1 leaves it pending: conv3's input-gradient launch in phase 2 takes it)
       const ScalarsJob::Args& sa = h->scalars_args;
@@ -903,110 +847,96 @@ int run_backward(ba3c_handle* h, hipStream_t s, const float* prm, const uint8_t*
       HIP_TRY(hipStreamWaitEvent(s, h->ev_join, 0));
     }
     const ReduceJobs& jb = h->rjobs;
-    if (jb.n > 0 && phase == 4) {
+    if (jb.n == 0) return BA3C_OK;
+    if (phase == 4) {
       h->held = true;          // ba3c_launch_held (or the next entry point) launches it
       h->held_stream = s;
       h->held_jobs = jb;
-    } else if (jb.n > 0 && h->defer_final && phase == 0) {
+    } else if (h->defer_final && phase == 0) {
       h->pend_reduce = true;   // the next fused apply runs it (flush_reduce otherwise)
       h->pend_stream = s;
       h->pend_grads = grads;
-    } else if (jb.n > 0) {
-      ProbeScope ps(h, s, BA3C_K_WGRAD_REDUCE);
-      hipLaunchKernelGGL(wgrad_reduce_all_kernel, dim3(jb.blk0[jb.n]), dim3(64 * RED_G), 0, s, jb);
+    } else {
+      return launch_reduce_all(h, s, jb);
     }
-    HIP_TRY(hipGetLastError());
     return BA3C_OK;
-  };
-  CHECK(fork());
+  }
 
-  if (phase != 2) {
-  // heads: d fc-pi/W, fc-pi/b, fc-v/W, fc-v/b  (X = h, G = [dz | dV])
-  {
-    WgradPlan pl = plan_wgrad(F + 1, A + 1, B, 128, 32);
-    BatchWgrad g{w.h, w.dzv, w.part_h, F, MAXA, 1, pl.M, pl.N, pl.K, pl.kchunk};
-    WgradPlan plf = fc1w_plan(F, B, legacy, fc1big);
-    BatchWgrad gf{w.a3, w.dh, w.part_f, 1600, F, legacy ? 1 : 0, plf.M, plf.N, plf.K, plf.kchunk};
-    FcDgrad d{w.dh, Wfc, w.a3, w.dy3, h->per, h->wstride, B, 1600, F, 0};
-    const int dbm = fc1big ? 128 : 64, fbn = fc1big ? 128 : 64;
-    const dim3 gd((d.M + dbm - 1) / dbm, (d.N + dbm - 1) / dbm, 1), gh((pl.M + 127) / 128, (pl.N + 31) / 32, pl.S),
-        gff((plf.M + 127) / 128, (plf.N + fbn - 1) / fbn, plf.S);
-    if (mj_fc)   // fc1 input gradient + head and fc1 weight gradients: one launch
+  int conv_reduce(int M, int N, int S, int layer, int cin, int cinpad, const float* part) {
+    ReduceMap mp{};
+    mp.kind = 0;
+    mp.M = M;
+    mp.N = N;
+    mp.cin = cin;
+    mp.cinpad = cinpad;
+    mp.dst = grad(h->idx_conv[layer]);
+    return add_reduce(h, part, S, mp);
+  }
+
+  // head and fc1 weight gradients (X = h, G = [dz | dV]: d fc-pi/W, fc-pi/b, fc-v/W, fc-v/b; fc1's
+  // + legacy bias) and fc1's input gradient -> dY3 (ReluGrad of conv3 fused)
+  int fc_and_heads() {
+    const int F = h->cfg.fc_neurons, A = h->cfg.num_actions;
+    const bool legacy = !h->cfg.replace_with_conv;
+    const WgradPlan ph = plan_wgrad(F + 1, A + 1, B, 128, 32), pf = fc1w_plan(F, B, legacy, pl.fc1_big_tiles);
+    const BatchWgrad gh{w.h, w.dzv, w.part_h, F, MAXA, 1, ph.M, ph.N, ph.K, ph.kchunk};
+    const BatchWgrad gf{w.a3, w.dh, w.part_f, 1600, F, legacy ? 1 : 0, pf.M, pf.N, pf.K, pf.kchunk};
+    const FcDgrad d{w.dh, param(h->idx_fc1), w.a3, w.dy3, h->per, h->wstride, B, 1600, F, 0};
+    if (pl.mj_fc) {   // one launch (the engine is the bf16x6 one: mj_fc is a split-path decision)
+      const int dbm = pl.fc1_big_tiles ? 128 : 64, fbn = dbm;
+      const dim3 gd((d.M + dbm - 1) / dbm, (d.N + dbm - 1) / dbm, 1), ghd((ph.M + 127) / 128, (ph.N + 31) / 32, ph.S),
+          gfd((pf.M + 127) / 128, (pf.N + fbn - 1) / fbn, pf.S);
       h->merged[BA3C_K_FC1_DGRAD] |= (1u << BA3C_K_FC1_WGRAD) | (1u << BA3C_K_HEAD_WGRAD);
-    if (mj_fc && !big)
-      CHECK((launch_multi<false, Gemm6Job<64, 64, 2, 2, FcDgrad, 4>, Gemm6Job<128, 32, 4, 1, BatchWgrad, 4>,
-                          Gemm6Job<128, 64, 2, 2, BatchWgrad, 4>>(s, d, gd, g, gh, gf, gff, h, BA3C_K_FC1_DGRAD)));
 #ifndef BA3C_FCD_DEPTH
 #define BA3C_FCD_DEPTH 2      // k-tile ring depth of the large-batch fc1 backward jobs (A/B)
 #endif
-    else if (mj_fc && fc1big)
-      CHECK((launch_multi<false, Gemm6Job<128, 128, 2, 2, FcDgrad, BA3C_FCD_DEPTH>,
-                          Gemm6Job<128, 32, 4, 1, BatchWgrad, BA3C_FCD_DEPTH>,
-                          Gemm6Job<128, 128, 2, 2, BatchWgrad, BA3C_FCD_DEPTH>>(s, d, gd, g, gh, gf, gff, h,
-                                                                              BA3C_K_FC1_DGRAD)));
-    else if (mj_fc)
-      CHECK((launch_multi<false, Gemm6Job<64, 64, 2, 2, FcDgrad, BA3C_FCD_DEPTH>, Gemm6Job<128, 32, 4, 1, BatchWgrad, BA3C_FCD_DEPTH>,
-                          Gemm6Job<128, 64, 2, 2, BatchWgrad, BA3C_FCD_DEPTH>>(s, d, gd, g, gh, gf, gff, h, BA3C_K_FC1_DGRAD)));
-    else
-      CHECK((launch_gemm<128, 32, 4, 1>(h, ws, BA3C_K_HEAD_WGRAD, g, pl.S)));
-    ReduceMap mp{};
-    mp.kind = 2;
-    mp.M = pl.M;
-    mp.N = pl.N;
-    mp.A = A;
-    mp.dst = grads + h->tensors[h->idx_piW].offset;
-    mp.dst_pib = grads + h->tensors[h->idx_pib].offset;
-    mp.dst_vW = grads + h->tensors[h->idx_vW].offset;
-    mp.dst_vb = grads + h->tensors[h->idx_vb].offset;
-    CHECK(launch_reduce(h, ws, w.part_h, pl.S, mp));
+      if (!pl.big)
+        CHECK((launch_multi<false, Gemm6Job<64, 64, 2, 2, FcDgrad, 4>, Gemm6Job<128, 32, 4, 1, BatchWgrad, 4>,
+                            Gemm6Job<128, 64, 2, 2, BatchWgrad, 4>>(s, d, gd, gh, ghd, gf, gfd, h, BA3C_K_FC1_DGRAD)));
+      else if (pl.fc1_big_tiles)
+        CHECK((launch_multi<false, Gemm6Job<128, 128, 2, 2, FcDgrad, BA3C_FCD_DEPTH>,
+                            Gemm6Job<128, 32, 4, 1, BatchWgrad, BA3C_FCD_DEPTH>,
+                            Gemm6Job<128, 128, 2, 2, BatchWgrad, BA3C_FCD_DEPTH>>(s, d, gd, gh, ghd, gf, gfd, h,
+                                                                                BA3C_K_FC1_DGRAD)));
+      else   // (the small tiles at full grids: no plan asks for them today)
+        CHECK((launch_multi<false, Gemm6Job<64, 64, 2, 2, FcDgrad, BA3C_FCD_DEPTH>, Gemm6Job<128, 32, 4, 1, BatchWgrad, BA3C_FCD_DEPTH>,
+                            Gemm6Job<128, 64, 2, 2, BatchWgrad, BA3C_FCD_DEPTH>>(s, d, gd, gh, ghd, gf, gfd, h, BA3C_K_FC1_DGRAD)));
+    } else {
+      CHECK((launch_gemm<128, 32, 4, 1>(h, ws, BA3C_K_HEAD_WGRAD, gh, ph.S)));
+      CHECK((launch_gemm<128, 64, 2, 2>(h, ws, BA3C_K_FC1_WGRAD, gf, pf.S)));
+      CHECK((launch_gemm<64, 64, 2, 2>(h, s, BA3C_K_FC1_DGRAD, d, 1)));
+    }
+    ReduceMap mh{};
+    mh.kind = 2;
+    mh.M = ph.M;
+    mh.N = ph.N;
+    mh.A = A;
+    mh.dst = grad(h->idx_piW);
+    mh.dst_pib = grad(h->idx_pib);
+    mh.dst_vW = grad(h->idx_vW);
+    mh.dst_vb = grad(h->idx_vb);
+    CHECK(add_reduce(h, w.part_h, ph.S, mh));
+    ReduceMap mf{};
+    mf.kind = 1;
+    mf.M = pf.M;
+    mf.N = pf.N;
+    mf.per = h->per;
+    mf.wstride = h->wstride;
+    mf.dst = grad(h->idx_fc1);
+    CHECK(add_reduce(h, w.part_f, pf.S, mf));
+    return fork();
   }
-  // fc1 weight (+ legacy bias) gradient
-  {
-    WgradPlan pl = fc1w_plan(F, B, legacy, fc1big);
-    BatchWgrad g{w.a3, w.dh, w.part_f, 1600, F, legacy ? 1 : 0, pl.M, pl.N, pl.K, pl.kchunk};
-    if (!mj_fc) CHECK((launch_gemm<128, 64, 2, 2>(h, ws, BA3C_K_FC1_WGRAD, g, pl.S)));
-    ReduceMap mp{};
-    mp.kind = 1;
-    mp.M = pl.M;
-    mp.N = pl.N;
-    mp.per = h->per;
-    mp.wstride = h->wstride;
-    mp.dst = grads + h->tensors[h->idx_fc1].offset;
-    CHECK(launch_reduce(h, ws, w.part_f, pl.S, mp));
-  }
-  // fc1 input gradient -> dY3 (ReluGrad of conv3 fused)
-  {
-    FcDgrad d{w.dh, Wfc, w.a3, w.dy3, h->per, h->wstride, B, 1600, F, 0};
-    if (!mj_fc) CHECK((launch_gemm<64, 64, 2, 2>(h, s, BA3C_K_FC1_DGRAD, d, 1)));
-    CHECK(fork());
-  }
-  }  // phase != 2
-  if (phase == 1 || phase == 4) return finish();
-  auto conv_reduce = [&](const WgradPlan& pl, int layer, int cin, int cinpad, const float* part) {
-    ReduceMap mp{};
-    mp.kind = 0;
-    mp.M = pl.M;
-    mp.N = pl.N;
-    mp.cin = cin;
-    mp.cinpad = cinpad;
-    mp.dst = grads + h->tensors[h->idx_conv[layer]].offset;
-    return launch_reduce(h, ws, part, pl.S, mp);
-  };
-  // conv3's weight gradient when it rides on conv2's launch (BA3C_C3W_RIDE)
-  Conv3WArgs c3w{};
-  int c3w_gx = 0;
-  // conv3
-  {
-    WgradPlan pl = plan_wgrad(576, 64, B * 25, 128, 64);
-    if (h->band) {
+
+  int conv3() {
+    if (pl.split) {
       // whole-image kernels (ba3c_conv3.h) at every batch: an image's dP2 rounds the same in
       // any batch.  Input gradient first: it publishes dY3's per-image maxima, the weight
       // gradient's scale (both on `s`, whatever the side-stream setting); the deferred
       // TfDictOp reduction rides on it as one extra workgroup
       const Conv3Args da{w.dy3, w.wt6 + 2 * (size_t)WT_C3D, w.wexp + WJ_C3D, w.dp2, nullptr,
                          w.am(AM_DP2, h), B, w.am(AM_DY3, h)};
-      const int gx = conv3_wgrad_p(B, h->cus);
-      if (mj) {
+      const int gx = pl.conv3_slabs;   // one slab per weight-gradient workgroup
+      if (pl.mj) {
         // small batches: input and weight gradient in one launch (two 256-thread workgroups per
         // weight-gradient slab; the weight gradient reduces max |dY3| itself, since the input
         // gradient publishes it only as it runs)
@@ -1015,7 +945,7 @@ int run_backward(ba3c_handle* h, hipStream_t s, const float* prm, const uint8_t*
                                                          0, dim3(0, 1, 1), h, BA3C_K_CONV3_DGRAD)));
         h->merged[BA3C_K_CONV3_DGRAD] |= 1u << BA3C_K_CONV3_WGRAD;
       } else {
-        if (big && h->pend_scalars) {
+        if (pl.big && h->pend_scalars) {
           CHECK((launch_multi<true, Conv3DJob, ScalarsJob>(s, da, dim3(std::min(B, BA3C_C3_WGPC * h->cus)), h->scalars_args,
                                                             dim3(1), 0, dim3(0, 1, 1), h, BA3C_K_CONV3_DGRAD)));
           h->merged[BA3C_K_CONV3_DGRAD] |= 1u << BA3C_K_SCALARS;   // the reduction rode on this launch
@@ -1024,178 +954,135 @@ int run_backward(ba3c_handle* h, hipStream_t s, const float* prm, const uint8_t*
           CHECK(launch_conv3<true>(h, s, BA3C_K_CONV3_DGRAD, da));
         }
         const Conv3WArgs wa{w.p2, w.dy3, w.part_3, B, w.am(AM_P2, h), w.am(AM_DY3, h), 0};
-        if (mj_c2 && h->c3ride) {
-          c3w = wa;   // a job of conv2's launch below
-          c3w_gx = gx;
-        } else {
+        {
           ProbeScope ps(h, s, BA3C_K_CONV3_WGRAD);
           hipLaunchKernelGGL(conv3_wgrad_kernel, dim3(gx), dim3(512), 0, s, wa);
         }
         HIP_TRY(hipGetLastError());
       }
-      pl.S = gx;   // one slab per workgroup
-    } else {   // BA3C_GENERIC: the fp32-MFMA GEMM engine
-      ConvWgrad<false, 7, 7, 64, 3, 3, 64, false> g{w.p2, w.dy3, nullptr, w.part_3, 1.0f, pl.M, pl.N, pl.K, pl.kchunk};
-      ConvDgrad<7, 7, 64, 3, 3, 64, false> d{w.dy3, nullptr, W3c, w.dp2, B * 49, 64, 576, 0, nullptr};
-      CHECK((launch_gemm<128, 64, 4, 1>(h, ws, BA3C_K_CONV3_WGRAD, g, pl.S)));
+      CHECK(conv_reduce(576, 64, gx, 3, 64, 64, w.part_3));
+    } else {
+      const WgradPlan p = plan_wgrad(576, 64, B * 25, 128, 64);
+      ConvWgrad<false, 7, 7, 64, 3, 3, 64, false> g{w.p2, w.dy3, nullptr, w.part_3, 1.0f, p.M, p.N, p.K, p.kchunk};
+      ConvDgrad<7, 7, 64, 3, 3, 64, false> d{w.dy3, nullptr, param(h->idx_conv[3]), w.dp2, B * 49, 64, 576, 0, nullptr};
+      CHECK((launch_gemm<128, 64, 4, 1>(h, ws, BA3C_K_CONV3_WGRAD, g, p.S)));
       CHECK((launch_gemm<64, 64, 2, 2>(h, s, BA3C_K_CONV3_DGRAD, d, 1)));
+      CHECK(conv_reduce(p.M, p.N, p.S, 3, 64, 64, w.part_3));
     }
-    CHECK(conv_reduce(pl, 3, 64, 64, w.part_3));
-    CHECK(fork());
+    return fork();
   }
-  if (phase == 2 && h->ev_mid) HIP_TRY(hipEventRecord(h->ev_mid, s));
-  // conv2
-  {
+
+  int conv2() {
+    if (!pl.split) {
+      const WgradPlan p = plan_wgrad(800, 64, B * 196, 128, 64);
+      ConvWgrad<false, 18, 18, 32, 5, 5, 64, true> g{w.p1, w.dp2, w.c2, w.part_2, 1.0f, p.M, p.N, p.K, p.kchunk};
+      CHECK((launch_gemm<128, 64, 4, 1>(h, ws, BA3C_K_CONV2_WGRAD, g, p.S)));
+      CHECK(conv_reduce(p.M, p.N, p.S, 2, 32, 32, w.part_2));
+      ConvDgrad<18, 18, 32, 5, 5, 64, true> d{w.dp2, w.c2, param(h->idx_conv[2]), w.dp1, B * 324, 32, 1600, 0};
+      CHECK((launch_gemm<128, 32, 4, 1>(h, s, BA3C_K_CONV2_DGRAD, d, 1)));
+      return fork();
+    }
     using W2 = typename LY::W2;
     const Wg6Args wa{w.p1, w.dp2, w.c2, w.part_2, B, w.am(AM_P1, h), w.am(AM_DP2, h)};
     const BandArgs ba{w.dp2, w.c2, w.wt + WT_C2D, w.dp1, nullptr, nullptr, B};
     const SplitIO io{AM_DP2, WJ_C2D, AM_DP1};
-    float* dW2 = grads + h->tensors[h->idx_conv[2]].offset;
-    if (mj || mj_c2) {
-      // input and weight gradient in one launch: the small-batch geometry, or the whole-map one
-      const dim3 wg = wgrad6_grid<W2>(W6_P2, B);
-      if (mj) {
-        CHECK((launch_multi<true, Band6Job<typename LY::C2DS>, Wg6Job<W2>>(
-            s, band6_args<typename LY::C2DS>(h, ba, w, WT_C2D, io), dim3(B * LY::C2DS::G::NBANDS), wa, wg)));
-      } else {
-        using C2D = typename LY::C2D;
-        const Band6Args da = band6_args<C2D>(h, ba, w, WT_C2D, io);
-        const dim3 gd(B * C2D::G::NBANDS), g3(c3w_gx, 2);
-        if (c3w_gx && h->c3ride == 2)
-          CHECK((launch_multi<true, Conv3WJob, Band6Job<C2D>, Wg6Job<W2>>(s, c3w, g3, da, gd, wa, wg, h,
-                                                                         BA3C_K_CONV2_DGRAD)));
-        else if (c3w_gx)
-          CHECK((launch_multi<true, Band6Job<C2D>, Wg6Job<W2>, Conv3WJob>(s, da, gd, wa, wg, c3w, g3, h,
-                                                                         BA3C_K_CONV2_DGRAD)));
-        else
-          CHECK((launch_multi<true, Band6Job<C2D>, Wg6Job<W2>>(s, da, gd, wa, wg, 0, dim3(0, 1, 1), h,
-                                                              BA3C_K_CONV2_DGRAD)));
-        if (c3w_gx) h->merged[BA3C_K_CONV2_DGRAD] |= 1u << BA3C_K_CONV3_WGRAD;
-      }
-      h->merged[BA3C_K_CONV2_DGRAD] |= 1u << BA3C_K_CONV2_WGRAD;
-      CHECK(reduce_wgrad6<W2>(h, s, wa, (int)wg.x, dW2));
-    } else {
-      if (h->band) {
-        CHECK(launch_wgrad6<W2>(h, ws, BA3C_K_CONV2_WGRAD, wa, W6_P2, dW2));
-      } else {
-        WgradPlan pl = plan_wgrad(800, 64, B * 196, 128, 64);
-        ConvWgrad<false, 18, 18, 32, 5, 5, 64, true> g{w.p1, w.dp2, w.c2, w.part_2, 1.0f, pl.M, pl.N, pl.K, pl.kchunk};
-        CHECK((launch_gemm<128, 64, 4, 1>(h, ws, BA3C_K_CONV2_WGRAD, g, pl.S)));
-        CHECK(conv_reduce(pl, 2, 32, 32, w.part_2));
-      }
-      if (h->band) {
-        if (B <= SMALL_B)
-          CHECK(launch_band6<typename LY::C2DS>(h, s, BA3C_K_CONV2_DGRAD, ba, w, WT_C2D, io));
-        else
-          CHECK(launch_band6<typename LY::C2D>(h, s, BA3C_K_CONV2_DGRAD, ba, w, WT_C2D, io));
-      } else {
-        ConvDgrad<18, 18, 32, 5, 5, 64, true> d{w.dp2, w.c2, W2c, w.dp1, B * 324, 32, 1600, 0};
-        CHECK((launch_gemm<128, 32, 4, 1>(h, s, BA3C_K_CONV2_DGRAD, d, 1)));
-      }
-      CHECK(fork());
+    float* dW2 = grad(h->idx_conv[2]);
+    if (!pl.mj && !pl.mj_c2) {
+      CHECK(launch_wgrad6<W2>(h, ws, BA3C_K_CONV2_WGRAD, wa, W6_P2, dW2));
+      if (pl.conv2_small)
+        CHECK(launch_band6<typename LY::C2DS>(h, s, BA3C_K_CONV2_DGRAD, ba, w, WT_C2D, io));
+      else
+        CHECK(launch_band6<typename LY::C2D>(h, s, BA3C_K_CONV2_DGRAD, ba, w, WT_C2D, io));
+      return fork();
     }
+    // input and weight gradient in one launch: the small-batch geometry, or the whole-map one
+    const dim3 wg = wgrad6_grid<W2>(W6_P2, B);
+    if (pl.mj) {
+      CHECK((launch_multi<true, Band6Job<typename LY::C2DS>, Wg6Job<W2>>(
+          s, band6_args<typename LY::C2DS>(h, ba, w, WT_C2D, io), dim3(B * LY::C2DS::G::NBANDS), wa, wg)));
+    } else {
+      using C2D = typename LY::C2D;
+      CHECK((launch_multi<true, Band6Job<C2D>, Wg6Job<W2>>(s, band6_args<C2D>(h, ba, w, WT_C2D, io),
+                                                          dim3(B * C2D::G::NBANDS), wa, wg, 0, dim3(0, 1, 1), h,
+                                                          BA3C_K_CONV2_DGRAD)));
+    }
+    h->merged[BA3C_K_CONV2_DGRAD] |= 1u << BA3C_K_CONV2_WGRAD;
+    return reduce_wgrad6<W2>(h, wa, (int)wg.x, dW2);
   }
-  // conv1
-  using W1 = typename LY::W1;
-  const Wg6Args wa1{w.p0, w.dp1, w.c1, w.part_1, B, w.am(AM_P0, h), w.am(AM_DP1, h)};
-  float* dW1 = grads + h->tensors[h->idx_conv[1]].offset;
-  // large batches: its whole-channel weight gradient waits for conv0's (one paired launch below),
-  // or shares the input gradient's launch, one workgroup of each per CU (each job walks twice the
-  // images of its separate launch)
-  const bool pairgeo = !mj && h->band && h->ring && conv1_pair_geometry(B, h->cus);
-  const bool defer_w1 = pairgeo && h->c1pair == 2 && CH == 4;
-  const bool paired = pairgeo && !defer_w1 && h->c1pair == 1;
-  {
+
+  // conv1: the weight gradient (alone on `ws`, or a job of the input gradient's launch; the pair
+  // with conv0's waits for conv0()), then the input gradient
+  int conv1() {
+    if (!pl.split) {
+      const WgradPlan p = plan_wgrad(800, 32, B * 1296, 128, 32);
+      ConvWgrad<false, 40, 40, 32, 5, 5, 32, true> g{w.p0, w.dp1, w.c1, w.part_1, 1.0f, p.M, p.N, p.K, p.kchunk};
+      CHECK((launch_gemm<128, 32, 4, 1>(h, ws, BA3C_K_CONV1_WGRAD, g, p.S)));
+      CHECK(conv_reduce(p.M, p.N, p.S, 1, 32, 32, w.part_1));
+      ConvDgrad<40, 40, 32, 5, 5, 32, true> d{w.dp1, w.c1, param(h->idx_conv[1]), w.dp0, B * 1600, 32, 800, 0};
+      return launch_gemm<128, 32, 4, 1>(h, s, BA3C_K_CONV1_DGRAD, d, 1);
+    }
+    const Wg6Args wa = wa1();
+    float* dW1 = grad(h->idx_conv[1]);
+    const int P = pl.conv1_slabs;
     const BandArgs ba{w.dp1, w.c1, w.wt + WT_C1D, w.dp0, nullptr, nullptr, B};
     const SplitIO io{AM_DP1, WJ_C1D, AM_DP0};
-    if (mj) {
+    if (pl.mj) {
       // small batches: input and weight gradient in one launch
-      const dim3 wg = wgrad6_grid<W1>(conv1_wgrad_p(B), B);
       CHECK((launch_multi<true, Band6Job<typename LY::C1D>, Wg6Job<W1>>(
-          s, band6_args<typename LY::C1D>(h, ba, w, WT_C1D, io), dim3(B * LY::C1D::G::NBANDS), wa1, wg)));
+          s, band6_args<typename LY::C1D>(h, ba, w, WT_C1D, io), dim3(B * LY::C1D::G::NBANDS), wa,
+          wgrad6_grid<W1>(P, B))));
       h->merged[BA3C_K_CONV1_DGRAD] |= 1u << BA3C_K_CONV1_WGRAD;
-      CHECK(reduce_wgrad6<W1>(h, s, wa1, (int)wg.x, dW1));
-    } else {
-      // the weight gradient: deferred, paired, whole-channel kernel, wgrad6, or the GEMM engine
-      if (defer_w1) {
-        // beside conv0's weight gradient below
-      } else if (paired) {
-        CHECK((launch_multi<true, Band6RJob<typename LY::C1D>, Wg6WJob<typename LY::W1W>>(
-            s, band6_args<typename LY::C1D>(h, ba, w, WT_C1D, io), dim3(h->cus), wa1, dim3(h->cus), 0,
-            dim3(0, 1, 1), h, BA3C_K_CONV1_DGRAD)));
-        h->merged[BA3C_K_CONV1_DGRAD] |= 1u << BA3C_K_CONV1_WGRAD;
-        CHECK(reduce_wgrad6<W1>(h, s, wa1, h->cus, dW1));
-      } else if (h->band && B >= W6W_MIN_B) {
-        const int P = conv1_w6w_p(B, h->cus);
-        {
-          ProbeScope ps(h, ws, BA3C_K_CONV1_WGRAD);
-          hipLaunchKernelGGL(wgrad6w_kernel<typename LY::W1W>, dim3(P), dim3(256), 0, ws, wa1);
-        }
-        HIP_TRY(hipGetLastError());
-        CHECK(reduce_wgrad6<W1>(h, ws, wa1, P, dW1));
-      } else if (h->band) {
-        CHECK(launch_wgrad6<W1>(h, ws, BA3C_K_CONV1_WGRAD, wa1, conv1_wgrad_p(B), dW1));
-      } else {
-        WgradPlan pl = plan_wgrad(800, 32, B * 1296, 128, 32);
-        ConvWgrad<false, 40, 40, 32, 5, 5, 32, true> g{w.p0, w.dp1, w.c1, w.part_1, 1.0f, pl.M, pl.N, pl.K, pl.kchunk};
-        CHECK((launch_gemm<128, 32, 4, 1>(h, ws, BA3C_K_CONV1_WGRAD, g, pl.S)));
-        CHECK(conv_reduce(pl, 1, 32, 32, w.part_1));
-      }
-      // then the input gradient
-      if (paired) {
-        // ran in the multi-job launch above
-      } else if (h->band) {
-        CHECK(launch_band6<typename LY::C1D>(h, s, BA3C_K_CONV1_DGRAD, ba, w, WT_C1D, io, true));
-      } else {
-        ConvDgrad<40, 40, 32, 5, 5, 32, true> d{w.dp1, w.c1, W1c, w.dp0, B * 1600, 32, 800, 0};
-        CHECK((launch_gemm<128, 32, 4, 1>(h, s, BA3C_K_CONV1_DGRAD, d, 1)));
-      }
+      return reduce_wgrad6<W1>(h, wa, P, dW1);
     }
-  }
-  // conv0 (no input gradient: the frames are not trainable)
-  if (h->band && CH == 4) {
-    // slab count: one per CU where conv1's weight gradient can share the launch (on every launch
-    // path, so they all sum the same slabs), else up to WG_P0S
-    const int P = conv1_pair_geometry(B, h->cus) ? h->cus : std::min(WG_P0S, B * Conv0W<2>::NBANDS);
-    const Conv0WArgs a0{state, w.dp0, w.c0, w.part0, B, w.am(AM_DP0, h)};
-    if (defer_w1) {
-      // conv1's whole-channel weight gradient (MFMA-bound) beside conv0's (VALU-bound): one
-      // workgroup of each per CU, one launch (ba3c_conv0.hip)
+    if (pl.conv1_wgrad == Conv1Wgrad::whole) {
       {
-        ProbeScope ps(h, s, BA3C_K_CONV0_WGRAD);
-        HIP_TRY(launch_wgrad01_pair(s, wa1, h->cus, a0, P));
+        ProbeScope ps(h, ws, BA3C_K_CONV1_WGRAD);
+        hipLaunchKernelGGL(wgrad6w_kernel<typename LY::W1W>, dim3(P), dim3(256), 0, ws, wa);
       }
-      h->merged[BA3C_K_CONV0_WGRAD] |= 1u << BA3C_K_CONV1_WGRAD;
-      CHECK(reduce_wgrad6<W1>(h, s, wa1, h->cus, dW1));
-    } else {
-      ProbeScope ps(h, s, BA3C_K_CONV0_WGRAD);
-      HIP_TRY(launch_conv0s_wgrad(dim3(P), s, a0));
+      HIP_TRY(hipGetLastError());
+      CHECK(reduce_wgrad6<W1>(h, wa, P, dW1));
+    } else if (pl.conv1_wgrad == Conv1Wgrad::wgrad6) {
+      CHECK(launch_wgrad6<W1>(h, ws, BA3C_K_CONV1_WGRAD, wa, P, dW1));
     }
-    HIP_TRY(hipGetLastError());
+    return launch_band6<typename LY::C1D>(h, s, BA3C_K_CONV1_DGRAD, ba, w, WT_C1D, io, pl.ring_dgrad);
+  }
+
+  // conv0 (no input gradient: the frames are not trainable)
+  int conv0() {
     ReduceMap mp{};
     mp.kind = 0;
-    mp.M = Conv0W<2>::M;
     mp.N = 32;
-    mp.cin = 4;
-    mp.cinpad = 16;
-    mp.dst = grads + h->tensors[h->idx_conv[0]].offset;
-    CHECK(launch_reduce(h, s, w.part0, P, mp));
-  } else {
-    WgradPlan pl = plan_wgrad(25 * CH, 32, B * 6400, 128, 32);
-    ConvWgrad<true, 84, 84, CH, 5, 5, 32, true> g{state, w.dp0, w.c0, w.part0, 1.0f / 255.0f, pl.M, pl.N, pl.K, pl.kchunk};
-    CHECK((launch_gemm<128, 32, 4, 1>(h, s, BA3C_K_CONV0_WGRAD, g, pl.S)));
-    ReduceMap mp{};
-    mp.kind = 0;
-    mp.M = pl.M;
-    mp.N = pl.N;
     mp.cin = CH;
     mp.cinpad = 16;
-    mp.dst = grads + h->tensors[h->idx_conv[0]].offset;
-    CHECK(launch_reduce(h, s, w.part0, pl.S, mp));
+    mp.dst = grad(h->idx_conv[0]);
+    if (pl.split && CH == 4) {
+      const int P = pl.conv0_slabs;
+      const Conv0WArgs a0{state, w.dp0, w.c0, w.part0, B, w.am(AM_DP0, h)};
+      if (pl.conv1_wgrad == Conv1Wgrad::pair0) {
+        // conv1's whole-channel weight gradient (MFMA-bound) beside conv0's (VALU-bound): one
+        // workgroup of each per CU, one launch (ba3c_conv0.hip)
+        const Wg6Args wa = wa1();
+        {
+          ProbeScope ps(h, s, BA3C_K_CONV0_WGRAD);
+          HIP_TRY(launch_wgrad01_pair(s, wa, pl.conv1_slabs, a0, P));
+        }
+        h->merged[BA3C_K_CONV0_WGRAD] |= 1u << BA3C_K_CONV1_WGRAD;
+        CHECK(reduce_wgrad6<W1>(h, wa, pl.conv1_slabs, grad(h->idx_conv[1])));
+      } else {
+        ProbeScope ps(h, s, BA3C_K_CONV0_WGRAD);
+        HIP_TRY(launch_conv0s_wgrad(dim3(P), s, a0));
+      }
+      mp.M = Conv0W<2>::M;
+      return add_reduce(h, w.part0, P, mp);
+    }
+    // C == 12, or BA3C_GENERIC: the GEMM engine
+    const WgradPlan p = plan_wgrad(25 * CH, 32, B * 6400, 128, 32);
+    ConvWgrad<true, 84, 84, CH, 5, 5, 32, true> g{state, w.dp0, w.c0, w.part0, 1.0f / 255.0f, p.M, p.N, p.K, p.kchunk};
+    CHECK((launch_gemm<128, 32, 4, 1>(h, s, BA3C_K_CONV0_WGRAD, g, p.S)));
+    mp.M = p.M;
+    return add_reduce(h, w.part0, p.S, mp);
   }
-  // all (remaining) weight-gradient reductions: one launch, every gradient element written once
-  return finish();
-}
+};
 
 int run_heads(ba3c_handle* h, hipStream_t s, const float* prm, const Workspace& w, int B,
               const int64_t* action, const float* R, float beta, float explore, bool train,
@@ -1252,13 +1139,27 @@ int run_heads(ba3c_handle* h, hipStream_t s, const float* prm, const Workspace& 
   HIP_TRY(hipGetLastError());
   if (train && scalars && !fuse_scalars && defer_scalars) {
     h->scalars_args = ScalarsJob::Args{w.terms, B, beta, w.relu, scalars};
-    h->pend_scalars = true;      // launched by run_backward (conv3's input gradient or finish)
+    h->pend_scalars = true;      // launched by BackwardPass (conv3's input gradient or finish)
   } else if (train && scalars && !fuse_scalars) {
     ProbeScope ps(h, s, BA3C_K_SCALARS);
     hipLaunchKernelGGL(scalars_kernel, dim3(1), dim3(256), 0, s, w.terms, B, beta, w.relu, scalars);
     HIP_TRY(hipGetLastError());
   }
   return BA3C_OK;
+}
+
+// the optimizer id as a compile-time kernel index (apply_update_impl validates the id first)
+template <class F>
+int with_opt(int32_t opt, F&& f) {
+  switch (opt) {
+    case BA3C_OPT_ADAM: return f(std::integral_constant<int, 0>{});
+    case BA3C_OPT_GD: return f(std::integral_constant<int, 1>{});
+    case BA3C_OPT_ADAGRAD: return f(std::integral_constant<int, 2>{});
+    case BA3C_OPT_ADADELTA: return f(std::integral_constant<int, 3>{});
+    case BA3C_OPT_MOMENTUM: return f(std::integral_constant<int, 4>{});
+    case BA3C_OPT_RMS: return f(std::integral_constant<int, 5>{});
+    default: return fail(BA3C_ERR_INVALID, "unknown optimizer id");
+  }
 }
 
 bool check_ptr(const void* p) { return p != nullptr && (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -1391,36 +1292,35 @@ int ba3c_create(const ba3c_config* cfg, ba3c_handle** out) {
     return fail(BA3C_ERR_INVALID, "fc_neurons must be a multiple of 4*fc_splits (or 4*ps)");
   // launch-structure switches (each exercised by a GPU test; values outside the listed ones
   // are rejected rather than coerced, so an A/B run measures what it asked for)
+  Switches sw;
   struct Switch {
     const char* name;
     const char* digits;   // the accepted values
-    int value;            // the default, then what the environment sets
-    void (*set)(ba3c_handle*, int);
+    void (*set)(Switches&, int);
   };
-  Switch switches[] = {
-      {"BA3C_GENERIC", "01", 0, [](ba3c_handle* h, int v) { h->band = v == 0; }},
-      {"BA3C_C1PAIR", "012", 2, [](ba3c_handle* h, int v) { h->c1pair = v; }},
-      {"BA3C_SCALARS_RIDE", "01", 1, [](ba3c_handle* h, int v) { h->scalars_ride = v != 0; }},
-      {"BA3C_OVERLAP", "012", 2, [](ba3c_handle* h, int v) { h->overlap = v; }},
-      {"BA3C_MULTI", "01", 1, [](ba3c_handle* h, int v) { h->multi = v != 0; }},
-      {"BA3C_MULTI_BIG", "0123", 3, [](ba3c_handle* h, int v) { h->multi_big = v; }},
-      {"BA3C_FUSED_UPDATE", "01", 1, [](ba3c_handle* h, int v) { h->fused_update = v != 0; }},
-      {"BA3C_RING", "01", 1, [](ba3c_handle* h, int v) { h->ring = v != 0; }},
-      {"BA3C_CHAIN", "01", 1, [](ba3c_handle* h, int v) { h->chain_on = v != 0; }},
-      {"BA3C_C3W_RIDE", "012", 0, [](ba3c_handle* h, int v) { h->c3ride = v; }},
-      {"BA3C_FWD01", "01", 1, [](ba3c_handle* h, int v) { h->fwd01 = v != 0; }},
+  const Switch switches[] = {
+      {"BA3C_GENERIC", "01", [](Switches& w, int v) { w.generic = v != 0; }},
+      {"BA3C_C1PAIR", "02", [](Switches& w, int v) { w.c1pair = v; }},
+      {"BA3C_SCALARS_RIDE", "01", [](Switches& w, int v) { w.scalars_ride = v != 0; }},
+      {"BA3C_OVERLAP", "012", [](Switches& w, int v) { w.overlap = v; }},
+      {"BA3C_MULTI", "01", [](Switches& w, int v) { w.multi = v != 0; }},
+      {"BA3C_MULTI_BIG", "0123", [](Switches& w, int v) { w.multi_big = v; }},
+      {"BA3C_FUSED_UPDATE", "01", [](Switches& w, int v) { w.fused_update = v != 0; }},
+      {"BA3C_RING", "01", [](Switches& w, int v) { w.ring = v != 0; }},
+      {"BA3C_CHAIN", "01", [](Switches& w, int v) { w.chain = v != 0; }},
+      {"BA3C_FWD01", "01", [](Switches& w, int v) { w.fwd01 = v != 0; }},
   };
-  for (Switch& k : switches) {
+  for (const Switch& k : switches) {
     const char* e = getenv(k.name);
     if (!e) continue;
     if (!e[0] || e[1] || !strchr(k.digits, e[0]))
       return fail(BA3C_ERR_INVALID, std::string(k.name) + "=" + e + ": expected one digit of " + k.digits);
-    k.value = e[0] - '0';
+    k.set(sw, e[0] - '0');
   }
   ba3c_handle* h = new ba3c_handle();
   h->cfg = c;
-  for (const Switch& k : switches) k.set(h, k.value);
-  h->g6 = h->band;
+  h->sw = sw;
+  h->band = h->g6 = !sw.generic;
   {
     int dev = 0, n = 0;
     if (hipGetDevice(&dev) == hipSuccess &&
@@ -1584,8 +1484,9 @@ int ba3c_forward(ba3c_handle* h, void* stream, const float* params, const uint8_
   CHECK(flush_held(h, s));
   Workspace w = carve(h, workspace, batch, false);
   std::memset(h->merged, 0, sizeof(h->merged));
-  int r = h->cfg.channels == 4 ? run_forward<4>(h, s, params, state, batch, w, false)
-                               : run_forward<12>(h, s, params, state, batch, w, false);
+  const LaunchPlan pl = plan_launches(h->sw, batch, h->cfg.channels, h->cus, false);
+  int r = h->cfg.channels == 4 ? run_forward<4>(h, s, pl, params, state, batch, w, false)
+                               : run_forward<12>(h, s, pl, params, state, batch, w, false);
   if (r != BA3C_OK) return r;
   return run_heads(h, s, params, w, batch, nullptr, nullptr, 0.f, explore_factor, false, probs,
                    probsT, value);
@@ -1601,12 +1502,7 @@ static int train_grads_impl(ba3c_handle* h, void* stream, const float* params, c
 static int flush_reduce(ba3c_handle* h, hipStream_t s) {
   if (!h || !h->pend_reduce) return BA3C_OK;
   h->pend_reduce = false;
-  const ReduceJobs& jb = h->rjobs;
-  {
-    ProbeScope ps(h, h->pend_stream, BA3C_K_WGRAD_REDUCE);
-    hipLaunchKernelGGL(wgrad_reduce_all_kernel, dim3(jb.blk0[jb.n]), dim3(64 * RED_G), 0, h->pend_stream, jb);
-  }
-  HIP_TRY(hipGetLastError());
+  CHECK(launch_reduce_all(h, h->pend_stream, h->rjobs));
   if (s != h->pend_stream) {
     if (!h->ev_pend) HIP_TRY(hipEventCreateWithFlags(&h->ev_pend, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(h->ev_pend, h->pend_stream));
@@ -1627,13 +1523,7 @@ static int flush_held(ba3c_handle* h, hipStream_t s, bool order) {
     HIP_TRY(hipEventRecord(h->ev_pend, h->held_stream));
     HIP_TRY(hipStreamWaitEvent(s, h->ev_pend, 0));
   }
-  const ReduceJobs& jb = h->held_jobs;
-  {
-    ProbeScope ps(h, s, BA3C_K_WGRAD_REDUCE);
-    hipLaunchKernelGGL(wgrad_reduce_all_kernel, dim3(jb.blk0[jb.n]), dim3(64 * RED_G), 0, s, jb);
-  }
-  HIP_TRY(hipGetLastError());
-  return BA3C_OK;
+  return launch_reduce_all(h, s, h->held_jobs);
 }
 
 int ba3c_launch_held(ba3c_handle* h, void* stream) {
@@ -1692,22 +1582,23 @@ static int train_grads_impl(ba3c_handle* h, void* stream, const float* params, c
   Workspace w = carve(h, workspace, batch, true);
   // no memset of `grads`: the backward pass's single reduction launch writes every element
   // of every tensor (incl. conv0's zero-padded channels)
-  if (phase == 2)   // conv layers' backward on the workspace phase 1 left
-    return h->cfg.channels == 4 ? run_backward<4>(h, s, params, state, batch, w, grads, 2)
-                                : run_backward<12>(h, s, params, state, batch, w, grads, 2);
+  const LaunchPlan pl = plan_launches(h->sw, batch, h->cfg.channels, h->cus, true);
+  auto backward = [&] {
+    return h->cfg.channels == 4 ? BackwardPass<4>(h, s, pl, w, params, state, grads, batch, phase).run()
+                                : BackwardPass<12>(h, s, pl, w, params, state, grads, batch, phase).run();
+  };
+  if (phase == 2) return backward();   // conv layers' backward on the workspace phase 1 left
   std::memset(h->merged, 0, sizeof(h->merged));   // a new training pass
   // on the split path the weight-prep launch zeroes the ReLU counters
   if (!h->band) HIP_TRY(hipMemsetAsync(w.relu, 0, RELU_WORDS * 8, s));
-  int r = h->cfg.channels == 4 ? run_forward<4>(h, s, params, state, batch, w, true)
-                               : run_forward<12>(h, s, params, state, batch, w, true);
+  int r = h->cfg.channels == 4 ? run_forward<4>(h, s, pl, params, state, batch, w, true)
+                               : run_forward<12>(h, s, pl, params, state, batch, w, true);
   if (r != BA3C_OK) return r;
   // heads + loss + its gradient, fc1's split-K finish and (last workgroup) the TfDictOp scalars
   h->pend_scalars = false;
   CHECK(run_heads(h, s, params, w, batch, action, futurereward, entropy_beta, 1.0f, true, nullptr,
-                  nullptr, nullptr, scalars, phase != 2 && h->scalars_ride && h->g6));
-  if (h->cfg.channels == 4)
-    return run_backward<4>(h, s, params, state, batch, w, grads, phase);
-  return run_backward<12>(h, s, params, state, batch, w, grads, phase);
+                  nullptr, nullptr, scalars, phase != 2 && h->sw.scalars_ride && h->g6));
+  return backward();
 }
 
 int ba3c_clip_grads_range(ba3c_handle* h, void* stream, float* grads, void* workspace, int32_t t0,
@@ -1726,7 +1617,7 @@ int ba3c_clip_grads_range2(ba3c_handle* h, void* stream, float* grads, void* wor
   float* part = carve(h, workspace, 1, false).sumsq;
   const int c0 = h->table.chunk0[t0], nc = h->table.chunk0[t1] - c0;
   ProbeScope ps(h, s, BA3C_K_CLIP);
-  if (h->ctag && h->fused_update && nc <= h->cus && !(flags & BA3C_CLIP_NO_RESIDENCY)) {
+  if (h->ctag && h->sw.fused_update && nc <= h->cus && !(flags & BA3C_CLIP_NO_RESIDENCY)) {
     // one launch (tagged partials), bit-identical to the two below
     const UpdateSync us{h->ctag, reinterpret_cast<unsigned int*>(h->ctag + h->table.nchunks)};
     hipLaunchKernelGGL(clip_range_kernel, dim3(nc), dim3(256), 0, s, grads, h->table, c0, us);
@@ -1787,7 +1678,7 @@ static int apply_update_impl(ba3c_handle* h, void* stream, int32_t opt, float* p
   a.beta1 = hp->beta1;
   a.beta2 = hp->beta2;
   float* part = carve(h, workspace, 1, false).sumsq;  // batch-independent first region
-  const bool fused = fuse_clip && h->fused_update && h->utag && h->table.nchunks <= h->cus;
+  const bool fused = fuse_clip && h->sw.fused_update && h->utag && h->table.nchunks <= h->cus;
   if (RED_G == 4 && fused && h->pend_reduce && h->pend_stream == s && h->pend_grads == grads && chain_ok(h)) {
     // the pending reduction and this apply as one chained launch: the reduce workgroups
     // signal, the chunks wait for them before reading their gradient
@@ -1798,19 +1689,10 @@ static int apply_update_impl(ba3c_handle* h, void* stream, int32_t opt, float* p
     ca.a.clip_part = part;
     const dim3 gr(jb.blk0[jb.n]), gu(h->table.nchunks);
     h->merged[BA3C_K_UPDATE] |= 1u << BA3C_K_WGRAD_REDUCE;
-#define BA3C_RCU(O)                                                                                     \
-  launch_chain<false, ReduceJob, ClipUpdJob<O>>(s, CHAIN_REDUCE_UPDATE, 1, 2, 2, jb, gr, ca, gu, 0, dim3(0, 1, 1), h, \
-                                                BA3C_K_UPDATE, true)
-    switch (opt) {
-      case BA3C_OPT_ADAM: return BA3C_RCU(0);
-      case BA3C_OPT_GD: return BA3C_RCU(1);
-      case BA3C_OPT_ADAGRAD: return BA3C_RCU(2);
-      case BA3C_OPT_ADADELTA: return BA3C_RCU(3);
-      case BA3C_OPT_MOMENTUM: return BA3C_RCU(4);
-      case BA3C_OPT_RMS: return BA3C_RCU(5);
-      default: return fail(BA3C_ERR_INVALID, "unknown optimizer id");
-    }
-#undef BA3C_RCU
+    return with_opt(opt, [&](auto O) {
+      return launch_chain<false, ReduceJob, ClipUpdJob<decltype(O)::value>>(s, CHAIN_REDUCE_UPDATE, 1, 2, 2, jb, gr, ca, gu, 0,
+                                                           dim3(0, 1, 1), h, BA3C_K_UPDATE, true);
+    });
   }
   CHECK(flush_reduce(h, s));
   CHECK(flush_held(h, s));
@@ -1820,15 +1702,10 @@ static int apply_update_impl(ba3c_handle* h, void* stream, int32_t opt, float* p
     const UpdateSync us{h->utag, reinterpret_cast<unsigned int*>(h->utag + h->table.nchunks)};
     {
       ProbeScope ps(h, s, BA3C_K_UPDATE);
-      switch (opt) {
-        case BA3C_OPT_ADAM: hipLaunchKernelGGL(clip_update_kernel<0>, grid, dim3(256), 0, s, a, h->table, us); break;
-        case BA3C_OPT_GD: hipLaunchKernelGGL(clip_update_kernel<1>, grid, dim3(256), 0, s, a, h->table, us); break;
-        case BA3C_OPT_ADAGRAD: hipLaunchKernelGGL(clip_update_kernel<2>, grid, dim3(256), 0, s, a, h->table, us); break;
-        case BA3C_OPT_ADADELTA: hipLaunchKernelGGL(clip_update_kernel<3>, grid, dim3(256), 0, s, a, h->table, us); break;
-        case BA3C_OPT_MOMENTUM: hipLaunchKernelGGL(clip_update_kernel<4>, grid, dim3(256), 0, s, a, h->table, us); break;
-        case BA3C_OPT_RMS: hipLaunchKernelGGL(clip_update_kernel<5>, grid, dim3(256), 0, s, a, h->table, us); break;
-        default: return fail(BA3C_ERR_INVALID, "unknown optimizer id");
-      }
+      with_opt(opt, [&](auto O) {
+        hipLaunchKernelGGL(clip_update_kernel<decltype(O)::value>, grid, dim3(256), 0, s, a, h->table, us);
+        return BA3C_OK;
+      });
     }
     HIP_TRY(hipGetLastError());
     return BA3C_OK;   // the Adam device powers advanced inside the launch
@@ -1841,15 +1718,10 @@ static int apply_update_impl(ba3c_handle* h, void* stream, int32_t opt, float* p
   dim3 grid(h->table.nchunks);
   {
     ProbeScope ps(h, s, BA3C_K_UPDATE);
-    switch (opt) {
-      case BA3C_OPT_ADAM: hipLaunchKernelGGL(update_kernel<0>, grid, dim3(256), 0, s, a, h->table); break;
-      case BA3C_OPT_GD: hipLaunchKernelGGL(update_kernel<1>, grid, dim3(256), 0, s, a, h->table); break;
-      case BA3C_OPT_ADAGRAD: hipLaunchKernelGGL(update_kernel<2>, grid, dim3(256), 0, s, a, h->table); break;
-      case BA3C_OPT_ADADELTA: hipLaunchKernelGGL(update_kernel<3>, grid, dim3(256), 0, s, a, h->table); break;
-      case BA3C_OPT_MOMENTUM: hipLaunchKernelGGL(update_kernel<4>, grid, dim3(256), 0, s, a, h->table); break;
-      case BA3C_OPT_RMS: hipLaunchKernelGGL(update_kernel<5>, grid, dim3(256), 0, s, a, h->table); break;
-      default: return fail(BA3C_ERR_INVALID, "unknown optimizer id");
-    }
+    with_opt(opt, [&](auto O) {
+      hipLaunchKernelGGL(update_kernel<decltype(O)::value>, grid, dim3(256), 0, s, a, h->table);
+      return BA3C_OK;
+    });
   }
   HIP_TRY(hipGetLastError());
   if (opt == BA3C_OPT_ADAM && dev_powers) {
@@ -2158,11 +2030,11 @@ int ba3c_device_errors(ba3c_handle* h, uint32_t* flags) {
   HIP_TRY(hipMemcpy(&e, h->utag + h->table.nchunks, sizeof(e), hipMemcpyDeviceToHost));
   if (h->ctag) HIP_TRY(hipMemcpy(&e2, h->ctag + h->table.nchunks, sizeof(e2), hipMemcpyDeviceToHost));
   if (h->chain) HIP_TRY(hipMemcpy(&e3, h->chain + 4 * CHAIN_SITES, sizeof(e3), hipMemcpyDeviceToHost));
-  if (e3 && h->chain_on) {
+  if (e3 && h->sw.chain) {
     // a chained wait gave up: a late signal may have landed after the last waiter reset the
     // site's words, so they can no longer be trusted.  Zero them from the host and stop
     // chaining on this handle (the error bit stays set)
-    h->chain_on = false;
+    h->sw.chain = false;
     HIP_TRY(hipMemset(h->chain, 0, 4 * CHAIN_SITES * sizeof(unsigned)));
     HIP_TRY(hipMemset(h->spread, 0, CHAIN_SPREAD * CHAIN_STRIDE * sizeof(unsigned)));
   }

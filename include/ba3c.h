@@ -173,9 +173,8 @@ int ba3c_train_grads_phase(ba3c_handle* h, void* stream, const float* params, co
  * variables' gradients of OpenAIGym/train.py:598-606 (their aggregation starts from here). */
 int ba3c_launch_held(ba3c_handle* h, void* stream);
 /* Record the HIP event `event` (a hipEvent_t of the caller's, NULL: none) on the pass's stream
- * in every later phase-2 pass, right after conv3's input-gradient launch and its weight
- * gradient's (with BA3C_C3W_RIDE set the weight gradient is a job of conv2's launch and runs
- * after the event; the event only has to follow phase 1): the N>1 step starts the fc1 + heads
+ * in every later phase-2 pass, right after conv3's input- and weight-gradient launches (the
+ * event only has to follow phase 1): the N>1 step starts the fc1 + heads
  * bucket's exchange from there, so its collective's workgroups take CUs at the boundary before
  * conv2's launch (short, non-persistent workgroups the dispatcher rebalances) instead of
  * beside conv3's persistent ones. */

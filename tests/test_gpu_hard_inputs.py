@@ -233,12 +233,11 @@ def test_greedy_eval_action_matches_numpy_argmax():
     np.testing.assert_array_equal(got, want)
 
 
-@pytest.mark.parametrize("var,base,mode", [("BA3C_C1PAIR", None, "0"), ("BA3C_C1PAIR", None, "1"),
-                                           ("BA3C_SCALARS_RIDE", "0", "1")])
+@pytest.mark.parametrize("var,base,mode", [("BA3C_C1PAIR", None, "0"), ("BA3C_SCALARS_RIDE", "0", "1")])
 def test_large_batch_launch_structures_match_default(monkeypatch, var, base, mode):
     """conv1's large-batch backward launch structure (BA3C_C1PAIR): 2 (default) = input gradient
-    alone, then conv1's weight gradient beside conv0's in one launch; 1 = conv1 input + weight
-    gradients in one launch; 0 = separate launches.  Every variant sums the same slabs in the
+    alone, then conv1's weight gradient beside conv0's in one launch; 0 = separate launches.
+    Every variant sums the same slabs in the
     same order (one per CU in the pair geometry), so the gradients, scalars and dP0 are
     bit-identical — B=1024, 4 images per ring-walk workgroup.  BA3C_SCALARS_RIDE: the TfDictOp
     scalar reduction in its own launch after the heads (0) or as one workgroup of conv3's
