@@ -48,9 +48,9 @@ render: pixel (y, x) takes the first match of: ball (in_play, 255), paddle (255)
 a step returns is the frame AFTER the step, so on `over` it is the new episode's first frame
 (GymEnv's auto-restart; what HistoryFramePlayer / ba3c_history_push expect).
 """
-import ctypes
-
 import numpy as np
+
+from .gamevec import GameVec
 
 H = W = 84
 ROWS, COLS = 6, 14
@@ -183,113 +183,13 @@ def render_numpy(game):
     return frame
 
 
-class BreakoutVec(object):
-    """E GridBreakout simulators in HBM with SyntheticAtari's interface (`E`, `A`, `frames()`,
-    `step(actions) -> frames, reward, over`); every step is one HIP launch
-    (ba3c_breakout_step).  `step_into(actions, hist)` also pushes the new frames into a
-    FrameHistory(hist_len=4, channels=1) in that same launch.  `last_ep_score` / `last_over`
-    expose the episodes the last step finished.  A non-default `frame_skip` (K or an inclusive
-    (lo, hi)) / `sticky` (a probability) makes every step one DECISION of ba3c_amd.frameskip,
-    still one launch (ba3c_breakout_step_skip), with the aux rows in `aux`; `limit` counts game
-    steps either way."""
+class BreakoutVec(GameVec):
+    """E GridBreakout simulators in HBM (ba3c_amd.gamevec.GameVec): every step is one HIP launch
+    (ba3c_breakout_step).  A non-default `frame_skip` (K or an inclusive (lo, hi)) / `sticky` (a
+    probability) makes every step one DECISION of ba3c_amd.frameskip (ba3c_breakout_step_skip)."""
 
     A = NUM_ACTIONS
-
-    def __init__(self, n_envs, seed=0, limit=DEFAULT_LIMIT, device="cuda", frame_skip=1, sticky=0.0):
-        import torch
-
-        from . import _lib, frameskip
-        self.lib = _lib.load()
-        self._check = _lib.check
-        self._torch = torch
-        self.E = int(n_envs)
-        self.limit = int(limit)
-        if self.E < 1 or self.limit < 1:
-            raise ValueError("n_envs and limit must be >= 1")
-        self.device = torch.device(device)
-        dev = self.device
-        self.game = torch.from_numpy(initial_game(self.E, seed)).to(dev)
-        self.reward = torch.zeros(self.E, dtype=torch.float64, device=dev)
-        self.over = torch.zeros(self.E, dtype=torch.uint8, device=dev)
-        self.ep_score = torch.zeros(self.E, dtype=torch.int32, device=dev)
-        self.frame = torch.zeros((self.E, H, W, 1), dtype=torch.uint8, device=dev)
-        # (lo, hi, q16) of ba3c_amd.frameskip, or None: the plain one-step launch and no aux rows
-        self.skip = frameskip.setting(frame_skip, sticky)
-        self.aux = None
-        if self.skip is not None:
-            self.aux = torch.from_numpy(frameskip.initial_aux(self.E, seed)).to(dev)
-        self._palette = None               # PALETTE on the device, uploaded by the first view()
-
-    def _ptr(self, t):
-        return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-    def _stream(self):
-        return ctypes.c_void_p(self._torch.cuda.current_stream().cuda_stream)
-
-    def _actions(self, actions):
-        a = actions.to(device=self.device, dtype=self._torch.int64).contiguous()
-        assert a.shape == (self.E,)
-        return a
-
-    def frames(self):
-        """[E,84,84,1] uint8 frames of the current state (a new tensor)."""
-        out = self._torch.empty_like(self.frame)
-        self._check(self.lib.ba3c_breakout_render(self._stream(), self._ptr(self.game), self.E,
-                                                  self._ptr(out), None))
-        return out
-
-    def reset_history(self, hist):
-        """Start `hist` (FrameHistory 4x1) from the current frames: zeros + frame."""
-        self._check_hist(hist)
-        self._check(self.lib.ba3c_breakout_render(self._stream(), self._ptr(self.game), self.E,
-                                                  None, self._ptr(hist.state)))
-        return hist.state
-
-    def _check_hist(self, hist):
-        if (hist.H, hist.c, hist.E) != (4, 1, self.E) or not hist.state.is_contiguous():
-            raise ValueError("the fused push needs a FrameHistory(n_envs=%d, hist_len=4, channels=1)"
-                             % self.E)
-
-    def _step(self, actions, frame, state):
-        a = self._actions(actions)
-        if self.skip is None:
-            self._check(self.lib.ba3c_breakout_step(
-                self._stream(), self._ptr(self.game), self._ptr(a), self.E, self.limit,
-                self._ptr(self.reward), self._ptr(self.over), self._ptr(self.ep_score),
-                self._ptr(frame), self._ptr(state)))
-        else:
-            lo, hi, q16 = self.skip
-            self._check(self.lib.ba3c_breakout_step_skip(
-                self._stream(), self._ptr(self.game), self._ptr(self.aux), self._ptr(a), self.E,
-                self.limit, lo, hi, q16, self._ptr(self.reward), self._ptr(self.over),
-                self._ptr(self.ep_score), self._ptr(frame), self._ptr(state)))
-        return self.reward, self.over.view(self._torch.bool)
-
-    def step(self, actions):
-        """-> (frames [E,84,84,1] uint8, reward float64 [E], over bool [E]); the tensors are
-        this object's buffers, overwritten by the next step."""
-        reward, over = self._step(actions, self.frame, None)
-        return self.frame, reward, over
-
-    def step_into(self, actions, hist):
-        """Step and push the new frames into `hist.state` in the same launch.
-        -> (reward float64 [E], over bool [E])."""
-        self._check_hist(hist)
-        return self._step(actions, None, hist.state)
-
-    def view(self, scale=1, sel=None, hud=None):
-        """The colour view of the current games (ba3c_amd.view.view_numpy is its statement):
-        torch.uint8 [n, Hc*scale, 84*scale, 3] on the device, one launch (ba3c_breakout_view);
-        sel: simulator indices (None: all), hud: uint8 [n, 20] or None.  Reads `game` only."""
-        from .view import device_view
-        return device_view(self, self.lib.ba3c_breakout_view, PALETTE, scale, sel, hud)
-
-    @property
-    def last_over(self):
-        return self.over.view(self._torch.bool)
-
-    @property
-    def last_ep_score(self):
-        """(ep_score int32 [E], over bool [E]) of the last step: ep_score[e] is the finished
-        episode's score where over[e], stale elsewhere."""
-        return self.ep_score, self.last_over
+    PALETTE = PALETTE
+    STEP, DECIDE = "ba3c_breakout_step", "ba3c_breakout_step_skip"
+    RENDER, VIEW = "ba3c_breakout_render", "ba3c_breakout_view"
+    initial_game = staticmethod(initial_game)

@@ -92,8 +92,6 @@ decisions: decide(mirror(g), mirror_aux(x), (b, a)) == mirror(decide(g, x, (a, b
 ep_scores negated.  Had both sides drawn from one generator, the order of the two draws would
 have told them apart.
 """
-import ctypes
-
 import numpy as np
 
 from . import boxing, frameskip
@@ -101,6 +99,7 @@ from .boxing import (AX, AX0, AY, AY0, A_CD, A_SCORE, CLOCK, COOLDOWN, DEFAULT_L
                      H, KNOCK, KO, LEFT_MASK, NOOP, NUM_ACTIONS, OX, OX0, OY, OY0, O_CD, O_SCORE, PALETTE,
                      RIGHT_MASK, RNG, T, UP_MASK, W, X_MAX, X_MIN, Y_MAX, Y_MIN, _clamp, _pts,
                      initial_game)
+from .gamevec import GameVec
 
 STEP = 2                                 # both sides move 2 px per step
 MIRROR = 78                              # x -> 78 - x: body top-lefts 4..74 map onto themselves
@@ -303,91 +302,25 @@ def render_numpy(game):
     return np.concatenate([boxing.render_numpy(game), boxing.render_numpy(mirror_rows(game))])
 
 
-class BoxingDuelVec(object):
-    """G two-player GridBoxing games in HBM: E = 2G players with BoxingVec's interface (`E`,
-    `A`, `frames()`, `reset_history`, `step(actions) -> frames, reward, over`,
-    `step_into(actions, hist)`, `last_over`, `last_ep_score`, `game`, `ep_score`), all over the
-    E players in player order; `game` is [G,16].  Every step is one HIP launch
-    (ba3c_boxing_duel_step).  No frame skip, no sticky actions, the fixed start: those are
-    BoxingDuelDecisionVec's."""
+class BoxingDuelVec(GameVec):
+    """G two-player GridBoxing games in HBM: E = 2G players with BoxingVec's interface
+    (ba3c_amd.gamevec.GameVec), all over the E players in player order; `game` is [G,16].  Every
+    step is one HIP launch (ba3c_boxing_duel_step).  No frame skip, no sticky actions, the fixed
+    start: those are BoxingDuelDecisionVec's."""
 
     A = NUM_ACTIONS
-    skip = start = aux = None              # the one-step launch: no decision setting, no aux rows
+    PALETTE = PALETTE
+    PLAYERS, COUNT = 2, "n_games"
+    STEP, DECIDE = "ba3c_boxing_duel_step", "ba3c_boxing_duel_decide"
+    RENDER, VIEW = "ba3c_boxing_duel_render", "ba3c_boxing_view"
+    initial_aux = staticmethod(initial_aux)
 
     def __init__(self, n_games, seed=0, limit=DEFAULT_LIMIT, device="cuda"):
-        self._init(n_games, seed, limit, device)
+        self._counts(n_games, limit)
+        self._alloc(seed, device)
 
-    def _init(self, n_games, seed, limit, device):
-        import torch
-
-        from . import _lib
-        self.lib = _lib.load()
-        self._check = _lib.check
-        self._torch = torch
-        self.G = int(n_games)
-        self.E = 2 * self.G
-        self.limit = int(limit)
-        if self.G < 1 or self.limit < 1:
-            raise ValueError("n_games and limit must be >= 1")
-        self.device = torch.device(device)
-        dev = self.device
-        if self.skip is not None:
-            self.aux = torch.from_numpy(initial_aux(self.G, seed)).to(dev)
-        self.game = torch.from_numpy(initial_rows(self.G, seed, self.start)).to(dev)
-        self.reward = torch.zeros(self.E, dtype=torch.float64, device=dev)
-        self.over = torch.zeros(self.E, dtype=torch.uint8, device=dev)
-        self.ep_score = torch.zeros(self.E, dtype=torch.int32, device=dev)
-        self.frame = torch.zeros((self.E, H, W, 1), dtype=torch.uint8, device=dev)
-        self._palette = None               # PALETTE on the device, uploaded by the first view()
-
-    def _ptr(self, t):
-        return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-    def _stream(self):
-        return ctypes.c_void_p(self._torch.cuda.current_stream().cuda_stream)
-
-    def frames(self):
-        """[E,84,84,1] uint8 frames of the current state, each player's own (a new tensor)."""
-        out = self._torch.empty_like(self.frame)
-        self._check(self.lib.ba3c_boxing_duel_render(self._stream(), self._ptr(self.game), self.G,
-                                                     self._ptr(out), None))
-        return out
-
-    def reset_history(self, hist):
-        """Start `hist` (FrameHistory 4x1 over the E players) from the current frames."""
-        self._check_hist(hist)
-        self._check(self.lib.ba3c_boxing_duel_render(self._stream(), self._ptr(self.game), self.G,
-                                                     None, self._ptr(hist.state)))
-        return hist.state
-
-    def _check_hist(self, hist):
-        if (hist.H, hist.c, hist.E) != (4, 1, self.E) or not hist.state.is_contiguous():
-            raise ValueError("the fused push needs a FrameHistory(n_envs=%d, hist_len=4, channels=1)"
-                             % self.E)
-
-    def _step(self, actions, frame, state):
-        a = actions.to(device=self.device, dtype=self._torch.int64).contiguous()
-        assert a.shape == (self.E,)
-        self._launch(a, frame, state)
-        return self.reward, self.over.view(self._torch.bool)
-
-    def _launch(self, a, frame, state):
-        self._check(self.lib.ba3c_boxing_duel_step(
-            self._stream(), self._ptr(self.game), self._ptr(a), self.G, self.limit,
-            self._ptr(self.reward), self._ptr(self.over), self._ptr(self.ep_score),
-            self._ptr(frame), self._ptr(state)))
-
-    def step(self, actions):
-        """-> (frames [E,84,84,1] uint8, reward float64 [E], over bool [E]); the tensors are
-        this object's buffers, overwritten by the next step."""
-        reward, over = self._step(actions, self.frame, None)
-        return self.frame, reward, over
-
-    def step_into(self, actions, hist):
-        """Step and push every player's new frame into `hist.state` in the same launch.
-        -> (reward float64 [E], over bool [E])."""
-        self._check_hist(hist)
-        return self._step(actions, None, hist.state)
+    def initial_game(self, n_games, seed):
+        return initial_rows(n_games, seed, self.start)
 
     def mirrored_game(self):
         """mirror_rows of `game` as a new tensor on the device (a few tensor ops)."""
@@ -402,22 +335,9 @@ class BoxingDuelVec(object):
         (ba3c_amd.view.view_numpy of the rows with GridBoxing's palette): torch.uint8
         [n, Hc*scale, 84*scale, 3] through ba3c_boxing_view; sel: game indices (None: all G).
         side="b": the world as side B sees it, the same view of the mirrored rows."""
-        from .view import device_view
         if side not in ("a", "b"):
             raise ValueError("side must be 'a' or 'b'")
-        rows = self.mirrored_game() if side == "b" else None
-        return device_view(self, self.lib.ba3c_boxing_view, PALETTE, scale, sel, hud, n_rows=self.G,
-                           rows=rows)
-
-    @property
-    def last_over(self):
-        return self.over.view(self._torch.bool)
-
-    @property
-    def last_ep_score(self):
-        """(ep_score int32 [E], over bool [E]) of the last step: ep_score[p] is player p's score
-        of the finished episode where over[p], stale elsewhere."""
-        return self.ep_score, self.last_over
+        return GameVec.view(self, scale, sel, hud, self.mirrored_game() if side == "b" else None)
 
 
 class BoxingDuelDecisionVec(BoxingDuelVec):
@@ -433,16 +353,7 @@ class BoxingDuelDecisionVec(BoxingDuelVec):
         start = check_start(start)
         if skip is not None or start != FIXED_START:
             self.skip, self.start = skip or (1, 1, 0), start
-        self._init(n_games, seed, limit, device)
-
-    def _launch(self, a, frame, state):
-        if self.skip is None:
-            return BoxingDuelVec._launch(self, a, frame, state)
-        (lo, hi, q16), (h_lo, h_hi) = self.skip, self.start
-        self._check(self.lib.ba3c_boxing_duel_decide(
-            self._stream(), self._ptr(self.game), self._ptr(self.aux), self._ptr(a), self.G,
-            self.limit, lo, hi, q16, h_lo, h_hi, self._ptr(self.reward), self._ptr(self.over),
-            self._ptr(self.ep_score), self._ptr(frame), self._ptr(state)))
+        BoxingDuelVec.__init__(self, n_games, seed, limit, device)
 
 
 class _PolicySide(object):

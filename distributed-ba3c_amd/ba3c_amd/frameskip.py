@@ -3,7 +3,7 @@ policy DECISION does to a simulator.  ALE's `-v0` ids run each chosen action for
 frames drawn per decision and, with some probability per frame, repeat the previous frame's
 action instead of the chosen one ("sticky" actions); this module states that ONCE, over the
 games' own `step_numpy`, and is the oracle of the HIP kernel (csrc/ba3c_envkernel.h:
-env_skip_kernel, behind ba3c_breakout_step_skip / ba3c_boxing_step_skip) and of
+sim_kernel<SoloSim<Rules>, true>, behind ba3c_breakout_step_skip / ba3c_boxing_step_skip) and of
 `ba3c_amd.envs.FrameSkipPlayer`.  It restates no rule of either game.
 
 The 16-int game rows are full and their layout is public, so a decision keeps its own state in

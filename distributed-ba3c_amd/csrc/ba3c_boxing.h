@@ -6,7 +6,7 @@
 // game[e] = [ax, ay, ox, oy, a_cd, o_cd, a_score, o_score, t, rng, 0, 0, 0, 0, 0, 0],
 // 16 int32 = 64 bytes; a* is the agent, o* the opponent.
 //
-// The launch is env_kernel<BoxingRules> (ba3c_envkernel.h: one 256-thread workgroup per
+// The launch is sim_kernel<SoloSim<BoxingRules>, .> (ba3c_envkernel.h: one 256-thread workgroup per
 // simulator, the skeleton GridBreakout shares); this file holds the game's step and pixel rules.
 #pragma once
 #include "ba3c_envkernel.h"
@@ -90,7 +90,7 @@ __device__ __forceinline__ int32_t bx_step(BoxingGame& g, int64_t a, int32_t lim
   return reward;
 }
 
-// The game as ba3c_envkernel.h's env_kernel takes it.
+// The game as ba3c_envkernel.h's sim_kernel takes it.
 struct BoxingRules {
   using Game = BoxingGame;
   // boxing.py: render_numpy, for the pixels of one frame row.  A boxer's body and arm are

@@ -6,7 +6,7 @@
 //
 // game[e] = [px, bx, by, vx, vy, in_play, lives, score, t, rng, b0..b5], 16 int32 = 64 bytes.
 //
-// The launch is env_kernel<BreakoutRules> (ba3c_envkernel.h: one 256-thread workgroup per
+// The launch is sim_kernel<SoloSim<BreakoutRules>, .> (ba3c_envkernel.h: one 256-thread workgroup per
 // simulator, the skeleton GridBoxing shares); this file holds the game's step and pixel rules.
 #pragma once
 #include "ba3c_envkernel.h"
@@ -115,7 +115,7 @@ __device__ __forceinline__ uint32_t bk_pixel(const BreakoutGame& g, int y, int x
   return 0u;
 }
 
-// The game as ba3c_envkernel.h's env_kernel takes it.
+// The game as ba3c_envkernel.h's sim_kernel takes it.
 struct BreakoutRules {
   using Game = BreakoutGame;
   struct Row {

@@ -1199,59 +1199,58 @@ int rccl_fail(ncclResult_t e, const char* what) {
 }
 }  // namespace
 
-// The two entry points every on-device game has (Rules: ba3c_envkernel.h).
-template <class Rules>
-static int env_step(void* stream, int32_t* game, const int64_t* action, int32_t n_envs, int32_t limit,
-                    double* reward, uint8_t* over, int32_t* ep_score, uint8_t* frame, uint8_t* state) {
-  if (!game || !action) return fail(BA3C_ERR_INVALID, "null game / action pointer");
-  if (!reward || !over || !ep_score) return fail(BA3C_ERR_INVALID, "null output pointer");
-  if (n_envs < 1 || limit < 1) return fail(BA3C_ERR_INVALID, "n_envs and limit must be >= 1");
-  if (!check_ptr(game) || (state && !check_ptr(state)) || (reinterpret_cast<uintptr_t>(frame) & 3))
-    return fail(BA3C_ERR_INVALID, "game / state must be 16-byte and frame 4-byte aligned");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  EnvArgs a{game, action, limit, reward, over, ep_score, frame, state};
-  hipLaunchKernelGGL(env_kernel<Rules>, dim3(n_envs), dim3(256), 0, s, a);
-  HIP_TRY(hipGetLastError());
-  return BA3C_OK;
-}
+// What a decision entry point takes beyond a step's arguments, as the caller gave it.
+struct Decision {
+  int32_t* aux;
+  int32_t skip_lo, skip_hi, sticky_q16;
+  int32_t start_lo = 19, start_hi = 19;   // the fixed start: what a game without drawn starts passes
+};
 
-template <class Rules>
-static int env_render(void* stream, const int32_t* game, int32_t n_envs, uint8_t* frame, uint8_t* state) {
-  if (!game) return fail(BA3C_ERR_INVALID, "null game pointer");
-  if (n_envs < 1) return fail(BA3C_ERR_INVALID, "n_envs must be >= 1");
-  if (!check_ptr(game) || (state && !check_ptr(state)) || (reinterpret_cast<uintptr_t>(frame) & 3))
+// The argument checks of every step / decision / render entry point of the games, in one order;
+// the first that fails is the one reported.  render: no action, no outputs, no limit.  count: the
+// entry point's name of a.rows; aux_align: of a decision's aux rows, in bytes.
+static int game_check(const EnvArgs& a, const char* count, bool render, const Decision* d, size_t aux_align) {
+  if (render ? !a.game : !a.game || !a.action)
+    return fail(BA3C_ERR_INVALID, render ? "null game pointer" : "null game / action pointer");
+  if (d && !d->aux) return fail(BA3C_ERR_INVALID, "null aux pointer");
+  if (!render && (!a.reward || !a.over || !a.ep_score)) return fail(BA3C_ERR_INVALID, "null output pointer");
+  if (a.rows < 1 || a.limit < 1)
+    return fail(BA3C_ERR_INVALID, std::string(count) + (render ? "" : " and limit") + " must be >= 1");
+  if (!check_ptr(a.game) || (a.state && !check_ptr(a.state)) || (reinterpret_cast<uintptr_t>(a.frame) & 3))
     return fail(BA3C_ERR_INVALID, "game / state must be 16-byte and frame 4-byte aligned");
-  if (!frame && !state) return BA3C_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  // render only: the kernel never writes the row when action is null
-  EnvArgs a{const_cast<int32_t*>(game), nullptr, 1, nullptr, nullptr, nullptr, frame, state};
-  hipLaunchKernelGGL(env_kernel<Rules>, dim3(n_envs), dim3(256), 0, s, a);
-  HIP_TRY(hipGetLastError());
-  return BA3C_OK;
-}
-
-// One decision of ba3c_amd/frameskip.py for every simulator (env_skip_kernel).
-template <class Rules>
-static int env_step_skip(void* stream, int32_t* game, int32_t* aux, const int64_t* action, int32_t n_envs,
-                         int32_t limit, int32_t skip_lo, int32_t skip_hi, int32_t sticky_q16, double* reward,
-                         uint8_t* over, int32_t* ep_score, uint8_t* frame, uint8_t* state) {
-  if (!game || !action) return fail(BA3C_ERR_INVALID, "null game / action pointer");
-  if (!aux) return fail(BA3C_ERR_INVALID, "null aux pointer");
-  if (!reward || !over || !ep_score) return fail(BA3C_ERR_INVALID, "null output pointer");
-  if (n_envs < 1 || limit < 1) return fail(BA3C_ERR_INVALID, "n_envs and limit must be >= 1");
-  if (!check_ptr(game) || (state && !check_ptr(state)) || (reinterpret_cast<uintptr_t>(frame) & 3))
-    return fail(BA3C_ERR_INVALID, "game / state must be 16-byte and frame 4-byte aligned");
-  if (reinterpret_cast<uintptr_t>(aux) & 7) return fail(BA3C_ERR_INVALID, "aux must be 8-byte aligned");
-  if (skip_lo < 1 || skip_hi < skip_lo || skip_hi > 16)
+  if (!d) return BA3C_OK;
+  if (reinterpret_cast<uintptr_t>(d->aux) & (aux_align - 1))
+    return fail(BA3C_ERR_INVALID, "aux must be " + std::to_string(aux_align) + "-byte aligned");
+  if (d->skip_lo < 1 || d->skip_hi < d->skip_lo || d->skip_hi > 16)
     return fail(BA3C_ERR_INVALID, "frame skip must satisfy 1 <= skip_lo <= skip_hi <= 16");
-  if (sticky_q16 < 0 || sticky_q16 > 65536)
+  if (d->sticky_q16 < 0 || d->sticky_q16 > 65536)
     return fail(BA3C_ERR_INVALID, "sticky_q16 must be in [0, 65536]");
+  if (d->start_lo < 4 || d->start_hi < d->start_lo || d->start_hi > 19)
+    return fail(BA3C_ERR_INVALID, "start half-gap must satisfy 4 <= start_lo <= start_hi <= 19");
+  return BA3C_OK;
+}
+
+// Every step / decision / render entry point of the games (Sim: ba3c_envkernel.h): the checks,
+// then sim_kernel over a.rows rows.  d: a decision's arguments (null: a step, or with a null
+// a.action and render set, a render, which never writes the row).
+template <class Sim>
+static int game_launch(void* stream, const EnvArgs& a, const Decision* d = nullptr, bool render = false) {
+  if (int rc = game_check(a, Sim::PLAYERS == 1 ? "n_envs" : "n_games", render, d, alignof(typename Sim::Aux)))
+    return rc;
+  if (render && !a.frame && !a.state) return BA3C_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  EnvArgs a{game, action, limit, reward, over, ep_score, frame, state};
-  EnvSkipArgs k{aux, skip_lo, (uint32_t)(skip_hi - skip_lo + 1), (uint32_t)sticky_q16};
-  hipLaunchKernelGGL(env_skip_kernel<Rules>, dim3(n_envs), dim3(256), 0, s, a, k);
+  const Decision v = d ? *d : Decision{nullptr, 1, 1, 0};
+  const DuelDecideArgs all{{v.aux, v.skip_lo, (uint32_t)(v.skip_hi - v.skip_lo + 1), (uint32_t)v.sticky_q16},
+                           v.start_lo, (uint32_t)(v.start_hi - v.start_lo + 1)};
+  const typename Sim::DecideArgs& k = all;            // a game without drawn starts takes the base
+  const auto kernel = d ? sim_kernel<Sim, true> : sim_kernel<Sim, false>;
+  hipLaunchKernelGGL(kernel, dim3(a.rows), dim3(256), 0, s, a, k);
   HIP_TRY(hipGetLastError());
   return BA3C_OK;
+}
+
+static EnvArgs render_args(const int32_t* game, int32_t n, uint8_t* frame, uint8_t* state) {
+  return EnvArgs{const_cast<int32_t*>(game), nullptr, 1, n, nullptr, nullptr, nullptr, frame, state};
 }
 
 // The colour view of selected simulators (env_view_kernel; ba3c_amd/view.py is its oracle).
@@ -1870,95 +1869,63 @@ int ba3c_history_push(void* stream, const uint8_t* frame, uint8_t* state, const 
 int ba3c_breakout_step(void* stream, int32_t* game, const int64_t* action, int32_t n_envs,
                        int32_t limit, double* reward, uint8_t* over, int32_t* ep_score,
                        uint8_t* frame, uint8_t* state) {
-  return env_step<BreakoutRules>(stream, game, action, n_envs, limit, reward, over, ep_score, frame, state);
+  return game_launch<SoloSim<BreakoutRules>>(stream, {game, action, limit, n_envs, reward, over, ep_score,
+                                                      frame, state});
 }
 
 int ba3c_breakout_render(void* stream, const int32_t* game, int32_t n_envs, uint8_t* frame,
                          uint8_t* state) {
-  return env_render<BreakoutRules>(stream, game, n_envs, frame, state);
+  return game_launch<SoloSim<BreakoutRules>>(stream, render_args(game, n_envs, frame, state), nullptr, true);
 }
 
 int ba3c_boxing_step(void* stream, int32_t* game, const int64_t* action, int32_t n_envs,
                      int32_t limit, double* reward, uint8_t* over, int32_t* ep_score,
                      uint8_t* frame, uint8_t* state) {
-  return env_step<BoxingRules>(stream, game, action, n_envs, limit, reward, over, ep_score, frame, state);
+  return game_launch<SoloSim<BoxingRules>>(stream, {game, action, limit, n_envs, reward, over, ep_score,
+                                                    frame, state});
 }
 
+// One decision of ba3c_amd/frameskip.py for every simulator.
 int ba3c_breakout_step_skip(void* stream, int32_t* game, int32_t* aux, const int64_t* action, int32_t n_envs,
                             int32_t limit, int32_t skip_lo, int32_t skip_hi, int32_t sticky_q16,
                             double* reward, uint8_t* over, int32_t* ep_score, uint8_t* frame,
                             uint8_t* state) {
-  return env_step_skip<BreakoutRules>(stream, game, aux, action, n_envs, limit, skip_lo, skip_hi, sticky_q16,
-                                      reward, over, ep_score, frame, state);
+  const Decision d{aux, skip_lo, skip_hi, sticky_q16};
+  return game_launch<SoloSim<BreakoutRules>>(stream, {game, action, limit, n_envs, reward, over, ep_score,
+                                                      frame, state}, &d);
 }
 
 int ba3c_boxing_step_skip(void* stream, int32_t* game, int32_t* aux, const int64_t* action, int32_t n_envs,
                           int32_t limit, int32_t skip_lo, int32_t skip_hi, int32_t sticky_q16,
                           double* reward, uint8_t* over, int32_t* ep_score, uint8_t* frame,
                           uint8_t* state) {
-  return env_step_skip<BoxingRules>(stream, game, aux, action, n_envs, limit, skip_lo, skip_hi, sticky_q16,
-                                    reward, over, ep_score, frame, state);
+  const Decision d{aux, skip_lo, skip_hi, sticky_q16};
+  return game_launch<SoloSim<BoxingRules>>(stream, {game, action, limit, n_envs, reward, over, ep_score,
+                                                    frame, state}, &d);
 }
 
 int ba3c_boxing_render(void* stream, const int32_t* game, int32_t n_envs, uint8_t* frame,
                        uint8_t* state) {
-  return env_render<BoxingRules>(stream, game, n_envs, frame, state);
+  return game_launch<SoloSim<BoxingRules>>(stream, render_args(game, n_envs, frame, state), nullptr, true);
 }
 
 int ba3c_boxing_duel_step(void* stream, int32_t* game, const int64_t* action, int32_t n_games, int32_t limit,
                           double* reward, uint8_t* over, int32_t* ep_score, uint8_t* frame, uint8_t* state) {
-  if (!game || !action) return fail(BA3C_ERR_INVALID, "null game / action pointer");
-  if (!reward || !over || !ep_score) return fail(BA3C_ERR_INVALID, "null output pointer");
-  if (n_games < 1 || limit < 1) return fail(BA3C_ERR_INVALID, "n_games and limit must be >= 1");
-  if (!check_ptr(game) || (state && !check_ptr(state)) || (reinterpret_cast<uintptr_t>(frame) & 3))
-    return fail(BA3C_ERR_INVALID, "game / state must be 16-byte and frame 4-byte aligned");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  DuelArgs a{game, action, n_games, limit, reward, over, ep_score, frame, state};
-  hipLaunchKernelGGL(duel_kernel, dim3(n_games), dim3(256), 0, s, a);
-  HIP_TRY(hipGetLastError());
-  return BA3C_OK;
+  return game_launch<DuelSim>(stream, {game, action, limit, n_games, reward, over, ep_score, frame, state});
 }
 
-// One decision of ba3c_amd/duel.py (decide_numpy) for every game (duel_decide_kernel).
+// One decision of ba3c_amd/duel.py (decide_numpy) for every game.
 int ba3c_boxing_duel_decide(void* stream, int32_t* game, int32_t* aux, const int64_t* action, int32_t n_games,
                             int32_t limit, int32_t skip_lo, int32_t skip_hi, int32_t sticky_q16,
                             int32_t start_lo, int32_t start_hi, double* reward, uint8_t* over,
                             int32_t* ep_score, uint8_t* frame, uint8_t* state) {
-  if (!game || !action) return fail(BA3C_ERR_INVALID, "null game / action pointer");
-  if (!aux) return fail(BA3C_ERR_INVALID, "null aux pointer");
-  if (!reward || !over || !ep_score) return fail(BA3C_ERR_INVALID, "null output pointer");
-  if (n_games < 1 || limit < 1) return fail(BA3C_ERR_INVALID, "n_games and limit must be >= 1");
-  if (!check_ptr(game) || (state && !check_ptr(state)) || (reinterpret_cast<uintptr_t>(frame) & 3))
-    return fail(BA3C_ERR_INVALID, "game / state must be 16-byte and frame 4-byte aligned");
-  if (!check_ptr(aux)) return fail(BA3C_ERR_INVALID, "aux must be 16-byte aligned");
-  if (skip_lo < 1 || skip_hi < skip_lo || skip_hi > 16)
-    return fail(BA3C_ERR_INVALID, "frame skip must satisfy 1 <= skip_lo <= skip_hi <= 16");
-  if (sticky_q16 < 0 || sticky_q16 > 65536)
-    return fail(BA3C_ERR_INVALID, "sticky_q16 must be in [0, 65536]");
-  if (start_lo < 4 || start_hi < start_lo || start_hi > 19)
-    return fail(BA3C_ERR_INVALID, "start half-gap must satisfy 4 <= start_lo <= start_hi <= 19");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  DuelArgs a{game, action, n_games, limit, reward, over, ep_score, frame, state};
-  DuelDecideArgs k{aux, skip_lo, (uint32_t)(skip_hi - skip_lo + 1), (uint32_t)sticky_q16,
-                   start_lo, (uint32_t)(start_hi - start_lo + 1)};
-  hipLaunchKernelGGL(duel_decide_kernel, dim3(n_games), dim3(256), 0, s, a, k);
-  HIP_TRY(hipGetLastError());
-  return BA3C_OK;
+  const Decision d{aux, skip_lo, skip_hi, sticky_q16, start_lo, start_hi};
+  return game_launch<DuelSim>(stream, {game, action, limit, n_games, reward, over, ep_score, frame, state}, &d);
 }
 
 int ba3c_boxing_duel_render(void* stream, const int32_t* game, int32_t n_games, uint8_t* frame,
                             uint8_t* state) {
-  if (!game) return fail(BA3C_ERR_INVALID, "null game pointer");
-  if (n_games < 1) return fail(BA3C_ERR_INVALID, "n_games must be >= 1");
-  if (!check_ptr(game) || (state && !check_ptr(state)) || (reinterpret_cast<uintptr_t>(frame) & 3))
-    return fail(BA3C_ERR_INVALID, "game / state must be 16-byte and frame 4-byte aligned");
-  if (!frame && !state) return BA3C_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  // render only: the kernel never writes the row when action is null
-  DuelArgs a{const_cast<int32_t*>(game), nullptr, n_games, 1, nullptr, nullptr, nullptr, frame, state};
-  hipLaunchKernelGGL(duel_kernel, dim3(n_games), dim3(256), 0, s, a);
-  HIP_TRY(hipGetLastError());
-  return BA3C_OK;
+  return game_launch<DuelSim>(stream, render_args(game, n_games, frame, state), nullptr, true);
 }
 
 int ba3c_breakout_view(void* stream, const int32_t* game, int32_t n_envs, const int32_t* sel, int32_t n_sel,

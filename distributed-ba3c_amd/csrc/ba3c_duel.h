@@ -9,23 +9,12 @@
 // and sees in the mirror x -> 78 - x, in which it is the white boxer that starts on the left.
 //
 // One 256-thread workgroup per GAME (not per player): both sides replace the same row, so one
-// workgroup steps it once and then renders twice, side A from g and side B from mirror(g).
+// workgroup steps it once and then renders twice, side A from g and side B from mirror(g):
+// sim_kernel<DuelSim, .> (ba3c_envkernel.h) with DuelSim below.
 #pragma once
 #include "ba3c_boxing.h"
 
 namespace ba3c {
-
-struct DuelArgs {
-  int32_t* game;            // [G][16]
-  const int64_t* action;    // [2G] (null: render only)
-  int32_t n_games;
-  int32_t limit;
-  double* reward;           // [2G]
-  uint8_t* over;            // [2G]
-  int32_t* ep_score;        // [2G], written where over
-  uint8_t* frame;           // [2G][84*84] or null
-  uint8_t* state;           // [2G][84*84][4] or null
-};
 
 // (dx, dy, fire) of an action in its side's own frame; out of range: NOOP.
 __device__ __forceinline__ void duel_decode(int64_t a, int32_t* dx, int32_t* dy, bool* fire) {
@@ -46,7 +35,7 @@ __device__ __forceinline__ BoxingGame duel_mirror(const BoxingGame& g) {
 
 // One step of the rules (duel.py: step_numpy).  Returns side A's reward (side B's is its
 // negative); *ep_out is side A's episode score.  kFresh: on `over` the row restarts from the fixed
-// start here; duel_decide_kernel passes false and starts the episode itself (a drawn start).
+// start here; DuelSim::decide passes false and starts the episode itself (a drawn start).
 template <bool kFresh = true>
 __device__ __forceinline__ int32_t duel_step(BoxingGame& g, int64_t a, int64_t b, int32_t limit,
                                              bool* over_out, int32_t* ep_out) {
@@ -95,94 +84,68 @@ __device__ __forceinline__ void duel_fresh(BoxingGame& g, int32_t h_lo, uint32_t
   g.a_cd = g.o_cd = g.a_score = g.o_score = g.t = 0;
 }
 
-__global__ void __launch_bounds__(256) duel_kernel(const DuelArgs a) {
-  const int e = blockIdx.x;
-  const int tid = threadIdx.x;
-  const int4* row = reinterpret_cast<const int4*>(a.game + (size_t)e * 16);
-  const int4 r0 = row[0], r1 = row[1], r2 = row[2], r3 = row[3];
-  BoxingGame g;
-  BoxingRules::load(g, r0, r1, r2, r3);
-  bool over = a.action == nullptr;      // render only: both histories start (zeros + frame)
-  if (a.action != nullptr) {
-    int32_t ep = 0;
-    const int32_t reward = duel_step(g, a.action[e], a.action[a.n_games + e], a.limit, &over, &ep);
-    __syncthreads();                    // every thread has read the row before it is replaced
-    if (tid == 0) {
-      BoxingRules::store(g, reinterpret_cast<int4*>(a.game + (size_t)e * 16));
-      a.reward[e] = (double)reward;
-      a.reward[a.n_games + e] = (double)-reward;
-      a.over[e] = a.over[a.n_games + e] = over ? 1 : 0;
-      if (over) {
-        a.ep_score[e] = ep;
-        a.ep_score[a.n_games + e] = -ep;
-      }
-    }
-  }
-  env_render_push<BoxingRules>(g, over, a.frame, a.state, e, tid);
-  env_render_push<BoxingRules>(duel_mirror(g), over, a.frame, a.state, a.n_games + e, tid);
-}
-
 // What a decision adds to a step (duel.py: decide_numpy): the aux rows, the frame-skip and sticky
-// parameters of ba3c_amd/frameskip.py and the range of the drawn start.
-struct DuelDecideArgs {
-  int32_t* aux;             // [G][8] = [rng_k, rng_a, rng_b, prev_a, prev_b, 0, 0, 0]
-  int32_t skip_lo;          // k = skip_lo + draw % skip_span, skip_span = hi - lo + 1
-  uint32_t skip_span;
-  uint32_t sticky_q16;      // a side's sub-step repeats its prev when its 16-bit draw is below this
-  int32_t start_lo;         // half-gap h = start_lo + draw % start_span; start_lo == 19: the fixed
+// parameters of ba3c_amd/frameskip.py (EnvSkipArgs, the sticky draw per side) and the range of the
+// drawn start.  aux is [G][8] = [rng_k, rng_a, rng_b, prev_a, prev_b, 0, 0, 0] here.
+struct DuelDecideArgs : EnvSkipArgs {
+  int32_t start_lo;        // half-gap h = start_lo + draw % start_span; start_lo == 19: the fixed
   uint32_t start_span;      // start, which draws nothing
 };
 
-// One DECISION of every game per launch (a.action is never null here): k drawn from rng_k, each
-// side's sticky draws from its own generator, k steps of the rules in registers, then one store
-// and two renders, as duel_kernel.  k, every draw and both rows are wave-uniform, so the whole
-// loop runs on the scalar unit; the sub-steps after an episode's end are dropped and the fresh
-// row is drawn once.  One barrier.
-__global__ void __launch_bounds__(256) duel_decide_kernel(const DuelArgs a, const DuelDecideArgs k) {
-  const int e = blockIdx.x;
-  const int tid = threadIdx.x;
-  const int4* row = reinterpret_cast<const int4*>(a.game + (size_t)e * 16);
-  const int4 r0 = row[0], r1 = row[1], r2 = row[2], r3 = row[3];
-  const int4* aux = reinterpret_cast<const int4*>(k.aux + (size_t)e * 8);
-  const int4 x0 = aux[0], x1 = aux[1];
-  BoxingGame g;
-  BoxingRules::load(g, r0, r1, r2, r3);
-  const int64_t act_a = a.action[e], act_b = a.action[a.n_games + e];
-  const int32_t chosen_a = (uint64_t)act_a < 32u ? (int32_t)act_a : 0;   // out of range: NOOP, before
-  const int32_t chosen_b = (uint64_t)act_b < 32u ? (int32_t)act_b : 0;   // it can be remembered
-  const uint32_t rng_k = env_lcg((uint32_t)x0.x);
-  uint32_t rng_a = (uint32_t)x0.y, rng_b = (uint32_t)x0.z;
-  int32_t prev_a = x0.w, prev_b = x1.x;
-  const int32_t n = k.skip_lo + (int32_t)((rng_k >> 16) % k.skip_span);
-  int32_t reward = 0, ep = 0;
-  bool over = false;
-  for (int32_t j = 0; j < n && !over; ++j) {
-    rng_a = env_lcg(rng_a);
-    prev_a = ((rng_a >> 8) & 0xFFFFu) < k.sticky_q16 ? prev_a : chosen_a;
-    rng_b = env_lcg(rng_b);
-    prev_b = ((rng_b >> 8) & 0xFFFFu) < k.sticky_q16 ? prev_b : chosen_b;
-    reward += duel_step<false>(g, (int64_t)prev_a, (int64_t)prev_b, a.limit, &over, &ep);
+// Two players per row (ba3c_envkernel.h: Sim): player 0 is side A, player 1 side B, who acts on
+// and sees the mirrored row.  The step is made once and both sides are rendered from it.
+struct DuelSim {
+  using Rules = BoxingRules;
+  using DecideArgs = DuelDecideArgs;
+  struct Aux { int4 lo, hi; };
+  static constexpr int PLAYERS = 2;
+  static __device__ __forceinline__ BoxingGame view(const BoxingGame& g, int p) {
+    return p ? duel_mirror(g) : g;
   }
-  if (over) {
-    prev_a = prev_b = 0;
-    duel_fresh(g, k.start_lo, k.start_span);
+  static __device__ __forceinline__ int32_t step(BoxingGame& g, const int64_t* action, int e, int G,
+                                                 int32_t limit, bool* over, int32_t* ep) {
+    return duel_step(g, action[e], action[G + e], limit, over, ep);
   }
-  __syncthreads();                      // every thread has read both rows before they are replaced
-  if (tid == 0) {
-    BoxingRules::store(g, reinterpret_cast<int4*>(a.game + (size_t)e * 16));
-    int4* aux_out = reinterpret_cast<int4*>(k.aux + (size_t)e * 8);
-    aux_out[0] = make_int4((int32_t)rng_k, (int32_t)rng_a, (int32_t)rng_b, prev_a);
-    aux_out[1] = make_int4(prev_b, 0, 0, 0);
-    a.reward[e] = (double)reward;
-    a.reward[a.n_games + e] = (double)-reward;
-    a.over[e] = a.over[a.n_games + e] = over ? 1 : 0;
-    if (over) {
-      a.ep_score[e] = ep;
-      a.ep_score[a.n_games + e] = -ep;
+  static __device__ __forceinline__ Aux load_aux(const DecideArgs& k, int e) {
+    const int4* aux = reinterpret_cast<const int4*>(k.aux + (size_t)e * 8);
+    return Aux{aux[0], aux[1]};
+  }
+  static __device__ __forceinline__ void store_aux(const DecideArgs& k, int e, const Aux& x) {
+    int4* aux = reinterpret_cast<int4*>(k.aux + (size_t)e * 8);
+    aux[0] = x.lo;
+    aux[1] = x.hi;
+  }
+  // duel.py: decide_numpy.  k drawn from rng_k, each side's sticky draws from its own generator,
+  // k steps of the rules in registers; the sub-steps after an episode's end are dropped and the
+  // fresh row is drawn once.
+  static __device__ __forceinline__ int32_t decide(BoxingGame& g, Aux& x, const int64_t* action, int e, int G,
+                                                   int32_t limit, const DecideArgs& k, bool* over_out,
+                                                   int32_t* ep) {
+    const int64_t act_a = action[e], act_b = action[G + e];
+    const int32_t chosen_a = (uint64_t)act_a < 32u ? (int32_t)act_a : 0;   // out of range: NOOP, before
+    const int32_t chosen_b = (uint64_t)act_b < 32u ? (int32_t)act_b : 0;   // it can be remembered
+    const uint32_t rng_k = env_lcg((uint32_t)x.lo.x);
+    uint32_t rng_a = (uint32_t)x.lo.y, rng_b = (uint32_t)x.lo.z;
+    int32_t prev_a = x.lo.w, prev_b = x.hi.x;
+    const int32_t n = k.skip_lo + (int32_t)((rng_k >> 16) % k.skip_span);
+    int32_t reward = 0;
+    bool over = false;
+    for (int32_t j = 0; j < n && !over; ++j) {
+      rng_a = env_lcg(rng_a);
+      prev_a = ((rng_a >> 8) & 0xFFFFu) < k.sticky_q16 ? prev_a : chosen_a;
+      rng_b = env_lcg(rng_b);
+      prev_b = ((rng_b >> 8) & 0xFFFFu) < k.sticky_q16 ? prev_b : chosen_b;
+      reward += duel_step<false>(g, (int64_t)prev_a, (int64_t)prev_b, limit, &over, ep);
     }
+    if (over) {
+      prev_a = prev_b = 0;
+      duel_fresh(g, k.start_lo, k.start_span);
+    }
+    x.lo = make_int4((int32_t)rng_k, (int32_t)rng_a, (int32_t)rng_b, prev_a);
+    x.hi = make_int4(prev_b, 0, 0, 0);
+    *over_out = over;
+    return reward;
   }
-  env_render_push<BoxingRules>(g, over, a.frame, a.state, e, tid);
-  env_render_push<BoxingRules>(duel_mirror(g), over, a.frame, a.state, a.n_games + e, tid);
-}
+};
 
 }  // namespace ba3c

@@ -2,8 +2,8 @@
 // simulators as an RGB image, at an integer scale, with an optional HUD strip (the policy's
 // output) under it.  ba3c_amd/view.py states the image once (view_numpy: the oracle of this
 // kernel, over the games' own render_numpy); this file restates the palette lookup, the HUD
-// strip and the scaling, and takes the game's pixels from the same `Rules` env_kernel uses
-// (ba3c_envkernel.h).  It lives in a header of its own so that the four step kernels compile
+// strip and the scaling, and takes the game's pixels from the same `Rules` sim_kernel uses
+// (ba3c_envkernel.h).  It lives in a header of its own so that the six step kernels compile
 // exactly as they did without it.
 //
 // Image i shows simulator sel[i] (sel null: i); an index outside [0, n_envs) gives an all-zero
