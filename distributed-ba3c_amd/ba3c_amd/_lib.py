@@ -38,8 +38,9 @@ class Ba3cOptParams(ctypes.Structure):
 
 
 _lib = None
-# roofline-accounting queries an alternative A/B build (BA3C_LIB) may predate
-AB_OPTIONAL = {"ba3c_kernel_merged", "ba3c_probe_every"}
+# roofline-accounting queries and the PPO entry points an alternative A/B build (BA3C_LIB) may
+# predate
+AB_OPTIONAL = {"ba3c_kernel_merged", "ba3c_probe_every", "ba3c_train_grads_ppo", "ba3c_sample_logp"}
 
 
 def load():
@@ -73,6 +74,8 @@ def load():
         "ba3c_clip_grads": (i32, [P, P, P, P]),
         "ba3c_clip_grads_range": (i32, [P, P, P, P, i32, i32]),
         "ba3c_train_grads_phase": (i32, [P, P, P, P, P, P, i32, f32, P, P, P, i32]),
+        "ba3c_train_grads_ppo": (i32, [P, P, P, P, P, P, i32, f32, f32, P, P, P, P, i32]),
+        "ba3c_sample_logp": (i32, [P, P, P, P, i32, i32, P, P, P]),
         "ba3c_bucket_tensor": (i32, [P]),
         "ba3c_flush_pending": (i32, [P]),
         "ba3c_launch_held": (i32, [P, P]),
@@ -116,7 +119,7 @@ def load():
     }
     for name, (res, args) in sig.items():
         if os.environ.get("BA3C_LIB") and name in AB_OPTIONAL and not hasattr(lib, name):
-            continue            # an A/B build older than this accounting query
+            continue            # an A/B build older than this entry point
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -10,6 +10,10 @@ One iteration is the reference's per-simulator message cycle (RL/simulator.py:95
   RolloutBuffer.on_state -> env step -> FrameHistory.push -> RolloutBuffer.on_reward
   (n-step returns, train.py:408-437) -> BatchQueue (BatchData) -> Ba3cTrainer.train_step
 
+With a PPO setting (ActorLearner(ppo=...), ba3c_amd.ppo) the datapoints go to a replay pool
+instead of the BatchQueue and every pool is trained for several passes with the clipped-surrogate
+loss; without one the loop is the reference's.
+
 The synthetic environment is NOT part of the reference's hot path; it only produces frames,
 rewards and episode ends with the shapes and value ranges of the Atari pipeline (84x84
 grayscale frames, integer rewards incl. values outside [-1, 1] that the returns clip).
@@ -17,6 +21,7 @@ grayscale frames, integer rewards incl. values outside [-1, 1] that the returns 
 import numpy as np
 import torch
 
+from . import ppo as ppo_rules
 from .rollout import GAMMA, LOCAL_TIME_MAX, BatchQueue, FrameHistory, RolloutBuffer
 
 
@@ -62,8 +67,14 @@ class ActorLearner(object):
 
     def __init__(self, trainer, n_envs, batch_size, seed=0, rs=None, on_train_step=None,
                  dummy_predictor=False, env=None, local_time_max=LOCAL_TIME_MAX, gamma=GAMMA,
-                 gae_lambda=1.0):
-        """local_time_max, gamma, gae_lambda: the rollout length, discount and GAE lambda of the
+                 gae_lambda=1.0, ppo=None):
+        """ppo: None is the A3C loop; a ppo.Setting(clip, epochs, minibatches) records each action's
+        log-probability under the policy that drew it (sample_logp on the forward's 'logitsT' /
+        'logits'), feeds a ppo.Pool of minibatches * batch_size datapoints instead of the
+        BatchQueue, trains every minibatch the pool yields with the clipped-surrogate loss and
+        keeps the last step's per-sample ratio on the device (last_ratio).  stop_at (an attribute, None: off) ends a pool early once the trainer's
+        global_step reaches it.
+        local_time_max, gamma, gae_lambda: the rollout length, discount and GAE lambda of the
         RolloutBuffer's returns (--local_time_max, --gamma, --gae_lambda; the defaults are the
         reference's 5-step, 0.99, n-step recipe).
         env: the vector of simulators (None: SyntheticAtari, as before); an env with
@@ -82,9 +93,16 @@ class ActorLearner(object):
         self.env = env
         self._fused = hasattr(env, "step_into")
         self.hist = FrameHistory(n_envs, hist_len=4, channels=1, device=eng.device)
+        self.ppo = ppo
+        if ppo is not None and trainer.model.explore_factor != 1.0:
+            raise ValueError("PPO records log pi of the policy it samples from: explore_factor must be 1")
         self.buf = RolloutBuffer(n_envs, channels=4, local_time_max=local_time_max, gamma=gamma,
-                                 gae_lambda=gae_lambda, device=eng.device)
+                                 gae_lambda=gae_lambda, device=eng.device, logp=ppo is not None)
         self.queue = BatchQueue(batch_size)
+        self.pool = None if ppo is None else ppo_rules.Pool(
+            batch_size, minibatches=ppo.minibatches, epochs=ppo.epochs, seed=seed)
+        self.last_ratio = None
+        self.stop_at = None
         self.rs = rs if rs is not None else np.random.RandomState(seed)
         self.hist.push(self.env.frames(), torch.ones(n_envs, dtype=torch.bool, device=eng.device))
         self.steps = 0
@@ -103,7 +121,51 @@ class ActorLearner(object):
         _, probsT, value = eng.forward(state, explore_factor=self.trainer.model.explore_factor)
         return probsT, value
 
+    def _predict_both(self, state):
+        """(probsT, probs, value): the distribution sampled from and the one whose log is kept."""
+        eng = self.engine
+        if self.dummy_predictor:
+            probs, value = self._predict(state)
+            return probs, probs, value
+        probs, probsT, value = eng.forward(state, explore_factor=self.trainer.model.explore_factor)
+        return probsT, probs, value
+
+    def _after_step(self):
+        self.train_steps += 1
+        self.last_scalars = self.trainer.model.scalars
+        if self.on_train_step is not None:
+            self.on_train_step(self.trainer)
+
+    def _iterate_ppo(self):
+        eng, clip = self.engine, self.ppo.clip
+        state = self.hist.state
+        probsT, probs, value = self._predict_both(state)
+        u = torch.from_numpy(self.rs.random_sample(self.env.E)).to(eng.device)
+        actions, logp, flag = eng.sample_logp(probsT, probs, u)
+        self.buf.on_state(state, actions, value, logp=logp)
+        if self._fused:
+            reward, over = self.env.step_into(actions, self.hist)
+        else:
+            frames, reward, over = self.env.step(actions)
+            self.hist.push(frames, over)
+        self.pool.put(self.buf.on_reward(reward, over))
+        while True:
+            batches = self.pool.get()
+            if batches is None:
+                break
+            for st, ac, rows in batches:
+                if self.stop_at is not None and self.trainer.global_step >= self.stop_at:
+                    break
+                self.trainer.train_step(st, ac, None, rows=rows, clip=clip)
+                self.last_ratio = self.trainer.model.ratio
+                self._after_step()
+        self.steps += 1
+        if int(flag.item()) & 1:
+            raise AssertionError("non-finite action distribution (train.py:381)")
+
     def iterate(self):
+        if self.ppo is not None:
+            return self._iterate_ppo()
         eng = self.engine
         state = self.hist.state
         probsT, value = self._predict(state)
@@ -121,10 +183,7 @@ class ActorLearner(object):
             if b is None:
                 break
             self.trainer.train_step(b[0].contiguous(), b[1].contiguous(), b[2].contiguous())
-            self.train_steps += 1
-            self.last_scalars = self.trainer.model.scalars
-            if self.on_train_step is not None:
-                self.on_train_step(self.trainer)
+            self._after_step()
         self.steps += 1
         if int(flag.item()) & 1:
             raise AssertionError("non-finite action distribution (train.py:381)")

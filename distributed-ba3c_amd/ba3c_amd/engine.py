@@ -80,6 +80,7 @@ class Ba3cEngine(object):
             self.ws_train = None
             self.ws_fwd = None
             self.scalars = torch.zeros(8, dtype=torch.float64, device=self.device)
+            self.ratio = None       # train_grads_ppo's per-sample rho [max_batch], on first use
 
     # -- parameters -------------------------------------------------------------------
     @property
@@ -177,6 +178,31 @@ class Ba3cEngine(object):
                                                    _ptr(grads), _ptr(self.scalars), int(phase)))
         return self.scalars
 
+    def train_grads_ppo(self, state, action, rows, clip_eps, entropy_beta=0.01, grads=None,
+                        phase=0, ratio=True):
+        """train_grads with the clipped-surrogate policy term (ba3c_train_grads_ppo, ba3c_amd.ppo):
+        rows float32 [B, 4] = {R, V_old, l_old, 0}; the phases are train_grads'.  ratio: True
+        writes each sample's rho into self.ratio[:B] (a tensor: into it; None / False: not
+        stored).  Returns the scalars tensor."""
+        B = self._check_state(state)
+        assert action.dtype == torch.int64 and action.shape == (B,) and action.is_cuda
+        assert rows.dtype == torch.float32 and rows.shape == (B, 4) and rows.is_cuda \
+            and rows.is_contiguous()
+        grads = self.grads if grads is None else grads
+        if ratio is True:
+            if self.ratio is None:
+                self.ratio = torch.ones(self.max_batch, dtype=torch.float32, device=self.device)
+            ratio = self.ratio
+        elif ratio is False:
+            ratio = None
+        assert ratio is None or (ratio.dtype == torch.float32 and ratio.numel() >= B)
+        _lib.check(self.lib.ba3c_train_grads_ppo(self.h, _stream(), _ptr(self.params), _ptr(state),
+                                                 _ptr(action.contiguous()), _ptr(rows), B,
+                                                 float(entropy_beta), float(clip_eps),
+                                                 _ptr(self._workspace(True)), _ptr(grads),
+                                                 _ptr(self.scalars), _ptr(ratio), int(phase)))
+        return self.scalars
+
     def flush_pending(self):
         """Launch a weight-gradient reduction a phase-3 pass left pending (no-op otherwise)."""
         _lib.check(self.lib.ba3c_flush_pending(self.h))
@@ -246,6 +272,23 @@ class Ba3cEngine(object):
         _lib.check(self.lib.ba3c_sample(_stream(), _ptr(probs.contiguous()), _ptr(u), B, A,
                                         _ptr(actions), _ptr(flag)))
         return actions, flag
+
+    def sample_logp(self, probs, pi, u, actions=None, logp=None, flag=None):
+        """sample(probs, u) that also records logp[i] = log(pi[i][a_i] + 1e-6) (float32): probs
+        is the distribution sampled from ('logitsT'), pi the one recorded ('logits')."""
+        B, A = probs.shape
+        assert pi.shape == (B, A) and pi.dtype == torch.float32
+        assert u.dtype == torch.float64 and u.shape == (B,)
+        if actions is None:
+            actions = torch.empty(B, dtype=torch.int64, device=probs.device)
+        if logp is None:
+            logp = torch.empty(B, dtype=torch.float32, device=probs.device)
+        if flag is None:
+            flag = torch.zeros(1, dtype=torch.int32, device=probs.device)
+        _lib.check(self.lib.ba3c_sample_logp(_stream(), _ptr(probs.contiguous()),
+                                             _ptr(pi.contiguous()), _ptr(u), B, A, _ptr(actions),
+                                             _ptr(logp), _ptr(flag)))
+        return actions, logp, flag
 
     def greedy(self, probs, u, random_actions, eps=0.001, actions=None):
         """Evaluation action: first argmax of each row, random_actions[i] where u[i] < eps."""

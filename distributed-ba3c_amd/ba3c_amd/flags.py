@@ -4,7 +4,7 @@ its single-node launcher (`python -m ba3c_amd.train`) consume.  Slurm / TF-serve
 flags are accepted and ignored."""
 import argparse
 
-from . import duel, frameskip
+from . import duel, frameskip, ppo
 from .boxing import BoxingVec
 from .breakout import BreakoutVec
 
@@ -104,6 +104,15 @@ def build_parser():
                    help="lambda of the returns the learner fits (ba3c_amd.returns), in [0, 1]: "
                         "1 is the reference's n-step return, below 1 the policy advantage is "
                         "GAE(lambda) and the value target TD(lambda)")
+    p.add_argument("--ppo_clip", type=float, default=0.0,
+                   help="clip eps of the clipped-surrogate (PPO) loss, in (0, 1); 0: off, the A3C "
+                        "loss and one gradient step per datapoint (ba3c_amd.ppo)")
+    p.add_argument("--ppo_epochs", type=int, default=None,
+                   help="passes over each pool of datapoints (default %d); needs --ppo_clip"
+                        % ppo.DEFAULT_EPOCHS)
+    p.add_argument("--ppo_minibatches", type=int, default=None,
+                   help="minibatches of --batch_size datapoints per pool (default %d); needs "
+                        "--ppo_clip" % ppo.DEFAULT_MINIBATCHES)
     p.add_argument("--dummy", type=int, default=0)
     p.add_argument("--dummy_predictor", type=int, default=0)
     p.add_argument("--models_dir", default="models")
@@ -135,7 +144,11 @@ def resolve(args, duel_tool=False):
     --frame_skip / --sticky).  args.play_frame_skip / args.play_sticky are the run's setting
     either way, for the games and for --nr_eval alike.
     --gae_lambda in [0, 1], --local_time_max in 1..128, --gamma in (0, 1], and the states ring
-    they imply at most 16 GiB; they apply to every -e, with and without --self_play."""
+    they imply at most 16 GiB; they apply to every -e, with and without --self_play.
+    --ppo_clip in [0, 1) (0: off); --ppo_epochs / --ppo_minibatches >= 1 and only with
+    --ppo_clip > 0 (default 4 each); the pool's --ppo_minibatches x --batch_size states at most
+    16 GiB; not with --dummy (no simulators, nothing to replay).  args.ppo is the run's
+    ppo.Setting, or None when off; it applies to every -e and to --self_play."""
     if args.replace_with_conv is None:
         args.replace_with_conv = not args.use_normal_fc
     if args.adam_debug:
@@ -191,4 +204,24 @@ def resolve(args, duel_tool=False):
         raise SystemExit("--simulator_procs %d x --local_time_max %d: the states ring would take "
                          "%.1f GiB (limit 16 GiB)"
                          % (args.simulator_procs, args.local_time_max, ring / 2.0 ** 30))
+    if not 0.0 <= args.ppo_clip < 1.0:
+        raise SystemExit("--ppo_clip %r: the clip must be in [0, 1) (0: off)" % args.ppo_clip)
+    on = args.ppo_clip > 0.0
+    for name in ("ppo_epochs", "ppo_minibatches"):
+        v = getattr(args, name)
+        if v is not None and not on:
+            raise SystemExit("--%s needs --ppo_clip > 0" % name)
+        if v is not None and v < 1:
+            raise SystemExit("--%s %d: must be >= 1" % (name, v))
+    args.ppo = None
+    if on:
+        if args.dummy:
+            raise SystemExit("--ppo_clip replays rollouts: it cannot go with --dummy")
+        K = ppo.DEFAULT_EPOCHS if args.ppo_epochs is None else args.ppo_epochs
+        M = ppo.DEFAULT_MINIBATCHES if args.ppo_minibatches is None else args.ppo_minibatches
+        pool = M * args.batch_size * STATE_BYTES
+        if pool > MAX_RING_BYTES:
+            raise SystemExit("--ppo_minibatches %d x --batch_size %d: the pool's states would take "
+                             "%.1f GiB (limit 16 GiB)" % (M, args.batch_size, pool / 2.0 ** 30))
+        args.ppo = ppo.Setting(clip=args.ppo_clip, epochs=K, minibatches=M)
     return args

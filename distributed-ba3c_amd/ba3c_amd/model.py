@@ -42,6 +42,10 @@ class Model(ModelDesc):
         self.explore_factor = 1.0     # non-trainable var 'explore_factor' (train.py:294-295)
         self.vars_for_save = {n: n for n in self.engine.tensor_names}
         self.cost = None
+        # (rows, clip) of a clipped-surrogate step (Ba3cTrainer.train_step sets it for the
+        # step's passes); None: the A3C loss
+        self.ppo = None
+        self.ratio = None             # the last PPO pass's per-sample rho (device, [B])
 
     def _get_input_vars(self):
         return [InputVar(torch.uint8, (None,) + IMAGE_SIZE + (self.channel,), "state"),
@@ -62,8 +66,15 @@ class Model(ModelDesc):
         self.delay = inputs[3] if len(inputs) > 3 else None
         # train_phase 1 / 2: the two halves of the pass around the fc1 + heads gradient bucket
         # (Ba3cTrainer's bucketed data-parallel step); 0: the whole pass
-        sc = self.engine.train_grads(state, action, futurereward, entropy_beta=self.entropy_beta,
-                                     phase=getattr(self, "train_phase", 0))
+        phase = getattr(self, "train_phase", 0)
+        if self.ppo is not None:
+            rows, clip = self.ppo
+            sc = self.engine.train_grads_ppo(state, action, rows, clip,
+                                             entropy_beta=self.entropy_beta, phase=phase)
+            self.ratio = self.engine.ratio[:state.shape[0]]
+        else:
+            sc = self.engine.train_grads(state, action, futurereward,
+                                         entropy_beta=self.entropy_beta, phase=phase)
         self.scalars = sc
         self.cost = sc[0]
 

@@ -36,11 +36,13 @@ def _stream():
 
 class Datapoints(object):
     """One parse's datapoints: [state, action, R, init_R, isOver] (train.py:432; the ts field
-    is carried separately by callers that track it)."""
+    is carried separately by callers that track it).  rows (optional, RolloutBuffer(logp=True)):
+    float32 [n, 4] = {R, V_old, l_old, 0}, the per-sample input of the PPO loss (ba3c_amd.ppo)."""
 
-    def __init__(self, state, action, R, init_R, over, src):
+    def __init__(self, state, action, R, init_R, over, src, rows=None):
         self.state, self.action, self.R, self.init_R, self.over, self.src = \
             state, action, R, init_R, over, src
+        self.rows = rows
 
     def __len__(self):
         return int(self.R.shape[0])
@@ -49,10 +51,12 @@ class Datapoints(object):
 class RolloutBuffer(object):
     """gae_lambda = 1.0 (the reference's n-step returns) parses with `ba3c_nstep_returns`, as
     before; any other lambda in [0, 1] with `ba3c_lambda_returns` (ba3c_amd.returns states the
-    recursion)."""
+    recursion).
+    logp=True adds a ring of the behaviour policy's log-probabilities (on_state's `logp`) and
+    makes every parse's Datapoints carry `rows`."""
 
     def __init__(self, n_envs, channels=4, local_time_max=LOCAL_TIME_MAX, gamma=GAMMA,
-                 gae_lambda=1.0, device="cuda"):
+                 gae_lambda=1.0, device="cuda", logp=False):
         self.lib = _lib.load()
         self.E, self.T = int(n_envs), int(local_time_max) + 1
         self.C = int(channels)
@@ -67,6 +71,7 @@ class RolloutBuffer(object):
         self.actions = torch.zeros(E, T, dtype=torch.int64, device=dev)
         self.values = torch.zeros(E, T, dtype=torch.float32, device=dev)
         self.rewards = torch.zeros(E, T, dtype=torch.float64, device=dev)
+        self.logp = torch.zeros(E, T, dtype=torch.float32, device=dev) if logp else None
         self.start = torch.zeros(E, dtype=torch.int32, device=dev)
         self.length = torch.zeros(E, dtype=torch.int32, device=dev)
         # scratch of one parse
@@ -81,10 +86,14 @@ class RolloutBuffer(object):
     def _slot(self, offset):
         return ((self.start + self.length + offset) % self.T).long()
 
-    def on_state(self, states, actions, values):
-        """_on_state (train.py:364-392) for every simulator: append (state, action, value)."""
+    def on_state(self, states, actions, values, logp=None):
+        """_on_state (train.py:364-392) for every simulator: append (state, action, value), and
+        with the logp ring the action's log-probability under the policy that drew it."""
         assert states.shape == (self.E,) + IMAGE_SIZE + (self.C,) and states.dtype == torch.uint8
+        assert (logp is None) == (self.logp is None), "logp goes with RolloutBuffer(logp=True)"
         slot = self._slot(0)
+        if logp is not None:
+            self.logp[self._ar, slot] = logp.to(torch.float32)
         self.states[self._ar, slot] = states
         self.actions[self._ar, slot] = actions.to(torch.int64)
         self.values[self._ar, slot] = values.to(torch.float32)
@@ -129,11 +138,20 @@ class RolloutBuffer(object):
         row = IMAGE_SIZE[0] * IMAGE_SIZE[1] * self.C
         if n == 0:
             return Datapoints(st, ac, self._R[:0].clone(), self._init[:0].clone(),
-                              self._over[:0].clone(), src)
+                              self._over[:0].clone(), src, rows=self._rows(self._R[:0], src))
         _lib.check(self.lib.ba3c_gather_rows(_stream(), _ptr(self.states), _ptr(src), n, row, _ptr(st)))
         _lib.check(self.lib.ba3c_gather_rows(_stream(), _ptr(self.actions), _ptr(src), n, 8, _ptr(ac)))
-        return Datapoints(st, ac, self._R[:n].clone(), self._init[:n].clone(),
-                          self._over[:n].clone(), src)
+        R = self._R[:n].clone()
+        return Datapoints(st, ac, R, self._init[:n].clone(), self._over[:n].clone(), src,
+                          rows=self._rows(R, src))
+
+    def _rows(self, R, src):
+        """{R, values[src], logp[src], 0} per datapoint, before the slots are reused."""
+        if self.logp is None:
+            return None
+        i = src.long()
+        return torch.stack([R, self.values.view(-1)[i], self.logp.view(-1)[i],
+                            torch.zeros_like(R)], dim=1).contiguous()
 
 
 class BatchQueue(object):

@@ -10,7 +10,8 @@ flags.GAMES (`--frame_skip` / `--sticky`: ALE's frame skip and sticky actions, f
 evaluation alike; `--self_play`: two-player GridBoxing, ba3c_amd.duel, every game's two sides
 both played by the learner, with `--duel_frame_skip` / `--duel_sticky` per side and `--duel_start`, the gap
 between the boxers of a fresh episode; `--local_time_max` / `--gamma` / `--gae_lambda`: the rollout length,
-discount and GAE lambda of the returns, ba3c_amd.returns) and, for `--nr_eval N`, the Evaluator callback every --steps_per_epoch steps), plus
+discount and GAE lambda of the returns, ba3c_amd.returns; `--ppo_clip` / `--ppo_epochs` /
+`--ppo_minibatches`: the clipped-surrogate loss over replayed pools of datapoints, ba3c_amd.ppo) and, for `--nr_eval N`, the Evaluator callback every --steps_per_epoch steps), plus
 the DebugLogCallback metrics channels and PeriodicPerStepCallback(ModelSaver) (:608-630) and
 `--load` (SaverRestore, :706-707).
 
@@ -99,8 +100,14 @@ class _Metrics(object):
     """DebugLogCallback over device-resident step scalars: each learner step's 8 scalars are
     kept on the GPU and fetched once per --send_debug_every steps (no per-step host sync)."""
 
-    def __init__(self, trainer, batch_size, every, client):
+    def __init__(self, trainer, batch_size, every, client, ppo_clip=None):
+        """ppo_clip (eps, None: off): each PPO step's per-sample ratio is kept on the device too, and
+        every flush writes two more channels from them: ppo_clip_fraction = mean(|rho - 1| > eps)
+        and ppo_approx_kl = mean(-log rho) over the flushed steps."""
         from .metrics import DebugLogCallback
+        self.ppo_clip, self.client = ppo_clip, client
+        self.ratios = []
+        self.last_ppo = None
         self.trainer, self.B = trainer, batch_size
         self.every = max(1, int(every))
         self.cb = DebugLogCallback(client, worker_id=0, nr_send=self.every) if client else None
@@ -110,6 +117,8 @@ class _Metrics(object):
 
     def __call__(self, trainer):
         self.pending.append(trainer.model.scalars.clone())
+        if self.ppo_clip is not None and trainer.model.ratio is not None:
+            self.ratios.append(trainer.model.ratio.clone())
         if len(self.pending) >= self.every:
             self.flush()
 
@@ -127,6 +136,15 @@ class _Metrics(object):
             if self.cb is not None:
                 self.cb.trigger_step(d, dp_per_s)
         self.pending = []
+        if self.ratios:
+            from . import ppo
+            rho = torch.cat(self.ratios).cpu().numpy()
+            self.ratios = []
+            self.last_ppo = {"ppo_clip_fraction": ppo.clip_fraction(rho, self.ppo_clip),
+                             "ppo_approx_kl": ppo.approx_kl(rho)}
+            if self.client is not None:
+                for name, v in self.last_ppo.items():
+                    self.client.write_scalar(name, v)
         self.t0 = time.time()
 
 
@@ -157,7 +175,8 @@ def _run(args, rank, world):
     np.random.seed(rank)                                      # train.py:679
     model, trainer, savers = build(args, rank, world)
     client = CsvChannels(args.experiment_dir) if rank == 0 else None
-    metrics = _Metrics(trainer, args.batch_size, args.send_debug_every, client)
+    metrics = _Metrics(trainer, args.batch_size, args.send_debug_every, client,
+                       ppo_clip=args.ppo.clip if args.ppo is not None else None)
 
     evaluator = None
     if args.nr_eval and rank == 0:
@@ -202,7 +221,8 @@ def _run(args, rank, world):
                           seed=rank, rs=np.random.RandomState(rank), on_train_step=on_step,
                           dummy_predictor=bool(args.dummy_predictor), env=env,
                           local_time_max=args.local_time_max, gamma=args.gamma,
-                          gae_lambda=args.gae_lambda)
+                          gae_lambda=args.gae_lambda, ppo=args.ppo)
+        al.stop_at = max_steps if args.ppo is not None else None
         while trainer.global_step < max_steps:
             al.iterate()
         sim_steps = al.steps
@@ -215,6 +235,8 @@ def _run(args, rank, world):
            "simulator_steps": sim_steps, "samples_per_s": round(
                trainer.global_step * args.batch_size * world / max(wall, 1e-9), 1),
            "last": metrics.last}
+    if args.ppo is not None:
+        out["ppo"] = dict(args.ppo._asdict(), **(metrics.last_ppo or {}))
     if evaluator is not None:
         out["eval"] = evaluator.history
     if rank == 0:

@@ -135,11 +135,25 @@ class Ba3cTrainer(object):
             raise RuntimeError("device error flags 0x%x after global step %d: %s"
                                % (f, self.global_step, self.describe_device_errors(f)))
 
-    def train_step(self, state, action, futurereward):
+    def train_step(self, state, action, futurereward, rows=None, clip=None):
         """Device-side step (used by bench.py).  No host synchronisation, except with backup
         workers (SyncReplicasOptimizer with replicas_to_aggregate < world): each step then
         synchronises the stream and all-gathers the ranks' ready times on the host before a
-        flat (not bucketed) all-reduce, so its step times are not comparable with k = N."""
+        flat (not bucketed) all-reduce, so its step times are not comparable with k = N.
+        rows (float32 [B, 4] = {R, V_old, l_old, 0}) with clip (eps): the same step, through the
+        same phases, with the clipped-surrogate loss (ba3c_amd.ppo); futurereward is then unused
+        (rows carries R) and may be None."""
+        if (rows is None) != (clip is None):
+            raise ValueError("a PPO step takes rows and clip together")
+        if rows is None:
+            return self._train_step(state, action, futurereward)
+        self.model.ppo = (rows, float(clip))
+        try:
+            return self._train_step(state, action, futurereward)
+        finally:
+            self.model.ppo = None
+
+    def _train_step(self, state, action, futurereward):
         opt = self.optimizer
         # backup workers pick the first k ranks once the whole gradient is ready: flat path
         if (isinstance(opt, SyncReplicasOptimizer) and self._fused_clip and opt.bucketed
@@ -218,14 +232,16 @@ class Ba3cTrainer(object):
     timeline = None
     _mid = None
 
-    def capture_step(self, state, action, futurereward, warmup=2):
+    def capture_step(self, state, action, futurereward, warmup=2, rows=None, clip=None):
         """Capture one full step (fwd+bwd+clip+update) on static input tensors as a hipGraph
         (torch.cuda.CUDAGraph over the HIP stream).  Returns a callable that replays it; the
         caller refills `state`/`action`/`futurereward` in place between replays.  Adam's
         beta powers move to the device so every replay uses the right bias correction.
         The `warmup` eager steps that precede the capture (allocator / library warm-up) are
         undone: parameters, optimizer slots and beta powers are restored afterwards, so
-        capturing does not train the model."""
+        capturing does not train the model.  A PPO step (rows / clip) is refused."""
+        if rows is not None or clip is not None or self.model.ppo is not None:
+            raise ValueError("graph capture of a PPO step (rows / clip) is not supported")
         opt = self.optimizer
         if isinstance(opt, SyncReplicasOptimizer) and opt.backup_workers:
             raise ValueError("backup workers choose the aggregated ranks on the host each "

@@ -1084,11 +1084,39 @@ struct BackwardPass {
   }
 };
 
+// the PPO form of a training heads launch (ba3c_train_grads_ppo): rows replaces R
+struct PpoArgs {
+  const float* rows;   // [B][4] {R, V_old, l_old, 0}
+  float* ratio;        // [B] or null
+  float clip_eps;
+};
+
+// the heads instantiation of (F, A) for one loss: features per lane unrolled (heads_sample),
+// the smallest instantiation that covers F
+template <int LOSS>
+void launch_heads(hipStream_t s, int B, const HeadsArgsOf<LOSS>& a) {
+  const int F = a.F;
+  const dim3 g((B + 3) / 4), t(256);
+  // the reference's Atari action sets are mostly 4 actions: compile-time A there (heads_sample)
+  if (a.A == 4 && F <= 128 && F > 64) hipLaunchKernelGGL((heads_kernel<2, FC_SPLIT, 4, LOSS>), g, t, 0, s, a);
+  else if (a.A == 4 && F <= 512 && F > 256) hipLaunchKernelGGL((heads_kernel<8, FC_SPLIT, 4, LOSS>), g, t, 0, s, a);
+  else if (F <= 64) hipLaunchKernelGGL((heads_kernel<1, FC_SPLIT, 0, LOSS>), g, t, 0, s, a);
+  else if (F <= 128) hipLaunchKernelGGL((heads_kernel<2, FC_SPLIT, 0, LOSS>), g, t, 0, s, a);
+  else if (F <= 256) hipLaunchKernelGGL((heads_kernel<4, FC_SPLIT, 0, LOSS>), g, t, 0, s, a);
+  else if (F <= 512) hipLaunchKernelGGL((heads_kernel<8, FC_SPLIT, 0, LOSS>), g, t, 0, s, a);
+  else hipLaunchKernelGGL((heads_kernel<0, FC_SPLIT, 0, LOSS>), g, t, 0, s, a);
+}
+
 int run_heads(ba3c_handle* h, hipStream_t s, const float* prm, const Workspace& w, int B,
               const int64_t* action, const float* R, float beta, float explore, bool train,
               float* probs, float* probsT, float* value, double* scalars = nullptr,
-              bool defer_scalars = false) {
-  HeadsArgs a{};
+              bool defer_scalars = false, const PpoArgs* ppo = nullptr) {
+  HeadsArgsPpo a{};
+  if (ppo) {
+    a.rows = reinterpret_cast<const float4*>(ppo->rows);
+    a.ratio = ppo->ratio;
+    a.clip_eps = ppo->clip_eps;
+  }
   a.fcpart = w.fcpart;
   a.fc_split = FC_SPLIT;
   a.per = h->per;
@@ -1124,17 +1152,8 @@ int run_heads(ba3c_handle* h, hipStream_t s, const float* prm, const Workspace& 
   a.invB = 1.0f / (float)B;
   {
     ProbeScope ps(h, s, BA3C_K_HEADS);
-    // features per lane unrolled (heads_sample): the smallest instantiation that covers F
-    const int F = a.F;
-    const dim3 g((B + 3) / 4), t(256);
-    // the reference's Atari action sets are mostly 4 actions: compile-time A there (heads_sample)
-    if (a.A == 4 && F <= 128 && F > 64) hipLaunchKernelGGL((heads_kernel<2, FC_SPLIT, 4>), g, t, 0, s, a);
-    else if (a.A == 4 && F <= 512 && F > 256) hipLaunchKernelGGL((heads_kernel<8, FC_SPLIT, 4>), g, t, 0, s, a);
-    else if (F <= 64) hipLaunchKernelGGL((heads_kernel<1, FC_SPLIT>), g, t, 0, s, a);
-    else if (F <= 128) hipLaunchKernelGGL((heads_kernel<2, FC_SPLIT>), g, t, 0, s, a);
-    else if (F <= 256) hipLaunchKernelGGL((heads_kernel<4, FC_SPLIT>), g, t, 0, s, a);
-    else if (F <= 512) hipLaunchKernelGGL((heads_kernel<8, FC_SPLIT>), g, t, 0, s, a);
-    else hipLaunchKernelGGL((heads_kernel<0, FC_SPLIT>), g, t, 0, s, a);
+    if (ppo && train) launch_heads<LOSS_PPO>(s, B, a);
+    else launch_heads<LOSS_A3C>(s, B, a);
   }
   HIP_TRY(hipGetLastError());
   if (train && scalars && !fuse_scalars && defer_scalars) {
@@ -1494,7 +1513,7 @@ int ba3c_forward(ba3c_handle* h, void* stream, const float* params, const uint8_
 static int train_grads_impl(ba3c_handle* h, void* stream, const float* params, const uint8_t* state,
                             const int64_t* action, const float* futurereward, int32_t batch,
                             float entropy_beta, void* workspace, float* grads, double* scalars,
-                            int32_t phase);
+                            int32_t phase, const PpoArgs* ppo = nullptr);
 
 // launch a reduction a phase-3 pass left pending, on the pass's stream; a call on another
 // stream `s` then waits for it (an event recorded by the caller after the pass predates it)
@@ -1569,9 +1588,10 @@ int ba3c_flush_pending(ba3c_handle* h) {
 static int train_grads_impl(ba3c_handle* h, void* stream, const float* params, const uint8_t* state,
                             const int64_t* action, const float* futurereward, int32_t batch,
                             float entropy_beta, void* workspace, float* grads, double* scalars,
-                            int32_t phase) {
+                            int32_t phase, const PpoArgs* ppo) {
+  // ppo: the clipped-surrogate heads (ba3c_train_grads_ppo); its rows stand in for futurereward
   if (!h || !check_ptr(params) || !check_ptr(state) || !check_ptr(workspace) || !check_ptr(grads) ||
-      !action || !futurereward)
+      !action || (!futurereward && !ppo))
     return fail(BA3C_ERR_INVALID, "null or misaligned pointer");
   if (batch < 1 || batch > h->cfg.max_batch) return fail(BA3C_ERR_INVALID, "batch out of range");
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1596,8 +1616,28 @@ static int train_grads_impl(ba3c_handle* h, void* stream, const float* params, c
   // heads + loss + its gradient, fc1's split-K finish and (last workgroup) the TfDictOp scalars
   h->pend_scalars = false;
   CHECK(run_heads(h, s, params, w, batch, action, futurereward, entropy_beta, 1.0f, true, nullptr,
-                  nullptr, nullptr, scalars, phase != 2 && h->sw.scalars_ride && h->g6));
+                  nullptr, nullptr, scalars, phase != 2 && h->sw.scalars_ride && h->g6, ppo));
   return backward();
+}
+
+int ba3c_train_grads_ppo(ba3c_handle* h, void* stream, const float* params, const uint8_t* state,
+                         const int64_t* action, const float* rows, int32_t batch,
+                         float entropy_beta, float clip_eps, void* workspace, float* grads,
+                         double* scalars, float* ratio, int32_t phase) {
+  if (!check_ptr(rows)) return fail(BA3C_ERR_INVALID, "rows must be non-null and 16-byte aligned");
+  if (ratio && !check_ptr(ratio)) return fail(BA3C_ERR_INVALID, "ratio must be 16-byte aligned (or null)");
+  // written so that a NaN fails it
+  if (!(clip_eps > 0.f && clip_eps < 1.f)) return fail(BA3C_ERR_INVALID, "clip_eps must be in (0, 1)");
+  if (phase < 0 || phase > 4) return fail(BA3C_ERR_INVALID, "phase must be 0, 1, 2, 3 or 4");
+  const PpoArgs ppo{rows, ratio, clip_eps};
+  if (phase != 3)
+    return train_grads_impl(h, stream, params, state, action, nullptr, batch, entropy_beta, workspace,
+                            grads, scalars, phase, &ppo);
+  if (h) h->defer_final = true;
+  const int r = train_grads_impl(h, stream, params, state, action, nullptr, batch, entropy_beta,
+                                 workspace, grads, scalars, 0, &ppo);
+  if (h) h->defer_final = false;
+  return r;
 }
 
 int ba3c_clip_grads_range(ba3c_handle* h, void* stream, float* grads, void* workspace, int32_t t0,
@@ -1755,6 +1795,20 @@ int ba3c_sample(void* stream, const float* probs, const double* u, int32_t batch
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(sample_kernel, dim3((batch + 255) / 256), dim3(256), 0, s, probs, u, batch,
                      num_actions, actions, nonfinite);
+  HIP_TRY(hipGetLastError());
+  return BA3C_OK;
+}
+
+int ba3c_sample_logp(void* stream, const float* probs, const float* pi, const double* u,
+                     int32_t batch, int32_t num_actions, int64_t* actions, float* logp,
+                     int32_t* nonfinite) {
+  if (!probs || !u || !actions) return fail(BA3C_ERR_INVALID, "null pointer");
+  if (!pi || !logp) return fail(BA3C_ERR_INVALID, "null pi or logp");
+  if (batch < 0 || num_actions < 1 || num_actions >= MAXA) return fail(BA3C_ERR_INVALID, "bad shape");
+  if (batch == 0) return BA3C_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(sample_logp_kernel, dim3((batch + 255) / 256), dim3(256), 0, s, probs, pi, u,
+                     batch, num_actions, actions, logp, nonfinite);
   HIP_TRY(hipGetLastError());
   return BA3C_OK;
 }

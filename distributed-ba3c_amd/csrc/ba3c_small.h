@@ -34,7 +34,17 @@ __device__ __forceinline__ unsigned long long ld_agent(const unsigned long long*
 //   dz_k = p_k (dL/dp_k - sum_j p_j dL/dp_j),  dV = (V - R) / B,
 //   dh_f = sum_k dz_k W_pi[f][k] + dV W_v[f]  (x (h_f > 0) for the legacy ReLU FC).
 // terms[n] = {log(p_a+1e-6)*adv, sum p log(p+1e-6), (V-R)^2, adv, V, max p, 0, 0}
+//
+// LOSS_PPO: the clipped-surrogate policy term (Schulman et al. 2017; ba3c_amd/ppo.py states it
+// and is its oracle).  Per sample rows[n] = {R, V_old, l_old, 0} with l_old =
+// log(pi_old(a) + 1e-6):
+//   Adv = R - V_old,  rho = exp(log(p_a+1e-6) - l_old),  rc = clip(rho, 1-eps, 1+eps)
+//   s = -min(rho Adv, rc Adv),  c = (rho Adv <= rc Adv) ? -Adv rho : 0   (a tie is unclipped)
+// and dL/dp is the A3C one with `adv` replaced by `c`; terms[n][0] = s, the entropy and value
+// terms and terms 1-5 are the A3C ones (term 3 stays V - R with the current V).  At rho = 1
+// and V_old = V this is the A3C gradient.
 // ---------------------------------------------------------------------------------------
+constexpr int LOSS_A3C = 0, LOSS_PPO = 1;
 struct HeadsArgs {
   float* h;
   const float* piW;
@@ -62,6 +72,15 @@ struct HeadsArgs {
   unsigned long long* done;  // completion counter (zero on entry; reset by the last workgroup)
   double* scalars;           // null: no scalars
 };
+// The LOSS_PPO instantiations' arguments: HeadsArgs grown by the PPO inputs.  A type of its own
+// so that the LOSS_A3C kernels keep the kernel-argument block, and with it the code, they had.
+struct HeadsArgsPpo : HeadsArgs {
+  const float4* rows;        // [B] {R, V_old, l_old, 0}: replaces R
+  float* ratio;              // [B] rho, may be null
+  float clip_eps;
+};
+template <int LOSS>
+using HeadsArgsOf = std::conditional_t<LOSS == LOSS_PPO, HeadsArgsPpo, HeadsArgs>;
 
 // The per-sample head arithmetic runs in fp64: the softmax gradient
 // p_k (g_k - sum_j p_j g_j) cancels catastrophically when the policy saturates, and fp64 here
@@ -82,8 +101,10 @@ __device__ __forceinline__ double wave_max_d(double v, int w = 64) { return wave
 // ~80 dependent global round trips per sample (r04 ISA) — the heads launch's whole time.  With
 // AT every weight load of a lane's features is unconditional (features past F read feature
 // F - 1 and are multiplied by zero), so they are all in flight together.
-template <int FCH, int NZ, int AT>
-__device__ __forceinline__ void heads_sample(const HeadsArgs& p, int n, int lane) {
+// LOSS: the policy term (LOSS_A3C / LOSS_PPO), compile-time so that the A3C instantiations
+// carry nothing of the other; a LOSS_PPO launch is a training launch (p.train != 0).
+template <int FCH, int NZ, int AT, int LOSS>
+__device__ __forceinline__ void heads_sample(const HeadsArgsOf<LOSS>& p, int n, int lane) {
   const int A = AT ? AT : p.A;
   constexpr int NA = AT ? AT : MAXA;                 // loop bound over actions
   double acc[NA];
@@ -104,6 +125,7 @@ __device__ __forceinline__ void heads_sample(const HeadsArgs& p, int n, int lane
   float bpre[PRE ? AT + 1 : 1];                  // pi biases, v bias
   float blg[PRE ? FCH : 1];                      // legacy FC bias of the lane's features
   float Rpre = 0.f;
+  float4 rowpre = make_float4(0.f, 0.f, 0.f, 0.f);   // LOSS_PPO: the sample's row, one 16-byte load
   int apre = 0;
   float hv32[FCH > 0 ? FCH : 1];
   if constexpr (PRE) {
@@ -129,7 +151,8 @@ __device__ __forceinline__ void heads_sample(const HeadsArgs& p, int n, int lane
 #pragma unroll
     for (int a = 0; a < AT; ++a) bpre[a] = p.pib[a];
     bpre[AT] = p.vb[0];
-    Rpre = *(p.train ? p.R + n : p.pib);
+    if constexpr (LOSS == LOSS_PPO) rowpre = p.rows[n];
+    else Rpre = *(p.train ? p.R + n : p.pib);
     // the action's low word (actions are small and non-negative)
     apre = *(p.train ? reinterpret_cast<const int*>(p.action + n) : reinterpret_cast<const int*>(p.pib));
 #pragma unroll
@@ -249,7 +272,8 @@ __device__ __forceinline__ void heads_sample(const HeadsArgs& p, int n, int lane
   if (p.value && lane == 0) p.value[n] = (float)V;
   if (!p.train) return;
 
-  const double Rn = PRE ? (double)Rpre : (double)p.R[n];
+  if constexpr (LOSS == LOSS_PPO && !PRE) rowpre = p.rows[n];
+  const double Rn = LOSS == LOSS_PPO ? (double)rowpre.x : PRE ? (double)Rpre : (double)p.R[n];
   const int act = (int)(PRE ? apre : p.action[n]);
   const double adv = V - Rn;
   const double beta = (double)p.beta, invB = 1.0 / (double)p.B;
@@ -257,7 +281,17 @@ __device__ __forceinline__ void heads_sample(const HeadsArgs& p, int n, int lane
   const double lp = mine ? log(pe) : 0.0;
   const double xent = wave_sum_d(pr * lp, A);
   const double lpa = __shfl(lp, act, 64);
-  const double gp = mine ? ((lane == act ? adv / pe : 0.0) + beta * (lp + pr / pe)) * invB : 0.0;
+  double c = adv, t0 = lpa * adv;                   // the policy term's coefficient and value
+  if constexpr (LOSS == LOSS_PPO) {
+    const double Adv = Rn - (double)rowpre.y;
+    const double rho = exp(lpa - (double)rowpre.z);
+    const double eps = (double)p.clip_eps;
+    const double su = rho * Adv, sc = fmin(fmax(rho, 1.0 - eps), 1.0 + eps) * Adv;
+    c = su <= sc ? -Adv * rho : 0.0;                 // ties take the unclipped branch
+    t0 = -fmin(su, sc);
+    if (p.ratio && lane == 0) p.ratio[n] = (float)rho;
+  }
+  const double gp = mine ? ((lane == act ? c / pe : 0.0) + beta * (lp + pr / pe)) * invB : 0.0;
   const double sgp = wave_sum_d(gp * pr, A);
   const double dz = mine ? pr * (gp - sgp) : 0.0;
   const double dV = (V - Rn) * invB;
@@ -305,7 +339,7 @@ __device__ __forceinline__ void heads_sample(const HeadsArgs& p, int n, int lane
   }
   if (lane < NTERMS) {
     double t = 0.0;
-    t = lane == 0 ? lpa * adv : t;
+    t = lane == 0 ? t0 : t;
     t = lane == 1 ? xent : t;
     t = lane == 2 ? (V - Rn) * (V - Rn) : t;
     t = lane == 3 ? adv : t;
@@ -403,11 +437,11 @@ __global__ void __launch_bounds__(256) scalars_kernel(const float* terms, int B,
 // barrier.  The counter itself is a device atomic.  No step relies on release/acquire ordering.
 // (bx, nblk): the workgroup's index and the grid size (a plain launch: blockIdx.x, gridDim.x;
 // a chained multi-job launch, ba3c_multi.h: the job's own)
-template <int FCH, int NZ, int AT = 0>
-__device__ __forceinline__ void heads_body(const HeadsArgs& p, int bx, int nblk) {
+template <int FCH, int NZ, int AT = 0, int LOSS = LOSS_A3C>
+__device__ __forceinline__ void heads_body(const HeadsArgsOf<LOSS>& p, int bx, int nblk) {
   const int lane = threadIdx.x & 63;
   const int n = bx * 4 + (threadIdx.x >> 6);
-  if (n < p.B) heads_sample<FCH, NZ, AT>(p, n, lane);
+  if (n < p.B) heads_sample<FCH, NZ, AT, LOSS>(p, n, lane);
   if (p.train && p.scalars) {                 // uniform over the grid
     // terms go out with st_agent and ReLU counts with device atomics; each wave waits for its
     // own stores before the workgroup's arrival is counted (no L2 write-back fence)
@@ -423,9 +457,9 @@ __device__ __forceinline__ void heads_body(const HeadsArgs& p, int bx, int nblk)
   }
 }
 
-template <int FCH, int NZ, int AT = 0>
-__global__ void __launch_bounds__(256) heads_kernel(const HeadsArgs p) {
-  heads_body<FCH, NZ, AT>(p, blockIdx.x, gridDim.x);
+template <int FCH, int NZ, int AT = 0, int LOSS = LOSS_A3C>
+__global__ void __launch_bounds__(256) heads_kernel(const HeadsArgsOf<LOSS> p) {
+  heads_body<FCH, NZ, AT, LOSS>(p, blockIdx.x, gridDim.x);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1071,6 +1105,40 @@ __global__ void __launch_bounds__(256) sample_kernel(const float* __restrict__ p
     a += (c / tot <= un) ? 1 : 0;
   }
   actions[n] = a;
+  if (bad && flag) atomicOr(flag, bad);
+}
+
+// sample_kernel that also records the behaviour policy's log-probability of the drawn action:
+// the same two passes over `probs` in the same order (the same actions and flag), then
+// logp[n] = log(pi[n][min(a, A - 1)] + 1e-6) in fp64 — the heads' log(p_a + 1e-6) of the PPO
+// ratio.  probs: the distribution sampled from ('logitsT'), pi: the one whose log is recorded
+// ('logits'); they may be the same array (no __restrict__ on either).
+__global__ void __launch_bounds__(256) sample_logp_kernel(const float* probs, const float* pi,
+                                                          const double* __restrict__ u, int B, int A,
+                                                          int64_t* __restrict__ actions,
+                                                          float* __restrict__ logp, int* flag) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= B) return;
+  const float* pn = probs + (size_t)n * A;
+  double cum = 0.0;
+  int bad = 0;
+  for (int k = 0; k < A; ++k) {
+    const float pk = pn[k];
+    if (!isfinite(pk)) bad |= 1;
+    if (pk < 0.f) bad |= 4;
+    cum += (double)pk;
+  }
+  if (fabs(cum - 1.0) > 3.4526698300124393e-04) bad |= 2;
+  const double tot = cum;
+  const double un = u[n];
+  int64_t a = 0;
+  double c = 0.0;
+  for (int k = 0; k < A; ++k) {
+    c += (double)pn[k];
+    a += (c / tot <= un) ? 1 : 0;
+  }
+  actions[n] = a;
+  logp[n] = (float)log((double)pi[(size_t)n * A + min((int)a, A - 1)] + 1e-6);
   if (bad && flag) atomicOr(flag, bad);
 }
 

@@ -166,6 +166,29 @@ int ba3c_train_grads_phase(ba3c_handle* h, void* stream, const float* params, co
                            const int64_t* action, const float* futurereward, int32_t batch,
                            float entropy_beta, void* workspace, float* grads, double* scalars,
                            int32_t phase);
+/* ba3c_train_grads_phase with the clipped-surrogate (PPO, Schulman et al. 2017) policy term in
+ * place of the A3C one; every other launch, the phases 0-4 and their meaning, the scalars and
+ * their scaling are ba3c_train_grads_phase's (the heads run in phase 1).
+ * rows: fp32 [B][4], row n = {R, V_old, l_old, 0} — the return (the value target, the A3C
+ * futurereward), the predictor's value when the action was taken and l_old =
+ * log(pi_old(a) + 1e-6) (ba3c_sample_logp).  With p = softmax(z), lp = log(p + 1e-6) and the
+ * current value V:
+ *   Adv  = R - V_old                                   (a constant of the sample)
+ *   rho  = exp(lp[a] - l_old)
+ *   s    = -min(rho Adv, clip(rho, 1 - clip_eps, 1 + clip_eps) Adv)
+ *   cost = (sum_n s + entropy_beta sum_n sum_k p_k lp_k + 1/2 sum_n (V - R)^2) / B
+ * and its gradient is the A3C one with the advantage factor replaced by
+ *   c = (rho Adv <= clip(rho, ...) Adv) ? -Adv rho : 0        (a tie takes the unclipped branch);
+ * at rho = 1 and V_old = V it is ba3c_train_grads' gradient.  scalars[1] (policy_loss) is
+ * sum_n s * 128 / B; scalars[4] (advantage) stays mean(V - R) with the current V.
+ * ratio: fp32 [B] device memory, receives rho per sample; may be NULL.
+ * Refused with BA3C_ERR_INVALID before any GPU call: rows NULL or not 16-byte aligned, ratio
+ * given but not 16-byte aligned, clip_eps not in (0, 1) (a NaN included), phase outside 0..4,
+ * then ba3c_train_grads_phase's own checks. */
+int ba3c_train_grads_ppo(ba3c_handle* h, void* stream, const float* params, const uint8_t* state,
+                         const int64_t* action, const float* rows, int32_t batch,
+                         float entropy_beta, float clip_eps, void* workspace, float* grads,
+                         double* scalars, float* ratio, int32_t phase);
 /* Launch the reduction a phase-4 pass held back, on `stream`; no-op when none is held.  The
  * caller orders `stream` after the phase-4 pass (e.g. by waiting for the ba3c_set_phase2_event
  * event, which follows it); the implicit launches of the other entry points order themselves
@@ -223,6 +246,15 @@ int ba3c_apply_update_dev(ba3c_handle* h, void* stream, int32_t opt, float* para
  * set to 1 if any probability is not finite (train.py:381 assert). */
 int ba3c_sample(void* stream, const float* probs, const double* u, int32_t batch,
                 int32_t num_actions, int64_t* actions, int32_t* nonfinite);
+
+/* ba3c_sample that also records the behaviour policy's log-probability of the drawn action:
+ * actions and nonfinite are exactly ba3c_sample(probs, u, ...)'s, and
+ * logp[i] = (float) log((double) pi[i][min(actions[i], A-1)] + 1e-6)  (fp32 [B], device).
+ * probs is the distribution sampled from ('logitsT'), pi the one whose log is recorded
+ * ('logits', the l_old of ba3c_train_grads_ppo's rows); they may be the same pointer. */
+int ba3c_sample_logp(void* stream, const float* probs, const float* pi, const double* u,
+                     int32_t batch, int32_t num_actions, int64_t* actions, float* logp,
+                     int32_t* nonfinite);
 
 /* Evaluation action (OpenAIGym/common.py:24-33, play_one_episode): actions[i] = first argmax of
  * probs[i] (np.argmax), or random_actions[i] (the player's action_space.sample()) when

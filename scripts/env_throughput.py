@@ -24,11 +24,16 @@ identical full memories at (simulators, slots) = (100, 6), (1024, 33), (4096, 12
 of 20 event-bracketed batches of 20 launches each, alternating; and ms per
 `ActorLearner.iterate` on GridBoxing at 100 simulators with the default returns and with
 20-step GAE(0.95) returns.
+With --ppo also the PPO learner step (`Ba3cTrainer.train_step(..., rows, clip)`, ba3c_amd.ppo) next
+to the A3C step on identical batches at (B, F, S) = (32, 128, 4) and (2048, 512, 1), by the same
+method (medians of event-bracketed batches of steps, alternating), and ms per
+`ActorLearner.iterate` and samples/s on GridBoxing at 100 simulators with the A3C loop and with
+--ppo_clip 0.2 at 4 epochs x 4 minibatches; --ppo_only skips the environment tables.
 Prints one JSON line.
 
     python scripts/env_throughput.py [--game boxing] [--envs 8192 64] [--iters 200] [--random 20]
                                      [--frame_skip 2-4] [--sticky 0.25] [--view 1 3] [--duel]
-                                     [--duel_start 8-14] [--duel_only] [--returns]
+                                     [--duel_start 8-14] [--duel_only] [--returns] [--ppo] [--ppo_only]
 """
 import argparse
 import json
@@ -192,10 +197,46 @@ def returns_table(repeats):
     return out
 
 
+PPO_SHAPES = [(32, 128, 4), (2048, 512, 1)]
+
+
+def ppo_step_table(repeats, clip=0.2):
+    """--ppo: µs per learner step (pass + fused clip + Adam apply) with the A3C loss and with the
+    clipped-surrogate loss on the same batch: rows = {R, the forward's value, sample_logp's logp,
+    0} of the policy before the timed steps, so the ratios move as the steps train."""
+    from ba3c_amd.model import Model
+    from ba3c_amd.optimizer import AdamOptimizer
+    from ba3c_amd.trainer import Ba3cTrainer, TrainConfig
+    out = {}
+    for B, F, S in PPO_SHAPES:
+        m = Model(num_actions=4, fc_neurons=F, fc_splits=S, batch_size=B, max_batch=B, seed=0)
+        tr = Ba3cTrainer(TrainConfig(model=m, optimizer=AdamOptimizer(1e-5, 0.8, 0.75, 1e-8)))
+        g = torch.Generator(device="cuda").manual_seed(B)
+        st = torch.randint(0, 256, (B, 84, 84, 4), generator=g, device="cuda").to(torch.uint8)
+        R = torch.randn(B, generator=g, device="cuda")
+        u = torch.rand(B, generator=g, device="cuda", dtype=torch.float64)
+        probs, probsT, value = m.engine.forward(st)
+        ac, logp, _ = m.engine.sample_logp(probsT, probs, u)
+        rows = torch.stack([R, value, logp, torch.zeros_like(R)], dim=1).contiguous()
+        legs = {"a3c_us": lambda: tr.train_step(st, ac, R),
+                "ppo_us": lambda: tr.train_step(st, ac, None, rows=rows, clip=clip)}
+        t = {k: [] for k in legs}
+        for _ in range(repeats):
+            for k, fn in legs.items():
+                t[k].append(timed_median(fn))
+        row = {k: [round(v, 2) for v in vs] for k, vs in t.items()}
+        row["ppo_over_a3c"] = round(min(t["ppo_us"]) / min(t["a3c_us"]), 4)
+        row["clip_fraction_after"] = round(float(((m.ratio - 1).abs() > clip).float().mean().item()), 4)
+        out["B%d_F%d_S%d" % (B, F, S)] = row
+        tr.check_device_errors()
+    return out
+
+
 def iterate_table(settings, iters=420, warmup=42, E=100):
-    """--returns: ms per ActorLearner.iterate on GridBoxing at E simulators (README flags: B = 32,
-    F = 128, S = 4, Adam) per (local_time_max, gae_lambda) setting: a host clock around `iters`
-    iterations ending in a device synchronise (420 = a multiple of both rollout periods)."""
+    """--returns / --ppo: ms per ActorLearner.iterate on GridBoxing at E simulators (README flags:
+    B = 32, F = 128, S = 4, Adam) per (local_time_max, gae_lambda[, ppo.Setting]) setting: a host
+    clock around `iters` iterations ending in a device synchronise (420 = a multiple of both
+    rollout periods)."""
     import time
 
     from ba3c_amd.actor_learner import ActorLearner
@@ -204,20 +245,26 @@ def iterate_table(settings, iters=420, warmup=42, E=100):
     from ba3c_amd.optimizer import AdamOptimizer
     from ba3c_amd.trainer import Ba3cTrainer, TrainConfig
     out = {}
-    for ltm, lam in settings:
+    for setting in settings:
+        ltm, lam = setting[:2]
+        ppo = setting[2] if len(setting) > 2 else None
         m = Model(num_actions=18, fc_neurons=128, fc_splits=4, batch_size=32, max_batch=max(32, E), seed=0)
         tr = Ba3cTrainer(TrainConfig(model=m, optimizer=AdamOptimizer(1e-3, 0.8, 0.75, 1e-8)))
         al = ActorLearner(tr, n_envs=E, batch_size=32, seed=0, env=BoxingVec(E, seed=0),
-                          local_time_max=ltm, gae_lambda=lam)
+                          local_time_max=ltm, gae_lambda=lam, ppo=ppo)
         al.run(warmup)
         torch.cuda.synchronize()
         steps0, t0 = al.train_steps, time.time()
         al.run(iters)
         torch.cuda.synchronize()
         dt = time.time() - t0
-        out.setdefault("local_time_max=%d,gae_lambda=%g" % (ltm, lam), []).append({
+        key = "local_time_max=%d,gae_lambda=%g" % (ltm, lam)
+        if ppo is not None:
+            key += ",ppo_clip=%g,epochs=%d,minibatches=%d" % tuple(ppo)
+        out.setdefault(key, []).append({
             "ms_per_iterate": round(dt * 1e3 / iters, 3), "iterations": iters,
-            "train_steps": al.train_steps - steps0})
+            "train_steps": al.train_steps - steps0,
+            "samples_per_s": round((al.train_steps - steps0) * 32 / dt, 1)})
     return out
 
 
@@ -226,6 +273,10 @@ def main(argv=None):
     ap.add_argument("--returns", action="store_true",
                     help="also time ba3c_lambda_returns next to ba3c_nstep_returns, and one "
                          "ActorLearner iteration with 5-step n-step and 20-step GAE(0.95) returns")
+    ap.add_argument("--ppo", action="store_true",
+                    help="also time the PPO learner step next to the A3C step on identical batches, "
+                         "and one ActorLearner iteration with and without --ppo_clip 0.2 (4 x 4)")
+    ap.add_argument("--ppo_only", action="store_true", help="--ppo: skip the environment tables")
     ap.add_argument("--duel", action="store_true",
                     help="also time two-player GridBoxing at G = E / 2 games against BoxingVec at E")
     ap.add_argument("--envs", type=int, nargs="+", default=[8192, 64])
@@ -271,7 +322,7 @@ def main(argv=None):
         out["fill_GBps"] = round(fill.numel() / us / 1e3, 1)
         del fill
 
-    for E in ([] if args.duel and args.duel_only else args.envs):
+    for E in ([] if (args.duel and args.duel_only) or (args.ppo and args.ppo_only) else args.envs):
         g = torch.Generator(device="cuda").manual_seed(0)
         actions = torch.randint(0, A, (E,), generator=g, device="cuda")
         env, hist = Vec(E, seed=0), FrameHistory(E, 4, 1)
@@ -336,6 +387,11 @@ def main(argv=None):
     if args.returns:
         out["returns"] = returns_table(args.repeats)
         out["iterate"] = iterate_table([(5, 1.0), (20, 0.95), (5, 1.0), (20, 0.95)])
+    if args.ppo:
+        from ba3c_amd.ppo import Setting
+        out["ppo_step"] = ppo_step_table(args.repeats)
+        on = Setting(clip=0.2, epochs=4, minibatches=4)
+        out["ppo_iterate"] = iterate_table([(5, 1.0), (5, 1.0, on), (5, 1.0), (5, 1.0, on)])
     if args.random:
         from ba3c_amd.evaluate import eval_with_envs, uniform_policy
         from ba3c_amd.model import Model
