@@ -231,6 +231,19 @@ def test_greedy_eval_action_matches_numpy_argmax():
     want = np.where(u < 0.001, rand, np.argmax(probs, axis=1))
     got = eng.greedy(dev(probs), dev(u), dev(rand), eps=0.001).cpu().numpy()
     np.testing.assert_array_equal(got, want)
+    # the action counts at the two ends of ba3c_create's range: one action (nothing to compare:
+    # action 0 whatever the row holds) and 31 (ties and NaNs in the last columns)
+    for A in (1, 31):
+        probs = rs.dirichlet(np.ones(A) * 0.5, size=B).astype(np.float32)
+        probs[::17] = 1.0 / A
+        probs[5::23, A // 2] = probs[5::23, A - 1] = 0.9
+        probs[7::29, A - 1] = np.nan
+        probs[9::31, A // 3] = np.nan
+        probs[9::31, A - 1] = np.nan
+        rand = rs.randint(0, A, size=B).astype(np.int64)
+        want = np.where(u < 0.001, rand, np.argmax(probs, axis=1))
+        got = eng.greedy(dev(probs), dev(u), dev(rand), eps=0.001).cpu().numpy()
+        np.testing.assert_array_equal(got, want)
 
 
 @pytest.mark.parametrize("var,base,mode", [("BA3C_C1PAIR", None, "0"), ("BA3C_SCALARS_RIDE", "0", "1")])

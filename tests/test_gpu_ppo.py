@@ -166,7 +166,7 @@ def test_train_grads_is_unchanged_around_ppo_calls():
     assert torch.equal(before[0], after[0]) and torch.equal(before[1], after[1])
 
 
-@pytest.mark.parametrize("A", [4, 18])
+@pytest.mark.parametrize("A", [1, 4, 18, 31])
 @pytest.mark.parametrize("B", [1, 100, 1000])
 def test_sample_logp_is_sample_plus_the_log(A, B):
     eng = engine()
