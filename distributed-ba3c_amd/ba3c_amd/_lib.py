@@ -77,10 +77,7 @@ def load():
         "ba3c_train_grads_ppo": (i32, [P, P, P, P, P, P, i32, f32, f32, P, P, P, P, i32]),
         "ba3c_sample_logp": (i32, [P, P, P, P, i32, i32, P, P, P]),
         "ba3c_bucket_tensor": (i32, [P]),
-        "ba3c_flush_pending": (i32, [P]),
-        "ba3c_launch_held": (i32, [P, P]),
         "ba3c_set_phase2_event": (i32, [P, P]),
-        "ba3c_clip_grads_range2": (i32, [P, P, P, P, i32, i32, i32]),
         "ba3c_occupy_cus": (i32, [P, i32, ctypes.c_double]),
         "ba3c_comm_unique_id": (i32, [P]),
         "ba3c_comm_init": (i32, [P, P, i32, i32]),

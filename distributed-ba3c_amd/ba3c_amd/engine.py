@@ -163,10 +163,7 @@ class Ba3cEngine(object):
     def train_grads(self, state, action, futurereward, entropy_beta=0.01, grads=None, phase=0):
         """Forward + loss + backward; raw gradients into `grads` (default self.grads).
         Returns the device float64 scalars tensor (order: _lib.SCALAR_NAMES).  phase 1 / 2
-        split the pass at the fc1 + heads bucket (ba3c_train_grads_phase); phase 3 leaves the
-        final gradient reduction to the next fused-clip apply_update (one launch fewer): until
-        then `grads` holds unreduced data for any reader outside this handle — call
-        flush_pending() before reading it through torch."""
+        split the pass at the fc1 + heads bucket (ba3c_train_grads_phase)."""
         B = self._check_state(state)
         assert action.dtype == torch.int64 and action.shape == (B,) and action.is_cuda
         assert futurereward.dtype == torch.float32 and futurereward.shape == (B,)
@@ -203,10 +200,6 @@ class Ba3cEngine(object):
                                                  _ptr(self.scalars), _ptr(ratio), int(phase)))
         return self.scalars
 
-    def flush_pending(self):
-        """Launch a weight-gradient reduction a phase-3 pass left pending (no-op otherwise)."""
-        _lib.check(self.lib.ba3c_flush_pending(self.h))
-
     def occupy_cus(self, stream, n_cus, usec):
         """Diagnostic: hold `n_cus` CUs for `usec` microseconds on torch stream `stream`."""
         _lib.check(self.lib.ba3c_occupy_cus(ctypes.c_void_p(stream.cuda_stream), int(n_cus),
@@ -217,19 +210,11 @@ class Ba3cEngine(object):
         t = int(self.lib.ba3c_bucket_tensor(self.h))
         return t, self.layout[t][1]
 
-    def clip_grads_range(self, t0, t1, grads=None, no_residency=False):
-        """clip_by_average_norm over tensors [t0, t1) only.  no_residency: the two-launch form
-        (for a stream that runs beside other kernels, ba3c_clip_grads_range2)."""
+    def clip_grads_range(self, t0, t1, grads=None):
+        """clip_by_average_norm over tensors [t0, t1) only."""
         grads = self.grads if grads is None else grads
-        _lib.check(self.lib.ba3c_clip_grads_range2(self.h, _stream(), _ptr(grads),
-                                                   _ptr(self._workspace(True)), int(t0), int(t1),
-                                                   1 if no_residency else 0))
-
-    def launch_held(self, stream=None):
-        """Launch the fc1 + heads reduction a phase-4 pass held back, on `stream` (a torch
-        stream, default the current one), ordered after the pass's stream."""
-        st = ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
-        _lib.check(self.lib.ba3c_launch_held(self.h, st))
+        _lib.check(self.lib.ba3c_clip_grads_range(self.h, _stream(), _ptr(grads),
+                                                  _ptr(self._workspace(True)), int(t0), int(t1)))
 
     def set_phase2_event(self, event):
         """Record `event` (a hipevent.HipEvent, or None) in every later phase-2 pass after conv3's

@@ -455,48 +455,19 @@ class SyncReplicasOptimizer(object):
     _ready_event = None
     _fc1_join = None
 
-    def aggregate_held_bucket_async(self, engine, mid, t0, t1, off0, off1, marks=None, held=True):
-        """The N>1 step's first bucket (fc1 + heads): on the exchange stream, once `mid`
-        (recorded in phase 2 right after conv3's launches) has passed, the bucket's sum.
-        Starting there puts the collective's workgroups at the boundary before conv2's launch,
-        whose short non-persistent workgroups the dispatcher rebalances, rather than beside
-        conv3's persistent ones.  `held` (a phase-4 pass, BA3C_XCHG_HELD=1): the held reduction
-        of the bucket's weight gradients and the bucket's clip in its two-launch form (it runs
-        beside phase 2's kernels, so its workgroups cannot assume co-residency) run there
-        first; otherwise the caller clipped the bucket on its own stream after phase 1.
-        `marks`: (start, ready, begin, end) timing events on the exchange stream.  Returns the
-        work handle (always: the update must join the exchange stream)."""
-        start, ready, begin, end = marks if marks is not None else (None, None, None, None)
-        dev = engine.grads.device
-        buf = engine.grads[off0:off1]
-        if not buf.is_cuda:                   # CPU engines (tests): no streams
-            if held:
-                engine.launch_held()
-                engine.clip_grads_range(t0, t1)
-            return self._all_reduce(buf, async_op=True) if self.distributed else None
-        rccl = self.direct_rccl(dev) if self.distributed else None   # (collective on first use)
-        comm = self.comm_stream(dev)
-        if isinstance(mid, hipevent.HipEvent):
-            mid.wait(comm)
-        else:
-            comm.wait_event(mid)
-        join = _StreamJoin(comm)
+    def _sum_on_exchange_stream(self, engine, buf, comm, rccl, begin, end):
+        """Start the sum of `buf` on the exchange stream `comm` (already ordered after the
+        bucket's clip) by whichever transport the group has: host-staged (gloo), RCCL driven
+        directly, or torch's collective.  begin / end: timing events around it on `comm`.
+        Returns the work handle."""
         with torch.cuda.stream(comm):
-            if start is not None:
-                start.record(comm)
-            if held:
-                engine.launch_held(comm)
-                engine.clip_grads_range(t0, t1, no_residency=True)
-            if ready is not None:
-                ready.record(comm)
-            if not self.distributed:
-                return join
             if begin is not None:
                 begin.record(comm)
             if self._staged(buf):
                 host = buf.cpu()              # host-staged (gloo): waits for the clip
                 work = dist.all_reduce(host, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
                 return _StagedWork(work, host, buf, stream=comm, end=end)
+            join = _StreamJoin(comm)
             if rccl is not None:
                 rccl.all_reduce_sum(buf, comm)
                 self._occupy(engine, comm)
@@ -512,6 +483,32 @@ class SyncReplicasOptimizer(object):
             if end is not None:
                 end.record(comm)
         return join
+
+    def aggregate_fc1_bucket_async(self, engine, mid, off0, off1, marks=None):
+        """The N>1 step's first bucket (fc1 + heads), which the caller clipped on its own stream
+        after phase 1: on the exchange stream, once `mid` (recorded in phase 2 right after
+        conv3's launches) has passed, the bucket's sum.  Starting there puts the collective's
+        workgroups at the boundary before conv2's launch, whose short non-persistent workgroups
+        the dispatcher rebalances, rather than beside conv3's persistent ones.
+        `marks`: (start, ready, begin, end) timing events on the exchange stream.  Returns the
+        work handle (on a device always: the update must join the exchange stream)."""
+        start, ready, begin, end = marks if marks is not None else (None, None, None, None)
+        buf = engine.grads[off0:off1]
+        if not buf.is_cuda:                   # CPU engines (tests): no streams
+            return self._all_reduce(buf, async_op=True) if self.distributed else None
+        rccl = self.direct_rccl(buf.device) if self.distributed else None   # (collective on first use)
+        comm = self.comm_stream(buf.device)
+        if isinstance(mid, hipevent.HipEvent):
+            mid.wait(comm)
+        else:
+            comm.wait_event(mid)
+        if start is not None:
+            start.record(comm)
+        if ready is not None:
+            ready.record(comm)
+        if not self.distributed:
+            return _StreamJoin(comm)
+        return self._sum_on_exchange_stream(engine, buf, comm, rccl, begin, end)
 
     def aggregate_bucket_async(self, engine, t0, t1, off0, off1, marks=None, last=False):
         """Clip tensors [t0, t1) and start the RCCL sum of flat range [off0, off1); returns
@@ -553,30 +550,7 @@ class SyncReplicasOptimizer(object):
         if self._ready_event is None:
             self._ready_event = hipevent.join_event()
         hipevent.wait_stream(comm, cur, self._ready_event)
-        with torch.cuda.stream(comm):
-            if begin is not None:
-                begin.record(comm)
-            if self._staged(buf):
-                host = buf.cpu()              # host-staged (gloo): waits for the clip
-                work = dist.all_reduce(host, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
-                return _StagedWork(work, host, buf, stream=comm, end=end)
-            if rccl is not None:
-                rccl.all_reduce_sum(buf, comm)
-                self._occupy(engine, comm)
-                if self._ar_event is None:
-                    self._ar_event = hipevent.join_event()
-                self._ar_event.record(comm)
-                self._ar_done = self._ar_event
-            else:
-                work = dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
-                work.wait()                   # `comm` waits for the collective's stream
-                self._occupy(engine, comm)
-            if end is not None:
-                end.record(comm)
-        join = _StreamJoin(comm)
-        if rccl is not None:
-            self._fc1_join = join
-        return join
+        return self._sum_on_exchange_stream(engine, buf, comm, rccl, begin, end)
 
     # bench.py --occupy: (K, microseconds) — after the fc1 + heads bucket's sum, a launch on the
     # exchange stream holds K CUs for that long (ba3c_occupy_cus), standing in for the CUs

@@ -6,7 +6,6 @@ gradient processors (fused clip), the synchronous RCCL gradient mean when
 SyncReplicasOptimizer is used, and one fused optimizer apply; it returns the TfDictOp
 dictionary of the reference (multigpu.py:193-205).
 """
-import os
 import time
 
 import numpy as np
@@ -35,9 +34,9 @@ class ExchangeTimeline(object):
     """HIP timing events of the bucketed data-parallel step (Ba3cTrainer._bucketed_sync_step),
     recorded inside the real step: on the learner stream `start`, `phase1_end`, `conv_ready`
     (phase 2 + the conv bucket's clip done), `exchanged` (both sums joined) and `end` (update
-    applied); on the exchange stream `fc1_start` (the phase-2 event passed), `fc1_ready` (the
-    held fc1 + heads reduction and the bucket's clip done) and each bucket's all-reduce
-    begin / end.  summary() averages the intervals over the steps."""
+    applied); on the exchange stream `fc1_start` (the phase-2 event passed), `fc1_ready`
+    (right after it: the bucket's clip has run on the learner stream) and each bucket's
+    all-reduce begin / end.  summary() averages the intervals over the steps."""
 
     MAIN = ("start", "phase1_end", "conv_ready", "exchanged", "end")
     COMM = ("fc1_start", "fc1_ready", "fc1_ar_begin", "fc1_ar_end", "conv_ar_begin", "conv_ar_end")
@@ -55,8 +54,8 @@ class ExchangeTimeline(object):
         if not self.steps:
             return None
         keys = {"phase1_ms": ("start", "phase1_end"), "phase2_ms": ("phase1_end", "conv_ready"),
-                # exchange stream: the held fc1 + heads reduction and the bucket's clip, from
-                # the phase-2 event (after conv3) on
+                # exchange stream, back to back after the phase-2 event: ~0 (nothing is
+                # prepared there; bench.py reads the key)
                 "fc1_prep_ms": ("fc1_start", "fc1_ready"),
                 "fc1_start_after_phase1_ms": ("phase1_end", "fc1_start"),
                 "fc1_allreduce_ms": ("fc1_ar_begin", "fc1_ar_end"),
@@ -85,22 +84,6 @@ class Ba3cTrainer(object):
                             and isinstance(procs[0].func, ClipByAverageNorm)
                             and procs[0].regex == ".*$")
         self._procs = procs
-        # BA3C_DEFER_REDUCE=1 (single replica): the pass's weight-gradient reduction rides on the
-        # fused apply's launch (ba3c_train_grads_phase phase 3: one launch fewer).  Default off:
-        # same-box r05ab, B=32 step 0.1607 -> 0.1646 ms, B=2048 1.743 -> 1.752 ms (the hand-off's
-        # agent-scope stores / loads and signal counters cost more than the launch boundary)
-        flag = os.environ.get("BA3C_DEFER_REDUCE", "0")
-        if flag not in ("0", "1"):
-            raise ValueError("BA3C_DEFER_REDUCE must be 0 or 1 (got %r)" % flag)
-        self._defer_reduce = flag == "1"
-        # BA3C_XCHG_HELD=1: the N>1 step holds phase 1's fc1 + heads reduction and runs it and
-        # the bucket's clip on the exchange stream (ba3c_launch_held).  Default 0: same-box
-        # r06c, the held work beside conv2's launch stretched that launch by 24 us, more than
-        # the ~16 us it took off the learner stream
-        flag = os.environ.get("BA3C_XCHG_HELD", "0")
-        if flag not in ("0", "1"):
-            raise ValueError("BA3C_XCHG_HELD must be 0 or 1 (got %r)" % flag)
-        self._xchg_held = flag == "1"
         if isinstance(self.optimizer, SyncReplicasOptimizer):
             self.optimizer.broadcast_variables(self.engine)
 
@@ -161,12 +144,7 @@ class Ba3cTrainer(object):
             self._bucketed_sync_step(state, action, futurereward)
             self.global_step += 1
             return
-        if self._defer_reduce and self._fused_clip and not isinstance(opt, SyncReplicasOptimizer):
-            self.model.train_phase = 3
-        try:
-            self.model.build_graph([state, action, futurereward])
-        finally:
-            self.model.train_phase = 0
+        self.model.build_graph([state, action, futurereward])
         if isinstance(opt, SyncReplicasOptimizer):
             if self._fused_clip:
                 opt.aggregate(self.engine)
@@ -200,24 +178,20 @@ class Ba3cTrainer(object):
             self._mid = hipevent.HipEvent(hipevent.HIP_EVENT_DISABLE_TIMING
                                           | hipevent.HIP_EVENT_RELEASE_TO_DEVICE)
             eng.set_phase2_event(self._mid)
-        held = self._xchg_held
         mark("start")
         try:
-            # phase 1; BA3C_XCHG_HELD=1: phase 4, its fc1 + heads reduction held back for the
-            # exchange stream
-            m.train_phase = 4 if held else 1
+            m.train_phase = 1
             m.build_graph(inputs)
             mark("phase1_end")
-            if not held:
-                eng.clip_grads_range(tb, nt)     # the bucket's clip (one launch)
+            eng.clip_grads_range(tb, nt)     # the bucket's clip (one launch)
             m.train_phase = 2
             m.build_graph(inputs)
         finally:
             m.train_phase = 0
         # the fc1 + heads bucket's sum on the exchange stream from the phase-2 event on, beside
-        # conv2..conv0's backward (held: its reduction and clip first)
-        work = opt.aggregate_held_bucket_async(
-            eng, self._mid, tb, nt, off, total, held=held,
+        # conv2..conv0's backward
+        work = opt.aggregate_fc1_bucket_async(
+            eng, self._mid, off, total,
             marks=tl and (tl["fc1_start"], tl["fc1_ready"], tl["fc1_ar_begin"], tl["fc1_ar_end"]))
         work2 = opt.aggregate_bucket_async(
             eng, 0, tb, 0, off, last=True,

@@ -90,8 +90,7 @@ struct TensorDesc {
   int32_t ndim;
 };
 
-constexpr int CHAIN_SITES = 2;   // chained launch sites (launch_chain)
-constexpr int CHAIN_SPREAD = 32; // spread signal counters of a site with many signalling workgroups
+constexpr int CHAIN_SITES = 1;   // chained launch sites (launch_chain)
 
 struct ba3c_handle {
   ba3c_config cfg;
@@ -124,28 +123,12 @@ struct ba3c_handle {
   // boundary): CHAIN_SITES x 4 words + an error word after the tags (null: no device memory,
   // unchained launches)
   unsigned* chain = nullptr;
-  unsigned* spread = nullptr;   // CHAIN_SPREAD counters, CHAIN_STRIDE words apart (64-byte aligned)
-  // ba3c_train_grads_phase(phase 3): the pass's weight-gradient reduction is left pending and
-  // the next fused-clip apply on the handle runs it as the signalling job of a chained launch
-  // (reduce -> clip + update, one launch fewer); any other entry point launches it first
-  bool pend_reduce = false;
-  hipStream_t pend_stream = nullptr;
-  const float* pend_grads = nullptr;
-  hipEvent_t ev_pend = nullptr;   // orders a flush on the pass's stream before another stream
-  bool defer_final = false;   // set by train_grads_impl for phase 3
-  // phase 4 (phase 1 with its reduction held): the fc1 + heads weight-gradient reduction is
-  // kept here, unlaunched, until ba3c_launch_held puts it on the caller's stream (the exchange
-  // stream of the N>1 step); phase 2 does not launch it, every other entry point does
-  bool held = false;
-  hipStream_t held_stream = nullptr;
-  ReduceJobs held_jobs{};
   // recorded on the pass's stream after conv3's input- and weight-gradient launches of every
   // phase-2 pass (ba3c_set_phase2_event; null: none)
   hipEvent_t ev_mid = nullptr;
   hipStream_t side = nullptr;
   hipEvent_t ev_fork[4] = {}, ev_join = nullptr;
-  // weight-gradient reductions of the backward pass (BackwardPass), launched together at its
-  // end, or kept for a pending (phase 3) launch
+  // weight-gradient reductions of the backward pass (BackwardPass), launched together at its end
   ReduceJobs rjobs{};
   // RCCL communicator of the C-ABI gradient exchange (ba3c_comm_init; null: none)
   ncclComm_t comm = nullptr;
@@ -479,21 +462,20 @@ int launch_multi(hipStream_t s, const typename J0::Args& a0, dim3 g0, const type
 // A chained multi-job launch (ba3c_multi.h): jobs [0, nsig) signal, the jobs in `wmask` wait
 // for them (those in `late` inside their body); `site` picks the launch site's counter words.
 // Callers check chain_ok() first.
-constexpr int CHAIN_PREP_CONV0 = 0, CHAIN_REDUCE_UPDATE = 1;
+constexpr int CHAIN_PREP_CONV0 = 0;
 bool chain_ok(const ba3c_handle* h) { return h->sw.chain && h->chain != nullptr; }
 
 template <bool W2, class J0, class J1, class J2 = NoJob>
 int launch_chain(hipStream_t s, int site, int nsig, int wmask, int late, const typename J0::Args& a0, dim3 g0,
                  const typename J1::Args& a1, dim3 g1, const typename J2::Args& a2 = typename J2::Args{},
-                 dim3 g2 = dim3(0, 1, 1), ba3c_handle* h = nullptr, int kid = -1, bool spread = false) {
+                 dim3 g2 = dim3(0, 1, 1), ba3c_handle* h = nullptr, int kid = -1) {
   const MultiGrid g = multi_grid(g0, g1, g2);
   const int end = g.end[2];
   if (end == 0) return BA3C_OK;
   int nwait = 0;
   for (int j = 0; j < 3; ++j)
     if ((wmask >> j) & 1) nwait += g.end[j] - (j ? g.end[j - 1] : 0);
-  const ChainArgs c{h->chain + 4 * site, h->chain + 4 * CHAIN_SITES, nsig, wmask, nwait, late,
-                    h->spread, spread ? CHAIN_SPREAD : 0};
+  const ChainArgs c{h->chain + 4 * site, h->chain + 4 * CHAIN_SITES, nsig, wmask, nwait, late};
   std::optional<ProbeScope> probe;
   if (kid >= 0) probe.emplace(h, s, kid);
   if constexpr (W2)
@@ -775,7 +757,7 @@ int ensure_side_stream(ba3c_handle* h, hipStream_t s) {
 // fc1 products and their reductions (those gradients are final when it returns); phase 2:
 // conv3..conv0 and theirs.  Phases 1 + 2 compute exactly phase 0; between them a data-parallel
 // caller can all-reduce the fc1 + heads bucket (most of the parameters) while the conv layers
-// run.  phase 4: phase 1 with its reduction held (ba3c_launch_held).
+// run.
 // The weight-gradient kernels (heads, fc1, conv3..conv1) run on `ws`: the side stream where
 // the plan asks for it, each after the event that publishes its output gradient (the side
 // stream joins a graph capture of `s` through the fork events), else `s`.  The input-gradient
@@ -797,8 +779,7 @@ struct BackwardPass {
   int B, phase;
   int nfork = 0;
 
-  // every weight-gradient reduction is deferred into one launch at the end (h->rjobs: a phase-3
-  // pass leaves it there for the next fused apply)
+  // every weight-gradient reduction is deferred into one launch at the end (h->rjobs)
   BackwardPass(ba3c_handle* h_, hipStream_t s_, const LaunchPlan& pl_, const Workspace& w_, const float* prm_,
                const uint8_t* state_, float* grads_, int B_, int phase_)
       : h(h_), s(s_), ws(pl_.side_stream && h_->side ? h_->side : s_), pl(pl_), w(w_), prm(prm_), state(state_),
@@ -814,7 +795,7 @@ struct BackwardPass {
   int run() {
     CHECK(fork());
     if (phase != 2) CHECK(fc_and_heads());
-    if (phase == 1 || phase == 4) return finish();
+    if (phase == 1) return finish();
     CHECK(conv3());
     if (phase == 2 && h->ev_mid) HIP_TRY(hipEventRecord(h->ev_mid, s));
     CHECK(conv2());
@@ -834,7 +815,7 @@ struct BackwardPass {
 
   // join the side stream and run the deferred reductions of this phase in one launch
   int finish() {
-    if (h->pend_scalars && phase != 1 && phase != 4) {   // no launch took the deferred scalar reduction
+    if (h->pend_scalars && phase != 1) {   // no launch took the deferred scalar reduction
       // (phase 1 leaves it pending: conv3's input-gradient launch in phase 2 takes it)
       const ScalarsJob::Args& sa = h->scalars_args;
       ProbeScope ps(h, s, BA3C_K_SCALARS);
@@ -846,20 +827,7 @@ struct BackwardPass {
       HIP_TRY(hipEventRecord(h->ev_join, ws));
       HIP_TRY(hipStreamWaitEvent(s, h->ev_join, 0));
     }
-    const ReduceJobs& jb = h->rjobs;
-    if (jb.n == 0) return BA3C_OK;
-    if (phase == 4) {
-      h->held = true;          // ba3c_launch_held (or the next entry point) launches it
-      h->held_stream = s;
-      h->held_jobs = jb;
-    } else if (h->defer_final && phase == 0) {
-      h->pend_reduce = true;   // the next fused apply runs it (flush_reduce otherwise)
-      h->pend_stream = s;
-      h->pend_grads = grads;
-    } else {
-      return launch_reduce_all(h, s, jb);
-    }
-    return BA3C_OK;
+    return h->rjobs.n ? launch_reduce_all(h, s, h->rjobs) : BA3C_OK;
   }
 
   int conv_reduce(int M, int N, int S, int layer, int cin, int cinpad, const float* part) {
@@ -1406,7 +1374,7 @@ int ba3c_create(const ba3c_config* cfg, ba3c_handle** out) {
   // clip_update_kernel's and clip_range_kernel's tagged partials + error words (no device:
   // stay null, two-launch paths)
   const size_t ubytes = ((size_t)tt.nchunks + 1) * sizeof(unsigned long long);
-  const size_t cbytes = (4 * CHAIN_SITES + 4 + CHAIN_SPREAD * CHAIN_STRIDE + 16) * sizeof(unsigned);
+  const size_t cbytes = (4 * CHAIN_SITES + 4) * sizeof(unsigned);
   if (hipMalloc(reinterpret_cast<void**>(&h->utag), 2 * ubytes + cbytes) != hipSuccess) {
     h->utag = nullptr;
     (void)hipGetLastError();
@@ -1417,8 +1385,6 @@ int ba3c_create(const ba3c_config* cfg, ba3c_handle** out) {
   } else {
     h->ctag = h->utag + tt.nchunks + 1;
     h->chain = reinterpret_cast<unsigned*>(h->ctag + tt.nchunks + 1);
-    const uintptr_t sp = reinterpret_cast<uintptr_t>(h->chain + 4 * CHAIN_SITES + 4);
-    h->spread = reinterpret_cast<unsigned*>((sp + 63) & ~uintptr_t(63));
   }
   *out = h;
   return BA3C_OK;
@@ -1434,7 +1400,6 @@ void ba3c_destroy(ba3c_handle* h) {
   for (auto e : h->ev_fork)
     if (e) (void)hipEventDestroy(e);
   if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-  if (h->ev_pend) (void)hipEventDestroy(h->ev_pend);
   if (h->side) (void)hipStreamDestroy(h->side);
   if (h->utag) (void)hipFree(h->utag);
   delete h;
@@ -1488,9 +1453,6 @@ size_t ba3c_workspace_size(const ba3c_handle* h, int32_t batch, int32_t train) {
   return carve(h, nullptr, batch, train != 0).bytes;
 }
 
-static int flush_reduce(ba3c_handle* h, hipStream_t s);
-static int flush_held(ba3c_handle* h, hipStream_t s, bool order = true);
-
 int ba3c_forward(ba3c_handle* h, void* stream, const float* params, const uint8_t* state,
                  int32_t batch, float explore_factor, void* workspace, float* probs,
                  float* probsT, float* value) {
@@ -1498,8 +1460,6 @@ int ba3c_forward(ba3c_handle* h, void* stream, const float* params, const uint8_
     return fail(BA3C_ERR_INVALID, "null or misaligned pointer");
   if (batch < 1 || batch > h->cfg.max_batch) return fail(BA3C_ERR_INVALID, "batch out of range");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  CHECK(flush_reduce(h, s));
-  CHECK(flush_held(h, s));
   Workspace w = carve(h, workspace, batch, false);
   std::memset(h->merged, 0, sizeof(h->merged));
   const LaunchPlan pl = plan_launches(h->sw, batch, h->cfg.channels, h->cus, false);
@@ -1514,40 +1474,6 @@ static int train_grads_impl(ba3c_handle* h, void* stream, const float* params, c
                             const int64_t* action, const float* futurereward, int32_t batch,
                             float entropy_beta, void* workspace, float* grads, double* scalars,
                             int32_t phase, const PpoArgs* ppo = nullptr);
-
-// launch a reduction a phase-3 pass left pending, on the pass's stream; a call on another
-// stream `s` then waits for it (an event recorded by the caller after the pass predates it)
-static int flush_reduce(ba3c_handle* h, hipStream_t s) {
-  if (!h || !h->pend_reduce) return BA3C_OK;
-  h->pend_reduce = false;
-  CHECK(launch_reduce_all(h, h->pend_stream, h->rjobs));
-  if (s != h->pend_stream) {
-    if (!h->ev_pend) HIP_TRY(hipEventCreateWithFlags(&h->ev_pend, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(h->ev_pend, h->pend_stream));
-    HIP_TRY(hipStreamWaitEvent(s, h->ev_pend, 0));
-  }
-  return BA3C_OK;
-}
-
-// launch the fc1 + heads reduction a phase-4 pass held back, on stream `s`; `order`: after
-// everything enqueued on the pass's stream so far (an event, when the streams differ).
-// ba3c_launch_held leaves the ordering to its caller (the N>1 step orders the exchange stream
-// after the phase-2 event, i.e. after phase 1, not after the whole of phase 2)
-static int flush_held(ba3c_handle* h, hipStream_t s, bool order) {
-  if (!h || !h->held) return BA3C_OK;
-  h->held = false;
-  if (order && s != h->held_stream) {
-    if (!h->ev_pend) HIP_TRY(hipEventCreateWithFlags(&h->ev_pend, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(h->ev_pend, h->held_stream));
-    HIP_TRY(hipStreamWaitEvent(s, h->ev_pend, 0));
-  }
-  return launch_reduce_all(h, s, h->held_jobs);
-}
-
-int ba3c_launch_held(ba3c_handle* h, void* stream) {
-  if (!h) return fail(BA3C_ERR_INVALID, "null handle");
-  return flush_held(h, static_cast<hipStream_t>(stream), false);
-}
 
 int ba3c_set_phase2_event(ba3c_handle* h, void* event) {
   if (!h) return fail(BA3C_ERR_INVALID, "null handle");
@@ -1566,24 +1492,12 @@ int ba3c_train_grads_phase(ba3c_handle* h, void* stream, const float* params, co
                            const int64_t* action, const float* futurereward, int32_t batch,
                            float entropy_beta, void* workspace, float* grads, double* scalars,
                            int32_t phase) {
-  if (phase < 0 || phase > 4) return fail(BA3C_ERR_INVALID, "phase must be 0, 1, 2, 3 or 4");
-  if (phase != 3)
-    return train_grads_impl(h, stream, params, state, action, futurereward, batch, entropy_beta, workspace,
-                            grads, scalars, phase);
-  if (h) h->defer_final = true;
-  const int r = train_grads_impl(h, stream, params, state, action, futurereward, batch, entropy_beta,
-                                 workspace, grads, scalars, 0);
-  if (h) h->defer_final = false;
-  return r;
+  if (phase < 0 || phase > 2) return fail(BA3C_ERR_INVALID, "phase must be 0, 1 or 2");
+  return train_grads_impl(h, stream, params, state, action, futurereward, batch, entropy_beta, workspace,
+                          grads, scalars, phase);
 }
 
 int ba3c_bucket_tensor(const ba3c_handle* h) { return h ? h->idx_fc1 : -1; }
-
-int ba3c_flush_pending(ba3c_handle* h) {
-  if (!h) return fail(BA3C_ERR_INVALID, "null handle");
-  CHECK(flush_reduce(h, h->pend_stream));
-  return flush_held(h, h->held_stream);
-}
 
 static int train_grads_impl(ba3c_handle* h, void* stream, const float* params, const uint8_t* state,
                             const int64_t* action, const float* futurereward, int32_t batch,
@@ -1595,8 +1509,6 @@ static int train_grads_impl(ba3c_handle* h, void* stream, const float* params, c
     return fail(BA3C_ERR_INVALID, "null or misaligned pointer");
   if (batch < 1 || batch > h->cfg.max_batch) return fail(BA3C_ERR_INVALID, "batch out of range");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  CHECK(flush_reduce(h, s));
-  if (phase != 2) CHECK(flush_held(h, s));   // phase 2 runs beside the held reduction
   CHECK(ensure_side_stream(h, s));
   Workspace w = carve(h, workspace, batch, true);
   // no memset of `grads`: the backward pass's single reduction launch writes every element
@@ -1628,35 +1540,21 @@ int ba3c_train_grads_ppo(ba3c_handle* h, void* stream, const float* params, cons
   if (ratio && !check_ptr(ratio)) return fail(BA3C_ERR_INVALID, "ratio must be 16-byte aligned (or null)");
   // written so that a NaN fails it
   if (!(clip_eps > 0.f && clip_eps < 1.f)) return fail(BA3C_ERR_INVALID, "clip_eps must be in (0, 1)");
-  if (phase < 0 || phase > 4) return fail(BA3C_ERR_INVALID, "phase must be 0, 1, 2, 3 or 4");
+  if (phase < 0 || phase > 2) return fail(BA3C_ERR_INVALID, "phase must be 0, 1 or 2");
   const PpoArgs ppo{rows, ratio, clip_eps};
-  if (phase != 3)
-    return train_grads_impl(h, stream, params, state, action, nullptr, batch, entropy_beta, workspace,
-                            grads, scalars, phase, &ppo);
-  if (h) h->defer_final = true;
-  const int r = train_grads_impl(h, stream, params, state, action, nullptr, batch, entropy_beta,
-                                 workspace, grads, scalars, 0, &ppo);
-  if (h) h->defer_final = false;
-  return r;
+  return train_grads_impl(h, stream, params, state, action, nullptr, batch, entropy_beta, workspace,
+                          grads, scalars, phase, &ppo);
 }
 
 int ba3c_clip_grads_range(ba3c_handle* h, void* stream, float* grads, void* workspace, int32_t t0,
                           int32_t t1) {
-  return ba3c_clip_grads_range2(h, stream, grads, workspace, t0, t1, 0);
-}
-
-int ba3c_clip_grads_range2(ba3c_handle* h, void* stream, float* grads, void* workspace, int32_t t0,
-                           int32_t t1, int32_t flags) {
   if (!h || !check_ptr(grads) || !check_ptr(workspace)) return fail(BA3C_ERR_INVALID, "null pointer");
   if (t0 < 0 || t1 > h->table.n || t0 >= t1) return fail(BA3C_ERR_INVALID, "bad tensor range");
-  if (flags & ~BA3C_CLIP_NO_RESIDENCY) return fail(BA3C_ERR_INVALID, "unknown clip flags");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  CHECK(flush_reduce(h, s));
-  if (t1 > h->idx_fc1) CHECK(flush_held(h, s));   // the range holds tensors the held reduction writes
   float* part = carve(h, workspace, 1, false).sumsq;
   const int c0 = h->table.chunk0[t0], nc = h->table.chunk0[t1] - c0;
   ProbeScope ps(h, s, BA3C_K_CLIP);
-  if (h->ctag && h->sw.fused_update && nc <= h->cus && !(flags & BA3C_CLIP_NO_RESIDENCY)) {
+  if (h->ctag && h->sw.fused_update && nc <= h->cus) {
     // one launch (tagged partials), bit-identical to the two below
     const UpdateSync us{h->ctag, reinterpret_cast<unsigned int*>(h->ctag + h->table.nchunks)};
     hipLaunchKernelGGL(clip_range_kernel, dim3(nc), dim3(256), 0, s, grads, h->table, c0, us);
@@ -1671,8 +1569,6 @@ int ba3c_clip_grads_range2(ba3c_handle* h, void* stream, float* grads, void* wor
 int ba3c_clip_grads(ba3c_handle* h, void* stream, float* grads, void* workspace) {
   if (!h || !check_ptr(grads) || !check_ptr(workspace)) return fail(BA3C_ERR_INVALID, "null pointer");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  CHECK(flush_reduce(h, s));
-  CHECK(flush_held(h, s));
   float* part = carve(h, workspace, 1, false).sumsq;  // batch-independent first region
   {
     ProbeScope ps(h, s, BA3C_K_CLIP);
@@ -1693,8 +1589,7 @@ static int apply_update_impl(ba3c_handle* h, void* stream, int32_t opt, float* p
   if ((need0 && !check_ptr(slot0)) || (need1 && !check_ptr(slot1)))
     return fail(BA3C_ERR_INVALID, "missing optimizer slot");
   if (fuse_clip && !check_ptr(workspace)) return fail(BA3C_ERR_INVALID, "fuse_clip needs a workspace");
-  // validated before anything is launched or the pending reduction is consumed (ADVICE r05:
-  // the chained branch below clears pend_reduce, so an unknown id there would drop it)
+  // validated before anything is launched
   if (opt < BA3C_OPT_ADAM || opt > BA3C_OPT_RMS) return fail(BA3C_ERR_INVALID, "unknown optimizer id");
   hipStream_t s = static_cast<hipStream_t>(stream);
   UpdateArgs a{};
@@ -1718,23 +1613,6 @@ static int apply_update_impl(ba3c_handle* h, void* stream, int32_t opt, float* p
   a.beta2 = hp->beta2;
   float* part = carve(h, workspace, 1, false).sumsq;  // batch-independent first region
   const bool fused = fuse_clip && h->sw.fused_update && h->utag && h->table.nchunks <= h->cus;
-  if (RED_G == 4 && fused && h->pend_reduce && h->pend_stream == s && h->pend_grads == grads && chain_ok(h)) {
-    // the pending reduction and this apply as one chained launch: the reduce workgroups
-    // signal, the chunks wait for them before reading their gradient
-    h->pend_reduce = false;
-    const ReduceJobs& jb = h->rjobs;
-    ClipUpdArgs ca{a, h->table, UpdateSync{h->utag, reinterpret_cast<unsigned int*>(h->utag + h->table.nchunks)},
-                   h->spread, CHAIN_SPREAD, (unsigned)jb.blk0[jb.n], h->chain + 4 * CHAIN_SITES};
-    ca.a.clip_part = part;
-    const dim3 gr(jb.blk0[jb.n]), gu(h->table.nchunks);
-    h->merged[BA3C_K_UPDATE] |= 1u << BA3C_K_WGRAD_REDUCE;
-    return with_opt(opt, [&](auto O) {
-      return launch_chain<false, ReduceJob, ClipUpdJob<decltype(O)::value>>(s, CHAIN_REDUCE_UPDATE, 1, 2, 2, jb, gr, ca, gu, 0,
-                                                           dim3(0, 1, 1), h, BA3C_K_UPDATE, true);
-    });
-  }
-  CHECK(flush_reduce(h, s));
-  CHECK(flush_held(h, s));
   if (fused) {
     a.clip_part = part;
     const dim3 grid(h->table.nchunks);
@@ -2041,8 +1919,6 @@ int ba3c_kernel_family(const ba3c_handle* h, int32_t kid) {
 int ba3c_device_errors(ba3c_handle* h, uint32_t* flags) {
   if (!h || !flags) return fail(BA3C_ERR_INVALID, "null argument");
   *flags = 0;
-  CHECK(flush_reduce(h, h->pend_stream));
-  CHECK(flush_held(h, h->held_stream));
   if (!h->utag) return BA3C_OK;
   // every stream, the non-blocking ones torch creates included (a null-stream copy does not
   // wait for those)
@@ -2057,7 +1933,6 @@ int ba3c_device_errors(ba3c_handle* h, uint32_t* flags) {
     // chaining on this handle (the error bit stays set)
     h->sw.chain = false;
     HIP_TRY(hipMemset(h->chain, 0, 4 * CHAIN_SITES * sizeof(unsigned)));
-    HIP_TRY(hipMemset(h->spread, 0, CHAIN_SPREAD * CHAIN_STRIDE * sizeof(unsigned)));
   }
   *flags = e | (e2 << 1) | (e3 << 2);
   return BA3C_OK;
@@ -2117,8 +1992,6 @@ int ba3c_comm_destroy(ba3c_handle* h, int32_t abort) {
 int ba3c_allreduce_sum(ba3c_handle* h, void* stream, float* buf, int64_t count) {
   if (!h || !buf || count < 0) return fail(BA3C_ERR_INVALID, "bad argument");
   if (!h->comm) return fail(BA3C_ERR_INVALID, "no communicator (ba3c_comm_init)");
-  CHECK(flush_reduce(h, static_cast<hipStream_t>(stream)));
-  CHECK(flush_held(h, static_cast<hipStream_t>(stream)));
   const ncclResult_t e = rccl().all_reduce(buf, buf, (size_t)count, ncclFloat32, ncclSum, h->comm,
                                            static_cast<hipStream_t>(stream));
   if (e != ncclSuccess) return rccl_fail(e, "ncclAllReduce");

@@ -478,30 +478,25 @@ struct ReduceMap {
   float* dst_vb;
 };
 
-// a gradient element; COH: an agent-scope store (global_store sc1), for a consumer in the same
-// launch on another XCD (reduce_clip_update: MI355X's L2s are not coherent)
-template <bool COH = false>
-__device__ __forceinline__ void grad_store(float* p, float v) {
-  if constexpr (COH) st_agent_u32(reinterpret_cast<uint32_t*>(p), __float_as_uint(v));
-  else *p = v;
-}
+// a gradient element (a helper of its own: with the stores written out at their sites the
+// compiler schedules the reduction kernels' tails differently)
+__device__ __forceinline__ void grad_store(float* p, float v) { *p = v; }
 
-template <bool COH = false>
 __device__ __forceinline__ void reduce_store(const ReduceMap& mp, int m, int n, float v) {
   if (mp.kind == 0) {
     const int kk = m / mp.cin, c = m - kk * mp.cin;
-    grad_store<COH>(mp.dst + ((size_t)kk * mp.cinpad + c) * mp.N + n, v);
+    grad_store(mp.dst + ((size_t)kk * mp.cinpad + c) * mp.N + n, v);
   } else if (mp.kind == 1) {
     const int s = n / mp.per, fl = n - s * mp.per;
-    grad_store<COH>(mp.dst + (size_t)s * mp.wstride + (size_t)m * mp.per + fl, v);  // m == 1600: legacy bias
+    grad_store(mp.dst + (size_t)s * mp.wstride + (size_t)m * mp.per + fl, v);  // m == 1600: legacy bias
   } else {
     const int F = mp.M - 1;
     if (m < F) {
-      if (n < mp.A) grad_store<COH>(mp.dst + (size_t)m * mp.A + n, v);
-      else if (n == mp.A) grad_store<COH>(mp.dst_vW + m, v);
+      if (n < mp.A) grad_store(mp.dst + (size_t)m * mp.A + n, v);
+      else if (n == mp.A) grad_store(mp.dst_vW + m, v);
     } else {
-      if (n < mp.A) grad_store<COH>(mp.dst_pib + n, v);
-      else if (n == mp.A) grad_store<COH>(mp.dst_vb, v);
+      if (n < mp.A) grad_store(mp.dst_pib + n, v);
+      else if (n == mp.A) grad_store(mp.dst_vb, v);
     }
   }
 }
@@ -573,7 +568,7 @@ __device__ __forceinline__ int reduce_out_size(const ReduceMap& mp) {
 }
 
 // workgroup b of the launch (64 NG threads); `lds`: NG x 64 float4 of scratch
-template <bool COH, int NG>
+template <int NG>
 __device__ __forceinline__ void wgrad_reduce_body(const ReduceJobs& jobs, int b, char* lds) {
   float4 (*red4)[64] = reinterpret_cast<float4 (*)[64]>(lds);
   float (*red)[64] = reinterpret_cast<float (*)[64]>(lds);
@@ -639,14 +634,7 @@ __device__ __forceinline__ void wgrad_reduce_body(const ReduceJobs& jobs, int b,
         const int m = o / mp.N, n = o % mp.N, sidx = n / mp.per, fl = n - sidx * mp.per;
         dst = mp.dst + (size_t)sidx * mp.wstride + (size_t)m * mp.per + fl;
       }
-      if constexpr (COH) {
-        st_agent_u64(reinterpret_cast<unsigned long long*>(dst),
-                     ((unsigned long long)__float_as_uint(v.y) << 32) | __float_as_uint(v.x));
-        st_agent_u64(reinterpret_cast<unsigned long long*>(dst) + 1,
-                     ((unsigned long long)__float_as_uint(v.w) << 32) | __float_as_uint(v.z));
-      } else {
-        *reinterpret_cast<float4*>(dst) = v;
-      }
+      *reinterpret_cast<float4*>(dst) = v;
     }
     return;
   }
@@ -673,14 +661,14 @@ __device__ __forceinline__ void wgrad_reduce_body(const ReduceJobs& jobs, int b,
   __syncthreads();
   if (zg == 0 && o < NO) {
     const float v = red_sum<NG>(red, lane);
-    if (mp.kind == 0) grad_store<COH>(mp.dst + o, po >= 0 ? v : 0.f);   // [(kk * cinpad + c) * N + n] == o
-    else reduce_store<COH>(mp, o / mp.N, o % mp.N, v);
+    if (mp.kind == 0) grad_store(mp.dst + o, po >= 0 ? v : 0.f);   // [(kk * cinpad + c) * N + n] == o
+    else reduce_store(mp, o / mp.N, o % mp.N, v);
   }
 }
 
 __global__ void __launch_bounds__(64 * RED_G) wgrad_reduce_all_kernel(const ReduceJobs jobs) {
   __shared__ float4 red4[RED_G][64];
-  wgrad_reduce_body<false, RED_G>(jobs, blockIdx.x, reinterpret_cast<char*>(red4));
+  wgrad_reduce_body<RED_G>(jobs, blockIdx.x, reinterpret_cast<char*>(red4));
 }
 
 // ---------------------------------------------------------------------------------------
@@ -906,15 +894,11 @@ __device__ __forceinline__ float wait_partials(const UpdateSync& us, int c0, int
   return ss;
 }
 
-// Chunk b of nblk.  With `zsig` (reduce_clip_update: the gradient is being written by the
-// signalling workgroups of the same launch) the chunk loads its parameters and slots, waits
-// until the nctr spread counters at zsig sum to zneed, then reads its gradient with
-// agent-scope loads.  `red`: 4 floats of LDS, `fsh`: 1.
+// Chunk b of nblk.  `red`: 4 floats of LDS, `fsh`: 1.
 template <int OPT>
 __device__ __forceinline__ void clip_update_body(const UpdateArgs& a, const TensorTable& tt,
-                                                 const UpdateSync& us, int b, int nblk,
-                                                 const unsigned* zsig, int nctr, unsigned zneed,
-                                                 unsigned* zerr, float* red, float* fsh_p) {
+                                                 const UpdateSync& us, int b, int nblk, float* red,
+                                                 float* fsh_p) {
   float& fsh = *fsh_p;
   const int lane = threadIdx.x & 63;
   // this launch's generation (issued first: its latency hides behind the data loads)
@@ -933,20 +917,10 @@ __device__ __forceinline__ void clip_update_body(const UpdateArgs& a, const Tens
   for (int j = 0; j < PER; ++j) {
     const int i = beg + threadIdx.x + 256 * j;
     const long long k = o + min(i, end - 1);
-    if (!zsig) gv[j] = a.g[k];
+    gv[j] = a.g[k];
     pv[j] = a.p[k];
     s0v[j] = S0 ? a.s0[k] : 0.f;
     s1v[j] = S1 ? a.s1[k] : 0.f;
-  }
-  if (zsig) {
-    if (threadIdx.x < 64) chain_wait_spread(zsig, nctr, zneed, zerr);
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-      const long long k = o + min(beg + (int)threadIdx.x + 256 * j, end - 1);
-      gv[j] = __uint_as_float(__hip_atomic_load(reinterpret_cast<const unsigned*>(a.g) + k, __ATOMIC_RELAXED,
-                                                __HIP_MEMORY_SCOPE_AGENT));
-    }
   }
 #pragma unroll
   for (int j = 0; j < PER; ++j)
@@ -995,7 +969,7 @@ __global__ void __launch_bounds__(256) clip_update_kernel(const UpdateArgs a, co
                                                           const UpdateSync us) {
   __shared__ float red[4];
   __shared__ float fsh;
-  clip_update_body<OPT>(a, tt, us, blockIdx.x, gridDim.x, nullptr, 0, 0u, nullptr, red, &fsh);
+  clip_update_body<OPT>(a, tt, us, blockIdx.x, gridDim.x, red, &fsh);
 }
 
 // ---------------------------------------------------------------------------------------

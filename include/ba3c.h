@@ -150,24 +150,14 @@ int ba3c_train_grads(ba3c_handle* h, void* stream, const float* params, const ui
  * arguments, same workspace) runs conv3..conv0 and finishes the rest.  Phase 0 = both = the
  * bit-identical ba3c_train_grads.  Between the phases the caller may clip and all-reduce the
  * fc1 + heads bucket while the conv layers run (the reference's per-variable PS pushes,
- * OpenAIGym/train.py:598-606).
- * Phase 3 = phase 0 with the final weight-gradient reduction left pending: the next
- * ba3c_apply_update(_dev) with fuse_clip on the same handle, stream and `grads` runs it and the
- * clip + update as ONE chained launch (a launch fewer per step, but measured 4 us slower at
- * configs[1]: the trainer uses it only with BA3C_DEFER_REDUCE=1); any other entry
- * point on the handle (forward, train, clip, an unfused or mismatched apply, device_errors)
- * first launches it on the pass's stream (a call on another stream then waits for it).  `grads` holds the raw gradients only after that.
- * Phase 4 = phase 1 with the fc1 + heads reduction HELD: nothing launches it until
- * ba3c_launch_held(h, stream) puts it on the caller's stream (after the pass's stream), so the
- * N>1 step can run it, the bucket clip and the bucket's all-reduce on its exchange stream
- * while phase 2 runs; phase 2 does not launch it, every other entry point does (on its own
- * stream, after the pass's). */
+ * OpenAIGym/train.py:598-606).  Any other phase is refused with BA3C_ERR_INVALID before anything
+ * is launched. */
 int ba3c_train_grads_phase(ba3c_handle* h, void* stream, const float* params, const uint8_t* state,
                            const int64_t* action, const float* futurereward, int32_t batch,
                            float entropy_beta, void* workspace, float* grads, double* scalars,
                            int32_t phase);
 /* ba3c_train_grads_phase with the clipped-surrogate (PPO, Schulman et al. 2017) policy term in
- * place of the A3C one; every other launch, the phases 0-4 and their meaning, the scalars and
+ * place of the A3C one; every other launch, the phases 0-2 and their meaning, the scalars and
  * their scaling are ba3c_train_grads_phase's (the heads run in phase 1).
  * rows: fp32 [B][4], row n = {R, V_old, l_old, 0} — the return (the value target, the A3C
  * futurereward), the predictor's value when the action was taken and l_old =
@@ -183,18 +173,12 @@ int ba3c_train_grads_phase(ba3c_handle* h, void* stream, const float* params, co
  * sum_n s * 128 / B; scalars[4] (advantage) stays mean(V - R) with the current V.
  * ratio: fp32 [B] device memory, receives rho per sample; may be NULL.
  * Refused with BA3C_ERR_INVALID before any GPU call: rows NULL or not 16-byte aligned, ratio
- * given but not 16-byte aligned, clip_eps not in (0, 1) (a NaN included), phase outside 0..4,
+ * given but not 16-byte aligned, clip_eps not in (0, 1) (a NaN included), phase outside 0..2,
  * then ba3c_train_grads_phase's own checks. */
 int ba3c_train_grads_ppo(ba3c_handle* h, void* stream, const float* params, const uint8_t* state,
                          const int64_t* action, const float* rows, int32_t batch,
                          float entropy_beta, float clip_eps, void* workspace, float* grads,
                          double* scalars, float* ratio, int32_t phase);
-/* Launch the reduction a phase-4 pass held back, on `stream`; no-op when none is held.  The
- * caller orders `stream` after the phase-4 pass (e.g. by waiting for the ba3c_set_phase2_event
- * event, which follows it); the implicit launches of the other entry points order themselves
- * after everything enqueued on the pass's stream.  Replaces the PS push of the fc1 + heads
- * variables' gradients of OpenAIGym/train.py:598-606 (their aggregation starts from here). */
-int ba3c_launch_held(ba3c_handle* h, void* stream);
 /* Record the HIP event `event` (a hipEvent_t of the caller's, NULL: none) on the pass's stream
  * in every later phase-2 pass, right after conv3's input- and weight-gradient launches (the
  * event only has to follow phase 1): the N>1 step starts the fc1 + heads
@@ -202,22 +186,14 @@ int ba3c_launch_held(ba3c_handle* h, void* stream);
  * conv2's launch (short, non-persistent workgroups the dispatcher rebalances) instead of
  * beside conv3's persistent ones. */
 int ba3c_set_phase2_event(ba3c_handle* h, void* event);
-/* Launch a reduction that a phase-3 pass left pending, on the pass's stream (no-op when none
- * is pending; also launches a held phase-4 reduction).  For callers that read `grads` through another API (a torch view, a gradient
- * summary) between the pass and the fused apply. */
-int ba3c_flush_pending(ba3c_handle* h);
 /* First tensor of the fc1 + heads bucket (tensors before it: the conv layers). */
 int ba3c_bucket_tensor(const ba3c_handle* h);
 
 /* Per-tensor tf.clip_by_average_norm(g, 0.1) in place (n = graph numel incl. padding). */
 int ba3c_clip_grads(ba3c_handle* h, void* stream, float* grads, void* workspace);
-/* The same clip over tensors [t0, t1) only (a bucket). */
-/* ba3c_clip_grads_range with flags: BA3C_CLIP_NO_RESIDENCY makes no co-residency
- * assumption (sum-of-squares + clip launches instead of the one-launch tagged form, whose
- * workgroups wait for each other): for a clip on a stream that runs beside other kernels. */
-#define BA3C_CLIP_NO_RESIDENCY 1
-int ba3c_clip_grads_range2(ba3c_handle* h, void* stream, float* grads, void* workspace, int32_t t0,
-                           int32_t t1, int32_t flags);
+/* The same clip over tensors [t0, t1) only (a bucket): one launch with tagged partials when
+ * the bucket's chunks fit one workgroup per CU (BA3C_FUSED_UPDATE on), else the sum-of-squares
+ * + clip launches; bit-identical. */
 int ba3c_clip_grads_range(ba3c_handle* h, void* stream, float* grads, void* workspace, int32_t t0,
                           int32_t t1);
 

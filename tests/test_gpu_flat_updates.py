@@ -111,14 +111,13 @@ def test_clip_forms_agree_and_match_float64(geom, monkeypatch):
         flat = U.pack(layout, size, g, GRAD_GAP)
         got = {}
         for hi, h in enumerate(handles):
-            for form in ("whole", "ranges", "ranges_no_residency"):
+            for form in ("whole", "ranges"):
                 h.grads.copy_(up(h, flat))
                 if form == "whole":
                     h.clip_grads()
                 else:
-                    nores = form == "ranges_no_residency"
-                    h.clip_grads_range(tb, nt, no_residency=nores)
-                    h.clip_grads_range(0, tb, no_residency=nores)
+                    h.clip_grads_range(tb, nt)
+                    h.clip_grads_range(0, tb)
                 got[(hi, form)] = h.grads.cpu().numpy()
         first = got[(0, "whole")]
         for key, v in got.items():

@@ -25,6 +25,8 @@ GRADS_FAULTS = [
     ("clip nan", {"clip": float("nan")}, b"clip_eps"),
     ("phase -1", {"phase": -1}, b"phase"),
     ("phase 5", {"phase": 5}, b"phase"),
+    ("phase 3", {"phase": 3}, b"phase"),             # the deferred and held reductions are gone:
+    ("phase 4", {"phase": 4}, b"phase"),             # a pass is whole (0) or split in two (1, 2)
     ("null params", {"params": None}, b"pointer"),
     ("state + 8", {"state": "+8"}, b"pointer"),
     ("null action", {"action": None}, b"pointer"),
@@ -122,6 +124,19 @@ def test_a_null_handle_and_a_null_ratio(lib, base):
     assert _grads(lib, None, base) == 1 and b"pointer" in lib.ba3c_last_error()
     # ratio is optional: with none given the call gets as far as the next check
     assert _grads(lib, None, base, ratio=None, phase=9) == 1 and b"phase" in lib.ba3c_last_error()
+
+
+@pytest.mark.parametrize("phase", [-1, 3, 4, 5])
+def test_train_grads_phase_refuses_every_phase_but_0_1_2(lib, handle, base, phase):
+    p = ctypes.c_void_p(base[1])
+    assert lib.ba3c_train_grads_phase(handle, None, p, p, p, p, 4, 0.01, p, p, None, phase) == 1
+    msg = lib.ba3c_last_error()
+    assert b"phase" in msg and b"0, 1 or 2" in msg, msg
+
+
+def test_the_deferred_and_held_entry_points_are_not_exported(lib):
+    for name in ("ba3c_launch_held", "ba3c_flush_pending", "ba3c_clip_grads_range2"):
+        assert not hasattr(lib, name), name
 
 
 def test_an_empty_batch_samples_nothing(lib, handle, base):
