@@ -40,7 +40,9 @@ class Ba3cOptParams(ctypes.Structure):
 _lib = None
 # roofline-accounting queries and the PPO entry points an alternative A/B build (BA3C_LIB) may
 # predate
-AB_OPTIONAL = {"ba3c_kernel_merged", "ba3c_probe_every", "ba3c_train_grads_ppo", "ba3c_sample_logp"}
+AB_OPTIONAL = {"ba3c_kernel_merged", "ba3c_probe_every", "ba3c_train_grads_ppo", "ba3c_sample_logp",
+               "ba3c_train_grads_ppo_ext", "ba3c_ppo_norm_adv"}
+PPO_ADV_FROM_ROW = 1       # BA3C_PPO_ADV_FROM_ROW
 
 
 def load():
@@ -75,6 +77,9 @@ def load():
         "ba3c_clip_grads_range": (i32, [P, P, P, P, i32, i32]),
         "ba3c_train_grads_phase": (i32, [P, P, P, P, P, P, i32, f32, P, P, P, i32]),
         "ba3c_train_grads_ppo": (i32, [P, P, P, P, P, P, i32, f32, f32, P, P, P, P, i32]),
+        "ba3c_train_grads_ppo_ext": (i32, [P, P, P, P, P, P, i32, f32, f32, f32, ctypes.c_uint32, P, P,
+                                           P, P, i32]),
+        "ba3c_ppo_norm_adv": (i32, [P, P, i32, P]),
         "ba3c_sample_logp": (i32, [P, P, P, P, i32, i32, P, P, P]),
         "ba3c_bucket_tensor": (i32, [P]),
         "ba3c_set_phase2_event": (i32, [P, P]),

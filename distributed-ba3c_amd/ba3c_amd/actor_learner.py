@@ -74,6 +74,13 @@ class ActorLearner(object):
         BatchQueue, trains every minibatch the pool yields with the clipped-surrogate loss and
         keeps the last step's per-sample ratio on the device (last_ratio).  stop_at (an attribute, None: off) ends a pool early once the trainer's
         global_step reaches it.
+        The setting's norm_adv normalises each gathered minibatch's advantages on the device
+        before its step (the pool's own rows keep 0 in column 3) and keeps the batch's {mean, std}
+        on the device (last_adv_stats); vclip > 0 is the clipped value loss; target_kl > 0 reads
+        the mean of ppo.stop_kl (mean((rho - 1) - log rho)) over an epoch's minibatches once per
+        epoch — the only host synchronisation it adds — and abandons the pool's remaining epochs
+        when ppo.should_stop says so.  pool_epochs lists, per pool left, the epochs it ran
+        (steps / minibatches), epoch_kls every epoch mean that was read.
         local_time_max, gamma, gae_lambda: the rollout length, discount and GAE lambda of the
         RolloutBuffer's returns (--local_time_max, --gamma, --gae_lambda; the defaults are the
         reference's 5-step, 0.99, n-step recipe).
@@ -102,6 +109,10 @@ class ActorLearner(object):
         self.pool = None if ppo is None else ppo_rules.Pool(
             batch_size, minibatches=ppo.minibatches, epochs=ppo.epochs, seed=seed)
         self.last_ratio = None
+        self.last_adv_stats = None
+        self._adv_stats = None
+        self.pool_epochs = []
+        self.epoch_kls = []               # every epoch mean read for the KL stop, in order
         self.stop_at = None
         self.rs = rs if rs is not None else np.random.RandomState(seed)
         self.hist.push(self.env.frames(), torch.ones(n_envs, dtype=torch.bool, device=eng.device))
@@ -153,12 +164,30 @@ class ActorLearner(object):
             batches = self.pool.get()
             if batches is None:
                 break
+            M, kl, ran = self.pool.M, None, 0
             for st, ac, rows in batches:
                 if self.stop_at is not None and self.trainer.global_step >= self.stop_at:
                     break
-                self.trainer.train_step(st, ac, None, rows=rows, clip=clip)
+                if self.ppo.norm_adv:
+                    if self._adv_stats is None:
+                        self._adv_stats = torch.zeros(2, dtype=torch.float64, device=eng.device)
+                    eng.ppo_norm_adv(rows, self._adv_stats)       # the gathered copy, in place
+                    self.last_adv_stats = self._adv_stats
+                self.trainer.train_step(st, ac, None, rows=rows, clip=clip, vclip=self.ppo.vclip,
+                                        adv_from_row=self.ppo.norm_adv)
                 self.last_ratio = self.trainer.model.ratio
                 self._after_step()
+                ran += 1
+                if self.ppo.target_kl > 0:
+                    rho = self.last_ratio.double()
+                    step_kl = ((rho - 1.0) - torch.log(rho)).mean()      # ppo.stop_kl, on the device
+                    kl = step_kl if kl is None else kl + step_kl
+                    if ran % M == 0:                              # an epoch's end: the one host read
+                        self.epoch_kls.append(float((kl / M).item()))
+                        if ppo_rules.should_stop(self.epoch_kls[-1], self.ppo.target_kl):
+                            break
+                        kl = None
+            self.pool_epochs.append(ran / float(M))
         self.steps += 1
         if int(flag.item()) & 1:
             raise AssertionError("non-finite action distribution (train.py:381)")

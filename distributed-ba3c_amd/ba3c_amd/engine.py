@@ -175,12 +175,26 @@ class Ba3cEngine(object):
                                                    _ptr(grads), _ptr(self.scalars), int(phase)))
         return self.scalars
 
+    def ppo_norm_adv(self, rows, stats=None):
+        """Per-minibatch advantage normalisation in place (ba3c_ppo_norm_adv, ba3c_amd.ppo): writes
+        column 3 of the float32 rows [n, 4]; stats (a float64 device tensor of >= 2 elements, or
+        None) receives the batch's {mean, std}.  Returns rows."""
+        assert rows.dtype == torch.float32 and rows.dim() == 2 and rows.shape[1] == 4 \
+            and rows.is_cuda and rows.is_contiguous()
+        assert stats is None or (stats.dtype == torch.float64 and stats.numel() >= 2
+                                 and stats.is_cuda and stats.is_contiguous())
+        _lib.check(self.lib.ba3c_ppo_norm_adv(_stream(), _ptr(rows), int(rows.shape[0]),
+                                              _ptr(stats)))
+        return rows
+
     def train_grads_ppo(self, state, action, rows, clip_eps, entropy_beta=0.01, grads=None,
-                        phase=0, ratio=True):
+                        phase=0, ratio=True, vclip=0.0, adv_from_row=False):
         """train_grads with the clipped-surrogate policy term (ba3c_train_grads_ppo, ba3c_amd.ppo):
         rows float32 [B, 4] = {R, V_old, l_old, 0}; the phases are train_grads'.  ratio: True
         writes each sample's rho into self.ratio[:B] (a tensor: into it; None / False: not
-        stored).  Returns the scalars tensor."""
+        stored).  vclip > 0: the clipped value loss; adv_from_row: the advantage is rows[:, 3]
+        (ppo_norm_adv) — either one takes ba3c_train_grads_ppo_ext, neither the call as it was.
+        Returns the scalars tensor."""
         B = self._check_state(state)
         assert action.dtype == torch.int64 and action.shape == (B,) and action.is_cuda
         assert rows.dtype == torch.float32 and rows.shape == (B, 4) and rows.is_cuda \
@@ -193,6 +207,13 @@ class Ba3cEngine(object):
         elif ratio is False:
             ratio = None
         assert ratio is None or (ratio.dtype == torch.float32 and ratio.numel() >= B)
+        if vclip or adv_from_row:
+            _lib.check(self.lib.ba3c_train_grads_ppo_ext(
+                self.h, _stream(), _ptr(self.params), _ptr(state), _ptr(action.contiguous()),
+                _ptr(rows), B, float(entropy_beta), float(clip_eps), float(vclip),
+                _lib.PPO_ADV_FROM_ROW if adv_from_row else 0, _ptr(self._workspace(True)),
+                _ptr(grads), _ptr(self.scalars), _ptr(ratio), int(phase)))
+            return self.scalars
         _lib.check(self.lib.ba3c_train_grads_ppo(self.h, _stream(), _ptr(self.params), _ptr(state),
                                                  _ptr(action.contiguous()), _ptr(rows), B,
                                                  float(entropy_beta), float(clip_eps),

@@ -113,6 +113,14 @@ def build_parser():
     p.add_argument("--ppo_minibatches", type=int, default=None,
                    help="minibatches of --batch_size datapoints per pool (default %d); needs "
                         "--ppo_clip" % ppo.DEFAULT_MINIBATCHES)
+    p.add_argument("--ppo_norm_adv", action="store_true",
+                   help="normalise each minibatch's advantages to mean 0, std 1 before its step; "
+                        "needs --ppo_clip")
+    p.add_argument("--ppo_vclip", type=float, default=0.0,
+                   help="eps of the clipped value loss, >= 0; 0: off; needs --ppo_clip")
+    p.add_argument("--ppo_target_kl", type=float, default=0.0,
+                   help="abandon a pool's remaining epochs once an epoch's mean KL estimate "
+                        "(ppo.stop_kl) exceeds this, >= 0; 0: off; needs --ppo_clip (single replica)")
     p.add_argument("--dummy", type=int, default=0)
     p.add_argument("--dummy_predictor", type=int, default=0)
     p.add_argument("--models_dir", default="models")
@@ -147,8 +155,9 @@ def resolve(args, duel_tool=False):
     they imply at most 16 GiB; they apply to every -e, with and without --self_play.
     --ppo_clip in [0, 1) (0: off); --ppo_epochs / --ppo_minibatches >= 1 and only with
     --ppo_clip > 0 (default 4 each); the pool's --ppo_minibatches x --batch_size states at most
-    16 GiB; not with --dummy (no simulators, nothing to replay).  args.ppo is the run's
-    ppo.Setting, or None when off; it applies to every -e and to --self_play."""
+    16 GiB; not with --dummy (no simulators, nothing to replay).  --ppo_norm_adv, --ppo_vclip
+    (>= 0 and finite, 0: off) and --ppo_target_kl (the same) only with --ppo_clip > 0.  args.ppo
+    is the run's ppo.Setting, or None when off; it applies to every -e and to --self_play."""
     if args.replace_with_conv is None:
         args.replace_with_conv = not args.use_normal_fc
     if args.adam_debug:
@@ -213,6 +222,15 @@ def resolve(args, duel_tool=False):
             raise SystemExit("--%s needs --ppo_clip > 0" % name)
         if v is not None and v < 1:
             raise SystemExit("--%s %d: must be >= 1" % (name, v))
+    # written so that a NaN or an infinity fails
+    for name in ("ppo_vclip", "ppo_target_kl"):
+        v = getattr(args, name)
+        if not 0.0 <= v < float("inf"):
+            raise SystemExit("--%s %r: must be >= 0 and finite (0: off)" % (name, v))
+        if v > 0.0 and not on:
+            raise SystemExit("--%s needs --ppo_clip > 0" % name)
+    if args.ppo_norm_adv and not on:
+        raise SystemExit("--ppo_norm_adv needs --ppo_clip > 0")
     args.ppo = None
     if on:
         if args.dummy:
@@ -223,5 +241,7 @@ def resolve(args, duel_tool=False):
         if pool > MAX_RING_BYTES:
             raise SystemExit("--ppo_minibatches %d x --batch_size %d: the pool's states would take "
                              "%.1f GiB (limit 16 GiB)" % (M, args.batch_size, pool / 2.0 ** 30))
-        args.ppo = ppo.Setting(clip=args.ppo_clip, epochs=K, minibatches=M)
+        args.ppo = ppo.Setting(clip=args.ppo_clip, epochs=K, minibatches=M,
+                               norm_adv=bool(args.ppo_norm_adv), vclip=args.ppo_vclip,
+                               target_kl=args.ppo_target_kl)
     return args

@@ -42,8 +42,8 @@ class Model(ModelDesc):
         self.explore_factor = 1.0     # non-trainable var 'explore_factor' (train.py:294-295)
         self.vars_for_save = {n: n for n in self.engine.tensor_names}
         self.cost = None
-        # (rows, clip) of a clipped-surrogate step (Ba3cTrainer.train_step sets it for the
-        # step's passes); None: the A3C loss
+        # (rows, clip, vclip, adv_from_row) of a clipped-surrogate step (Ba3cTrainer.train_step
+        # sets it for the step's passes); None: the A3C loss
         self.ppo = None
         self.ratio = None             # the last PPO pass's per-sample rho (device, [B])
 
@@ -68,9 +68,10 @@ class Model(ModelDesc):
         # (Ba3cTrainer's bucketed data-parallel step); 0: the whole pass
         phase = getattr(self, "train_phase", 0)
         if self.ppo is not None:
-            rows, clip = self.ppo
+            rows, clip, vclip, adv_from_row = self.ppo
             sc = self.engine.train_grads_ppo(state, action, rows, clip,
-                                             entropy_beta=self.entropy_beta, phase=phase)
+                                             entropy_beta=self.entropy_beta, phase=phase,
+                                             vclip=vclip, adv_from_row=adv_from_row)
             self.ratio = self.engine.ratio[:state.shape[0]]
         else:
             sc = self.engine.train_grads(state, action, futurereward,

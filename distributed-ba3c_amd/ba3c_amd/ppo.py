@@ -23,7 +23,43 @@ gradient in closed form:
     dV      = (V - R) / B
 
 which is the A3C gradient with its advantage factor V - R replaced by c: at rho = 1 and
-V_old = V they are equal.  No value clipping, no advantage normalisation.
+V_old = V they are equal.
+
+Three further pieces, each off by default (ba3c_train_grads_ppo_ext, ba3c_ppo_norm_adv and the
+learner's loop; baselines ppo2, CleanRL, SB3 and Spinning Up carry the same three):
+
+Advantage normalisation, per minibatch (normalise_adv_numpy).  Over the B rows of one step
+
+    mean = sum_n Adv / B,   std = sqrt(sum_n (Adv - mean)^2 / B)      (population form, two passes)
+    A_n  = float32((Adv_n - mean) / (std + 1e-8))                     (B = 1 gives 0)
+
+is written into the rows' fourth float, and a step told to take its advantage from the row
+(`adv`, `adv_from_row`) uses A_n wherever the policy term has Adv; R and V_old keep their other
+uses.
+
+The clipped value loss (`vclip` > 0).  With d = V - V_old:
+
+    outside     = |d| > vclip
+    Vc          = outside ? V_old + sign(d) * vclip : V               (V exactly when inside)
+    use_clipped = outside and (Vc - R)^2 > (V - R)^2                  # a tie takes the unclipped branch
+    value term  = 1/2 sum_n (use_clipped ? (Vc - R)^2 : (V - R)^2)    = 1/2 sum_n max of the two
+    dV          = use_clipped ? 0 : (V - R) / B
+
+Term 2 of the kernel's per-sample terms and the value_loss scalar take the selected square; term 3
+(and the advantage scalar) stays V - R.
+
+The KL stop (should_stop, stop_kl).  The learner accumulates, over an epoch's minibatches, the
+mean of
+
+    stop_kl = mean_n((rho - 1) - log rho)
+
+and with a target_kl > 0 a pool's remaining epochs are abandoned once that epoch mean is not
+<= target_kl (a non-finite mean stops too).  (rho - 1) - log rho is the sample estimate of
+KL(pi_old || pi) that is >= 0 for every sample and 0 only at rho = 1 (Schulman, "Approximating KL
+divergence", k3; CleanRL's and SB3's stop use it).  mean(-log rho) — approx_kl, the
+ppo_approx_kl channel, which stays as it is — has the same expectation but either sign on a
+minibatch: on GridBoxing at B = 8 it was negative in 23 of 33 epochs, some at -1.7e-2, and a stop
+on it never fired in those.
 """
 import collections
 
@@ -33,7 +69,9 @@ LOG_EPS = 1e-6            # train.py:305
 MONITOR_SCALE = 128.0     # train.py:311
 
 # An ActorLearner's PPO setting (--ppo_clip / --ppo_epochs / --ppo_minibatches)
-Setting = collections.namedtuple("Setting", ["clip", "epochs", "minibatches"])
+# and its optional pieces (--ppo_norm_adv / --ppo_vclip / --ppo_target_kl), off by default
+Setting = collections.namedtuple("Setting", ["clip", "epochs", "minibatches", "norm_adv", "vclip",
+                                             "target_kl"], defaults=(False, 0.0, 0.0))
 DEFAULT_EPOCHS = 4
 DEFAULT_MINIBATCHES = 4
 
@@ -52,11 +90,35 @@ def make_rows(R, v_old, l_old):
     return rows
 
 
-def heads_numpy(z, V, action, R, v_old, l_old, eps, beta=0.01):
+def normalise_adv_numpy(rows):
+    """(rows_out, mean, std): a copy of the float32 rows [B, 4] whose column 3 holds the
+    normalised advantage float32((Adv - mean) / (std + 1e-8)), Adv = float64(R) - float64(V_old),
+    with the batch's mean and population std (two passes, float64).  Columns 0-2 are untouched."""
+    rows = np.asarray(rows, dtype=np.float32)
+    B = rows.shape[0]
+    adv = rows[:, 0].astype(np.float64) - rows[:, 1].astype(np.float64)
+    mean = adv.sum() / B
+    std = np.sqrt(((adv - mean) ** 2).sum() / B)
+    out = rows.copy()
+    out[:, 3] = ((adv - mean) / (std + 1e-8)).astype(np.float32)
+    return out, float(mean), float(std)
+
+
+def should_stop(epoch_kl, target_kl):
+    """Whether a pool's remaining epochs are abandoned: never with target_kl == 0, else unless
+    epoch_kl <= target_kl (so a NaN or an infinite KL stops)."""
+    if target_kl == 0:
+        return False
+    return not (epoch_kl <= target_kl)
+
+
+def heads_numpy(z, V, action, R, v_old, l_old, eps, beta=0.01, vclip=0.0, adv=None):
     """The loss and its closed-form gradient from the policy pre-activations z [B, A] and the
     current values V [B].  Returns a dict: cost, dz [B, A], dV [B], rho, active, c, s, the
     kernel's per-sample terms [B, 6] = {s, sum_k p lp, (V-R)^2, V - R, V, max p} and the eight
-    step scalars in _lib.SCALAR_NAMES order without active_relus (scalars [7])."""
+    step scalars in _lib.SCALAR_NAMES order without active_relus (scalars [7]).
+    adv [B]: replaces R - V_old in the policy term; vclip > 0: the clipped value loss (term 2,
+    value_loss and dV, as the module states); use_clipped [B] says where."""
     z = np.asarray(z, dtype=np.float64)
     V, R = np.asarray(V, dtype=np.float64), np.asarray(R, dtype=np.float64)
     v_old, l_old = np.asarray(v_old, dtype=np.float64), np.asarray(l_old, dtype=np.float64)
@@ -68,7 +130,7 @@ def heads_numpy(z, V, action, R, v_old, l_old, eps, beta=0.01):
     lp = np.log(pe)
     ar = np.arange(B)
     lpa = lp[ar, action]
-    Adv = R - v_old
+    Adv = R - v_old if adv is None else np.asarray(adv, dtype=np.float64)
     rho = np.exp(lpa - l_old)
     su = rho * Adv
     sc = np.clip(rho, 1.0 - eps, 1.0 + eps) * Adv
@@ -80,24 +142,36 @@ def heads_numpy(z, V, action, R, v_old, l_old, eps, beta=0.01):
     gp = (c[:, None] * onehot / pe + beta * (lp + p / pe)) / B
     dz = p * (gp - (gp * p).sum(axis=1, keepdims=True))
     dV = (V - R) / B
+    vsq = (V - R) ** 2
+    use_clipped = np.zeros(B, dtype=bool)
+    vclip = float(vclip)
+    if vclip > 0.0:
+        d = V - v_old
+        outside = np.abs(d) > vclip
+        Vc = np.where(outside, v_old + np.sign(d) * vclip, V)
+        use_clipped = outside & ((Vc - R) ** 2 > vsq)
+        vsq = np.where(use_clipped, (Vc - R) ** 2, vsq)
+        dV = np.where(use_clipped, 0.0, dV)
     xent = (p * lp).sum(axis=1)
-    terms = np.stack([s, xent, (V - R) ** 2, V - R, V, p.max(axis=1)], axis=1)
-    pl, xe, vl = s.sum(), xent.sum(), 0.5 * ((V - R) ** 2).sum()
+    terms = np.stack([s, xent, vsq, V - R, V, p.max(axis=1)], axis=1)
+    pl, xe, vl = s.sum(), xent.sum(), 0.5 * vsq.sum()
     cost = (pl + beta * xe + vl) / B
     scalars = np.array([cost, pl * MONITOR_SCALE / B, xe * MONITOR_SCALE / B * beta,
                         vl * MONITOR_SCALE / B, (V - R).mean(), V.mean(), p.max()])
     return dict(cost=cost, dz=dz, dV=dV, rho=rho, active=active, c=c, s=s, terms=terms,
-                scalars=scalars, p=p, lp=lp)
+                scalars=scalars, p=p, lp=lp, use_clipped=use_clipped)
 
 
-def heads_from_h(h, params, action, rows, eps, beta=0.01):
+def heads_from_h(h, params, action, rows, eps, beta=0.01, vclip=0.0, adv_from_row=False):
     """heads_numpy on an FC output h [B, F] and the head weights of a {name: array} dict, with the
-    kernel's rows [B, 4]; adds dh = dz W_pi^T + dV W_v^T (before any legacy ReLU mask)."""
+    kernel's rows [B, 4]; adds dh = dz W_pi^T + dV W_v^T (before any legacy ReLU mask).
+    adv_from_row: the policy term's advantage is rows[:, 3]."""
     f8 = lambda x: np.asarray(x, dtype=np.float64)
     h, rows = f8(h), f8(rows)
     z = h @ f8(params["fc-pi/W"]) + f8(params["fc-pi/b"])
     V = (h @ f8(params["fc-v/W"]) + f8(params["fc-v/b"]))[:, 0]
-    out = heads_numpy(z, V, action, rows[:, 0], rows[:, 1], rows[:, 2], eps, beta)
+    out = heads_numpy(z, V, action, rows[:, 0], rows[:, 1], rows[:, 2], eps, beta, vclip,
+                      rows[:, 3] if adv_from_row else None)
     out["dh"] = out["dz"] @ f8(params["fc-pi/W"]).T + out["dV"][:, None] @ f8(params["fc-v/W"]).T
     out["V"] = V
     return out
@@ -111,6 +185,12 @@ def clip_fraction(rho, eps):
 def approx_kl(rho):
     """mean(-log rho): the sample estimate of KL(pi_old || pi)."""
     return float(np.mean(-np.log(np.asarray(rho, dtype=np.float64))))
+
+
+def stop_kl(rho):
+    """mean((rho - 1) - log rho): the KL stop's estimate of KL(pi_old || pi), >= 0 per sample."""
+    rho = np.asarray(rho, dtype=np.float64)
+    return float(np.mean((rho - 1.0) - np.log(rho)))
 
 
 def device_gather(src, idx):

@@ -66,6 +66,9 @@ def check_distributed(args, world):
     if args.use_sync and not 1 <= args.ngrads <= world:
         raise SystemExit("--ngrads %d must be in [1, %d] (the number of GPU processes)"
                          % (args.ngrads, world))
+    if world > 1 and args.ppo is not None and args.ppo.target_kl > 0:
+        raise SystemExit("--ppo_target_kl with world size %d: replicas that stop at different "
+                         "epochs would leave the all-reduce unmatched; it is single-replica" % world)
 
 
 def build(args, rank=0, world=1, device=None):
@@ -103,10 +106,18 @@ class _Metrics(object):
     def __init__(self, trainer, batch_size, every, client, ppo_clip=None):
         """ppo_clip (eps, None: off): each PPO step's per-sample ratio is kept on the device too, and
         every flush writes two more channels from them: ppo_clip_fraction = mean(|rho - 1| > eps)
-        and ppo_approx_kl = mean(-log rho) over the flushed steps."""
+        and ppo_approx_kl = mean(-log rho) over the flushed steps.  With a `learner` attached
+        (an ActorLearner) whose setting normalises advantages, each step's device-held
+        {mean, std} is kept as well and a flush writes their means over the flushed steps as
+        ppo_adv_mean / ppo_adv_std; with a target KL it writes ppo_epochs_run, the mean epochs
+        per pool over the pools left since the last flush."""
         from .metrics import DebugLogCallback
         self.ppo_clip, self.client = ppo_clip, client
         self.ratios = []
+        self.adv_stats = []
+        self.learner = None
+        self.pools_seen = 0
+        self.epochs_run = None
         self.last_ppo = None
         self.trainer, self.B = trainer, batch_size
         self.every = max(1, int(every))
@@ -119,10 +130,25 @@ class _Metrics(object):
         self.pending.append(trainer.model.scalars.clone())
         if self.ppo_clip is not None and trainer.model.ratio is not None:
             self.ratios.append(trainer.model.ratio.clone())
+            if self.learner is not None and self.learner.last_adv_stats is not None:
+                self.adv_stats.append(self.learner.last_adv_stats.clone())
         if len(self.pending) >= self.every:
             self.flush()
 
+    def _flush_epochs(self):
+        # a pool is left after its last step's callback, so this runs with nothing pending too
+        al = self.learner
+        if al is None or not al.ppo.target_kl > 0 or len(al.pool_epochs) == self.pools_seen:
+            return
+        self.epochs_run = float(np.mean(al.pool_epochs[self.pools_seen:]))
+        self.pools_seen = len(al.pool_epochs)
+        if self.last_ppo is not None:
+            self.last_ppo["ppo_epochs_run"] = self.epochs_run
+        if self.client is not None:
+            self.client.write_scalar("ppo_epochs_run", self.epochs_run)
+
     def flush(self):
+        self._flush_epochs()
         if not self.pending:
             return
         from ._lib import SCALAR_NAMES
@@ -142,9 +168,16 @@ class _Metrics(object):
             self.ratios = []
             self.last_ppo = {"ppo_clip_fraction": ppo.clip_fraction(rho, self.ppo_clip),
                              "ppo_approx_kl": ppo.approx_kl(rho)}
+            if self.adv_stats:
+                m = torch.stack(self.adv_stats).cpu().numpy().mean(axis=0)
+                self.adv_stats = []
+                self.last_ppo.update(ppo_adv_mean=float(m[0]), ppo_adv_std=float(m[1]))
+            if self.epochs_run is not None:
+                self.last_ppo["ppo_epochs_run"] = self.epochs_run
             if self.client is not None:
                 for name, v in self.last_ppo.items():
-                    self.client.write_scalar(name, v)
+                    if name != "ppo_epochs_run":                  # written where it is taken
+                        self.client.write_scalar(name, v)
         self.t0 = time.time()
 
 
@@ -223,6 +256,7 @@ def _run(args, rank, world):
                           local_time_max=args.local_time_max, gamma=args.gamma,
                           gae_lambda=args.gae_lambda, ppo=args.ppo)
         al.stop_at = max_steps if args.ppo is not None else None
+        metrics.learner = al if args.ppo is not None else None
         while trainer.global_step < max_steps:
             al.iterate()
         sim_steps = al.steps

@@ -118,19 +118,23 @@ class Ba3cTrainer(object):
             raise RuntimeError("device error flags 0x%x after global step %d: %s"
                                % (f, self.global_step, self.describe_device_errors(f)))
 
-    def train_step(self, state, action, futurereward, rows=None, clip=None):
+    def train_step(self, state, action, futurereward, rows=None, clip=None, vclip=0.0,
+                   adv_from_row=False):
         """Device-side step (used by bench.py).  No host synchronisation, except with backup
         workers (SyncReplicasOptimizer with replicas_to_aggregate < world): each step then
         synchronises the stream and all-gathers the ranks' ready times on the host before a
         flat (not bucketed) all-reduce, so its step times are not comparable with k = N.
         rows (float32 [B, 4] = {R, V_old, l_old, 0}) with clip (eps): the same step, through the
         same phases, with the clipped-surrogate loss (ba3c_amd.ppo); futurereward is then unused
-        (rows carries R) and may be None."""
+        (rows carries R) and may be None.  vclip (> 0: the clipped value loss) and adv_from_row
+        (the advantage is rows[:, 3]) are PPO steps' too and go through every phase with them."""
         if (rows is None) != (clip is None):
             raise ValueError("a PPO step takes rows and clip together")
+        if rows is None and (vclip or adv_from_row):
+            raise ValueError("vclip and adv_from_row belong to a PPO step (rows and clip)")
         if rows is None:
             return self._train_step(state, action, futurereward)
-        self.model.ppo = (rows, float(clip))
+        self.model.ppo = (rows, float(clip), float(vclip), bool(adv_from_row))
         try:
             return self._train_step(state, action, futurereward)
         finally:

@@ -1057,6 +1057,10 @@ struct PpoArgs {
   const float* rows;   // [B][4] {R, V_old, l_old, 0}
   float* ratio;        // [B] or null
   float clip_eps;
+  // ba3c_train_grads_ppo_ext: the LOSS_PPO_EXT heads (at vclip_eps = 0, flags = 0 too)
+  bool ext = false;
+  float vclip_eps = 0.f;
+  unsigned flags = 0;
 };
 
 // the heads instantiation of (F, A) for one loss: features per lane unrolled (heads_sample),
@@ -1079,11 +1083,13 @@ int run_heads(ba3c_handle* h, hipStream_t s, const float* prm, const Workspace& 
               const int64_t* action, const float* R, float beta, float explore, bool train,
               float* probs, float* probsT, float* value, double* scalars = nullptr,
               bool defer_scalars = false, const PpoArgs* ppo = nullptr) {
-  HeadsArgsPpo a{};
+  HeadsArgsPpoExt a{};
   if (ppo) {
     a.rows = reinterpret_cast<const float4*>(ppo->rows);
     a.ratio = ppo->ratio;
     a.clip_eps = ppo->clip_eps;
+    a.vclip_eps = ppo->vclip_eps;
+    a.flags = ppo->flags;
   }
   a.fcpart = w.fcpart;
   a.fc_split = FC_SPLIT;
@@ -1120,7 +1126,8 @@ int run_heads(ba3c_handle* h, hipStream_t s, const float* prm, const Workspace& 
   a.invB = 1.0f / (float)B;
   {
     ProbeScope ps(h, s, BA3C_K_HEADS);
-    if (ppo && train) launch_heads<LOSS_PPO>(s, B, a);
+    if (ppo && train && ppo->ext) launch_heads<LOSS_PPO_EXT>(s, B, a);
+    else if (ppo && train) launch_heads<LOSS_PPO>(s, B, a);
     else launch_heads<LOSS_A3C>(s, B, a);
   }
   HIP_TRY(hipGetLastError());
@@ -1544,6 +1551,35 @@ int ba3c_train_grads_ppo(ba3c_handle* h, void* stream, const float* params, cons
   const PpoArgs ppo{rows, ratio, clip_eps};
   return train_grads_impl(h, stream, params, state, action, nullptr, batch, entropy_beta, workspace,
                           grads, scalars, phase, &ppo);
+}
+
+int ba3c_train_grads_ppo_ext(ba3c_handle* h, void* stream, const float* params, const uint8_t* state,
+                             const int64_t* action, const float* rows, int32_t batch,
+                             float entropy_beta, float clip_eps, float vclip_eps, uint32_t flags,
+                             void* workspace, float* grads, double* scalars, float* ratio,
+                             int32_t phase) {
+  if (!check_ptr(rows)) return fail(BA3C_ERR_INVALID, "rows must be non-null and 16-byte aligned");
+  if (ratio && !check_ptr(ratio)) return fail(BA3C_ERR_INVALID, "ratio must be 16-byte aligned (or null)");
+  // written so that a NaN fails them
+  if (!(clip_eps > 0.f && clip_eps < 1.f)) return fail(BA3C_ERR_INVALID, "clip_eps must be in (0, 1)");
+  if (!(vclip_eps >= 0.f && std::isfinite(vclip_eps)))
+    return fail(BA3C_ERR_INVALID, "vclip_eps must be finite and >= 0 (0: no value clipping)");
+  if (flags & ~BA3C_PPO_ADV_FROM_ROW) return fail(BA3C_ERR_INVALID, "unknown flags bits");
+  if (phase < 0 || phase > 2) return fail(BA3C_ERR_INVALID, "phase must be 0, 1 or 2");
+  static_assert(BA3C_PPO_ADV_FROM_ROW == PPO_ADV_FROM_ROW, "the header's bit is the kernel's");
+  const PpoArgs ppo{rows, ratio, clip_eps, true, vclip_eps, flags};
+  return train_grads_impl(h, stream, params, state, action, nullptr, batch, entropy_beta, workspace,
+                          grads, scalars, phase, &ppo);
+}
+
+int ba3c_ppo_norm_adv(void* stream, float* rows, int32_t n, double* stats) {
+  if (!check_ptr(rows)) return fail(BA3C_ERR_INVALID, "rows must be non-null and 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(stats) & 7) return fail(BA3C_ERR_INVALID, "stats must be 8-byte aligned (or null)");
+  if (n < 1) return fail(BA3C_ERR_INVALID, "bad count: n must be >= 1");
+  hipLaunchKernelGGL(ppo_norm_adv_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     reinterpret_cast<float4*>(rows), n, stats);
+  HIP_TRY(hipGetLastError());
+  return BA3C_OK;
 }
 
 int ba3c_clip_grads_range(ba3c_handle* h, void* stream, float* grads, void* workspace, int32_t t0,

@@ -43,8 +43,15 @@ __device__ __forceinline__ unsigned long long ld_agent(const unsigned long long*
 // and dL/dp is the A3C one with `adv` replaced by `c`; terms[n][0] = s, the entropy and value
 // terms and terms 1-5 are the A3C ones (term 3 stays V - R with the current V).  At rho = 1
 // and V_old = V this is the A3C gradient.
+//
+// LOSS_PPO_EXT: LOSS_PPO with two more choices, each uniform over the launch (ppo.py states them):
+//   flags bit 0: Adv = rows[n].w (a normalised advantage, ba3c_ppo_norm_adv) instead of R - V_old;
+//   vclip_eps > 0: the clipped value loss.  d = V - V_old, Vc = V_old + sign(d) vclip_eps,
+//     use_clipped = |d| > vclip_eps and (Vc - R)^2 > (V - R)^2   (a tie is unclipped);
+//     terms[n][2] = use_clipped ? (Vc - R)^2 : (V - R)^2,  dV = use_clipped ? 0 : (V - R) / B.
+// With vclip_eps = 0 and flags = 0 every stored value is LOSS_PPO's, bit for bit.
 // ---------------------------------------------------------------------------------------
-constexpr int LOSS_A3C = 0, LOSS_PPO = 1;
+constexpr int LOSS_A3C = 0, LOSS_PPO = 1, LOSS_PPO_EXT = 2;
 struct HeadsArgs {
   float* h;
   const float* piW;
@@ -79,8 +86,16 @@ struct HeadsArgsPpo : HeadsArgs {
   float* ratio;              // [B] rho, may be null
   float clip_eps;
 };
+// The LOSS_PPO_EXT instantiations' arguments, again a type of their own: the LOSS_A3C and
+// LOSS_PPO kernels keep their argument blocks.
+constexpr unsigned PPO_ADV_FROM_ROW = 1u;   // flags bit 0: Adv is rows[n].w
+struct HeadsArgsPpoExt : HeadsArgsPpo {
+  float vclip_eps;           // 0: no value clipping
+  unsigned flags;
+};
 template <int LOSS>
-using HeadsArgsOf = std::conditional_t<LOSS == LOSS_PPO, HeadsArgsPpo, HeadsArgs>;
+using HeadsArgsOf = std::conditional_t<LOSS == LOSS_PPO_EXT, HeadsArgsPpoExt,
+                                       std::conditional_t<LOSS == LOSS_PPO, HeadsArgsPpo, HeadsArgs>>;
 
 // The per-sample head arithmetic runs in fp64: the softmax gradient
 // p_k (g_k - sum_j p_j g_j) cancels catastrophically when the policy saturates, and fp64 here
@@ -101,8 +116,9 @@ __device__ __forceinline__ double wave_max_d(double v, int w = 64) { return wave
 // ~80 dependent global round trips per sample (r04 ISA) — the heads launch's whole time.  With
 // AT every weight load of a lane's features is unconditional (features past F read feature
 // F - 1 and are multiplied by zero), so they are all in flight together.
-// LOSS: the policy term (LOSS_A3C / LOSS_PPO), compile-time so that the A3C instantiations
-// carry nothing of the other; a LOSS_PPO launch is a training launch (p.train != 0).
+// LOSS: the policy term (LOSS_A3C / LOSS_PPO / LOSS_PPO_EXT), compile-time so that the A3C
+// instantiations carry nothing of the others; a LOSS_PPO* launch is a training launch
+// (p.train != 0).
 template <int FCH, int NZ, int AT, int LOSS>
 __device__ __forceinline__ void heads_sample(const HeadsArgsOf<LOSS>& p, int n, int lane) {
   const int A = AT ? AT : p.A;
@@ -125,7 +141,8 @@ __device__ __forceinline__ void heads_sample(const HeadsArgsOf<LOSS>& p, int n, 
   float bpre[PRE ? AT + 1 : 1];                  // pi biases, v bias
   float blg[PRE ? FCH : 1];                      // legacy FC bias of the lane's features
   float Rpre = 0.f;
-  float4 rowpre = make_float4(0.f, 0.f, 0.f, 0.f);   // LOSS_PPO: the sample's row, one 16-byte load
+  constexpr bool ROWS = LOSS != LOSS_A3C;            // LOSS_PPO*: the sample's row replaces R
+  float4 rowpre = make_float4(0.f, 0.f, 0.f, 0.f);   // one 16-byte load
   int apre = 0;
   float hv32[FCH > 0 ? FCH : 1];
   if constexpr (PRE) {
@@ -151,7 +168,7 @@ __device__ __forceinline__ void heads_sample(const HeadsArgsOf<LOSS>& p, int n, 
 #pragma unroll
     for (int a = 0; a < AT; ++a) bpre[a] = p.pib[a];
     bpre[AT] = p.vb[0];
-    if constexpr (LOSS == LOSS_PPO) rowpre = p.rows[n];
+    if constexpr (ROWS) rowpre = p.rows[n];
     else Rpre = *(p.train ? p.R + n : p.pib);
     // the action's low word (actions are small and non-negative)
     apre = *(p.train ? reinterpret_cast<const int*>(p.action + n) : reinterpret_cast<const int*>(p.pib));
@@ -272,8 +289,8 @@ __device__ __forceinline__ void heads_sample(const HeadsArgsOf<LOSS>& p, int n, 
   if (p.value && lane == 0) p.value[n] = (float)V;
   if (!p.train) return;
 
-  if constexpr (LOSS == LOSS_PPO && !PRE) rowpre = p.rows[n];
-  const double Rn = LOSS == LOSS_PPO ? (double)rowpre.x : PRE ? (double)Rpre : (double)p.R[n];
+  if constexpr (ROWS && !PRE) rowpre = p.rows[n];
+  const double Rn = ROWS ? (double)rowpre.x : PRE ? (double)Rpre : (double)p.R[n];
   const int act = (int)(PRE ? apre : p.action[n]);
   const double adv = V - Rn;
   const double beta = (double)p.beta, invB = 1.0 / (double)p.B;
@@ -282,8 +299,9 @@ __device__ __forceinline__ void heads_sample(const HeadsArgsOf<LOSS>& p, int n, 
   const double xent = wave_sum_d(pr * lp, A);
   const double lpa = __shfl(lp, act, 64);
   double c = adv, t0 = lpa * adv;                   // the policy term's coefficient and value
-  if constexpr (LOSS == LOSS_PPO) {
-    const double Adv = Rn - (double)rowpre.y;
+  if constexpr (ROWS) {
+    double Adv = Rn - (double)rowpre.y;
+    if constexpr (LOSS == LOSS_PPO_EXT) Adv = (p.flags & PPO_ADV_FROM_ROW) ? (double)rowpre.w : Adv;
     const double rho = exp(lpa - (double)rowpre.z);
     const double eps = (double)p.clip_eps;
     const double su = rho * Adv, sc = fmin(fmax(rho, 1.0 - eps), 1.0 + eps) * Adv;
@@ -294,7 +312,18 @@ __device__ __forceinline__ void heads_sample(const HeadsArgsOf<LOSS>& p, int n, 
   const double gp = mine ? ((lane == act ? c / pe : 0.0) + beta * (lp + pr / pe)) * invB : 0.0;
   const double sgp = wave_sum_d(gp * pr, A);
   const double dz = mine ? pr * (gp - sgp) : 0.0;
-  const double dV = (V - Rn) * invB;
+  // LOSS_PPO_EXT, the clipped value loss: the larger of the two squared errors, and no value
+  // gradient where it is the clipped one (selects, uniform in p.vclip_eps; 0 switches the clip
+  // off).  The other forms compile to what they were: use_clipped is a constant there.
+  bool use_clipped = false;
+  double csq = 0.0;
+  if constexpr (LOSS == LOSS_PPO_EXT) {
+    const double ve = (double)p.vclip_eps, Vold = (double)rowpre.y;
+    const double d = V - Vold, Vc = Vold + copysign(ve, d);
+    csq = (Vc - Rn) * (Vc - Rn);
+    use_clipped = ve > 0.0 && fabs(d) > ve && csq > (V - Rn) * (V - Rn);
+  }
+  const double dV = LOSS == LOSS_PPO_EXT && use_clipped ? 0.0 : (V - Rn) * invB;
   // [dz | dV | 0...] row for the head weight-gradient product
   if (lane < MAXA) p.dzv[(size_t)n * MAXA + lane] = (float)(lane == A ? dV : dz);
   double dza[NA];
@@ -341,7 +370,7 @@ __device__ __forceinline__ void heads_sample(const HeadsArgsOf<LOSS>& p, int n, 
     double t = 0.0;
     t = lane == 0 ? t0 : t;
     t = lane == 1 ? xent : t;
-    t = lane == 2 ? (V - Rn) * (V - Rn) : t;
+    t = lane == 2 ? (LOSS == LOSS_PPO_EXT && use_clipped ? csq : (V - Rn) * (V - Rn)) : t;
     t = lane == 3 ? adv : t;
     t = lane == 4 ? V : t;
     t = lane == 5 ? pmax : t;
@@ -460,6 +489,50 @@ __device__ __forceinline__ void heads_body(const HeadsArgsOf<LOSS>& p, int bx, i
 template <int FCH, int NZ, int AT = 0, int LOSS = LOSS_A3C>
 __global__ void __launch_bounds__(256) heads_kernel(const HeadsArgsOf<LOSS> p) {
   heads_body<FCH, NZ, AT, LOSS>(p, blockIdx.x, gridDim.x);
+}
+
+// ---------------------------------------------------------------------------------------
+// Per-minibatch advantage normalisation (ba3c_ppo_norm_adv; ppo.normalise_adv_numpy states it):
+// rows[i].w = (float)((Adv_i - mean) / (std + 1e-8)) with Adv_i = (double)R_i - (double)V_old_i,
+// mean = sum Adv / n and the population std = sqrt(sum (Adv - mean)^2 / n), two passes in fp64.
+// One workgroup (n is a minibatch); every sum in a fixed order — per-thread strided partials,
+// wave butterflies, the 4 wave results in wave order — so the result is a function of the rows
+// alone.  Only .w is written; stats (may be null) receives {mean, std}.
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ double block_sum_d(double v, double* red) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  v = wave_sum_d(v);
+  __syncthreads();                                   // the previous sum's readers are done
+  if (lane == 0) red[wv] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+__global__ void __launch_bounds__(256) ppo_norm_adv_kernel(float4* rows, int n, double* stats) {
+  __shared__ double red[4];
+  const int t = threadIdx.x;
+  double s = 0.0;
+  for (int i = t; i < n; i += 256) {
+    const float4 r = rows[i];
+    s += (double)r.x - (double)r.y;
+  }
+  const double mean = block_sum_d(s, red) / (double)n;
+  double q = 0.0;
+  for (int i = t; i < n; i += 256) {
+    const float4 r = rows[i];
+    const double d = ((double)r.x - (double)r.y) - mean;
+    q += d * d;
+  }
+  const double sd = sqrt(block_sum_d(q, red) / (double)n);
+  const double inv = sd + 1e-8;
+  for (int i = t; i < n; i += 256) {
+    const float4 r = rows[i];
+    reinterpret_cast<float*>(rows + i)[3] = (float)((((double)r.x - (double)r.y) - mean) / inv);
+  }
+  if (stats && t == 0) {
+    stats[0] = mean;
+    stats[1] = sd;
+  }
 }
 
 // ---------------------------------------------------------------------------------------

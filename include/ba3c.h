@@ -179,6 +179,36 @@ int ba3c_train_grads_ppo(ba3c_handle* h, void* stream, const float* params, cons
                          const int64_t* action, const float* rows, int32_t batch,
                          float entropy_beta, float clip_eps, void* workspace, float* grads,
                          double* scalars, float* ratio, int32_t phase);
+/* ba3c_train_grads_ppo with the two further pieces every PPO implementation carries (baselines
+ * ppo2, CleanRL): a caller-supplied advantage and the clipped value loss.  Everything not named
+ * here is ba3c_train_grads_ppo's: the launches, phases 0-2, rows, ratio, the scalars' scaling.
+ *   flags & BA3C_PPO_ADV_FROM_ROW: Adv = rows[n][3] (ba3c_ppo_norm_adv writes it) instead of
+ *     R - V_old, in s and in c; R and V_old keep their other uses.
+ *   vclip_eps > 0: with d = V - V_old and Vc = V_old + sign(d) vclip_eps,
+ *     use_clipped = |d| > vclip_eps and (Vc - R)^2 > (V - R)^2      (a tie is unclipped)
+ *     and the value term of the cost and scalars[3] (value_loss) take (Vc - R)^2 where
+ *     use_clipped, else (V - R)^2, i.e. 1/2 max((V - R)^2, (Vc - R)^2) per sample; dV is 0 where
+ *     use_clipped, else (V - R) / B.  scalars[4] stays mean(V - R).  vclip_eps = 0: no clipping.
+ * With vclip_eps = 0 and flags = 0 every output is ba3c_train_grads_ppo's, bit for bit.
+ * Refused with BA3C_ERR_INVALID before any GPU call, in this order: ba3c_train_grads_ppo's rows,
+ * ratio and clip_eps checks, vclip_eps negative or not finite (a NaN included), flags with a bit
+ * other than BA3C_PPO_ADV_FROM_ROW, phase outside 0..2, then ba3c_train_grads_phase's checks. */
+#define BA3C_PPO_ADV_FROM_ROW 1u
+int ba3c_train_grads_ppo_ext(ba3c_handle* h, void* stream, const float* params, const uint8_t* state,
+                             const int64_t* action, const float* rows, int32_t batch,
+                             float entropy_beta, float clip_eps, float vclip_eps, uint32_t flags,
+                             void* workspace, float* grads, double* scalars, float* ratio,
+                             int32_t phase);
+/* Per-minibatch advantage normalisation, in place on the n rows {R, V_old, l_old, .} of a PPO
+ * step (fp32 [n][4], device): with Adv_i = (double)R_i - (double)V_old_i, mean = sum Adv / n and
+ * the population std = sqrt(sum (Adv - mean)^2 / n) (two passes, fp64),
+ *   rows[i][3] = (float)((Adv_i - mean) / (std + 1e-8));
+ * columns 0-2 are not written.  stats (device, 8-byte aligned, may be NULL) receives
+ * {mean, std} as doubles.  One launch of one workgroup; the sums run in a fixed order, so the
+ * result is a function of the rows alone (a repeat gives the same bits).
+ * Refused with BA3C_ERR_INVALID before any GPU call: rows NULL or not 16-byte aligned, stats not
+ * 8-byte aligned, n < 1. */
+int ba3c_ppo_norm_adv(void* stream, float* rows, int32_t n, double* stats);
 /* Record the HIP event `event` (a hipEvent_t of the caller's, NULL: none) on the pass's stream
  * in every later phase-2 pass, right after conv3's input- and weight-gradient launches (the
  * event only has to follow phase 1): the N>1 step starts the fc1 + heads

@@ -28,12 +28,16 @@ With --ppo also the PPO learner step (`Ba3cTrainer.train_step(..., rows, clip)`,
 to the A3C step on identical batches at (B, F, S) = (32, 128, 4) and (2048, 512, 1), by the same
 method (medians of event-bracketed batches of steps, alternating), and ms per
 `ActorLearner.iterate` and samples/s on GridBoxing at 100 simulators with the A3C loop and with
---ppo_clip 0.2 at 4 epochs x 4 minibatches; --ppo_only skips the environment tables.
+--ppo_clip 0.2 at 4 epochs x 4 minibatches; --ppo_only skips the environment tables.  With
+--ppo_norm_adv and / or --ppo_vclip EPS the extended step (the normalisation launch and
+`ba3c_train_grads_ppo_ext`) and the normalisation launch alone are timed in the same alternation,
+and the loop once more with those settings.
 Prints one JSON line.
 
     python scripts/env_throughput.py [--game boxing] [--envs 8192 64] [--iters 200] [--random 20]
                                      [--frame_skip 2-4] [--sticky 0.25] [--view 1 3] [--duel]
                                      [--duel_start 8-14] [--duel_only] [--returns] [--ppo] [--ppo_only]
+                                     [--ppo_norm_adv] [--ppo_vclip 0.2]
 """
 import argparse
 import json
@@ -200,10 +204,13 @@ def returns_table(repeats):
 PPO_SHAPES = [(32, 128, 4), (2048, 512, 1)]
 
 
-def ppo_step_table(repeats, clip=0.2):
+def ppo_step_table(repeats, clip=0.2, norm_adv=False, vclip=0.0):
     """--ppo: µs per learner step (pass + fused clip + Adam apply) with the A3C loss and with the
     clipped-surrogate loss on the same batch: rows = {R, the forward's value, sample_logp's logp,
-    0} of the policy before the timed steps, so the ratios move as the steps train."""
+    0} of the policy before the timed steps, so the ratios move as the steps train.
+    norm_adv / vclip (--ppo_norm_adv / --ppo_vclip): also the extended step — the normalisation
+    launch (when asked for) and the step through ba3c_train_grads_ppo_ext — and the
+    normalisation launch alone, in the same alternation."""
     from ba3c_amd.model import Model
     from ba3c_amd.optimizer import AdamOptimizer
     from ba3c_amd.trainer import Ba3cTrainer, TrainConfig
@@ -220,12 +227,21 @@ def ppo_step_table(repeats, clip=0.2):
         rows = torch.stack([R, value, logp, torch.zeros_like(R)], dim=1).contiguous()
         legs = {"a3c_us": lambda: tr.train_step(st, ac, R),
                 "ppo_us": lambda: tr.train_step(st, ac, None, rows=rows, clip=clip)}
+        if norm_adv or vclip:
+            def ext():
+                if norm_adv:
+                    m.engine.ppo_norm_adv(rows)
+                tr.train_step(st, ac, None, rows=rows, clip=clip, vclip=vclip, adv_from_row=norm_adv)
+            legs["ppo_ext_us"] = ext
+            legs["norm_adv_us"] = lambda: m.engine.ppo_norm_adv(rows)
         t = {k: [] for k in legs}
         for _ in range(repeats):
             for k, fn in legs.items():
                 t[k].append(timed_median(fn))
         row = {k: [round(v, 2) for v in vs] for k, vs in t.items()}
         row["ppo_over_a3c"] = round(min(t["ppo_us"]) / min(t["a3c_us"]), 4)
+        if "ppo_ext_us" in t:
+            row["ppo_ext_over_ppo"] = round(min(t["ppo_ext_us"]) / min(t["ppo_us"]), 4)
         row["clip_fraction_after"] = round(float(((m.ratio - 1).abs() > clip).float().mean().item()), 4)
         out["B%d_F%d_S%d" % (B, F, S)] = row
         tr.check_device_errors()
@@ -260,7 +276,9 @@ def iterate_table(settings, iters=420, warmup=42, E=100):
         dt = time.time() - t0
         key = "local_time_max=%d,gae_lambda=%g" % (ltm, lam)
         if ppo is not None:
-            key += ",ppo_clip=%g,epochs=%d,minibatches=%d" % tuple(ppo)
+            key += ",ppo_clip=%g,epochs=%d,minibatches=%d" % tuple(ppo)[:3]
+            if ppo.norm_adv or ppo.vclip:
+                key += ",norm_adv=%d,vclip=%g" % (ppo.norm_adv, ppo.vclip)
         out.setdefault(key, []).append({
             "ms_per_iterate": round(dt * 1e3 / iters, 3), "iterations": iters,
             "train_steps": al.train_steps - steps0,
@@ -277,6 +295,10 @@ def main(argv=None):
                     help="also time the PPO learner step next to the A3C step on identical batches, "
                          "and one ActorLearner iteration with and without --ppo_clip 0.2 (4 x 4)")
     ap.add_argument("--ppo_only", action="store_true", help="--ppo: skip the environment tables")
+    ap.add_argument("--ppo_norm_adv", action="store_true",
+                    help="--ppo: also time the extended step with the advantage normalisation launch")
+    ap.add_argument("--ppo_vclip", type=float, default=0.0,
+                    help="--ppo: also time the extended step with this value clip (0: off)")
     ap.add_argument("--duel", action="store_true",
                     help="also time two-player GridBoxing at G = E / 2 games against BoxingVec at E")
     ap.add_argument("--envs", type=int, nargs="+", default=[8192, 64])
@@ -389,9 +411,12 @@ def main(argv=None):
         out["iterate"] = iterate_table([(5, 1.0), (20, 0.95), (5, 1.0), (20, 0.95)])
     if args.ppo:
         from ba3c_amd.ppo import Setting
-        out["ppo_step"] = ppo_step_table(args.repeats)
+        out["ppo_step"] = ppo_step_table(args.repeats, norm_adv=args.ppo_norm_adv, vclip=args.ppo_vclip)
         on = Setting(clip=0.2, epochs=4, minibatches=4)
-        out["ppo_iterate"] = iterate_table([(5, 1.0), (5, 1.0, on), (5, 1.0), (5, 1.0, on)])
+        legs = [(5, 1.0), (5, 1.0, on)]
+        if args.ppo_norm_adv or args.ppo_vclip:
+            legs.append((5, 1.0, on._replace(norm_adv=args.ppo_norm_adv, vclip=args.ppo_vclip)))
+        out["ppo_iterate"] = iterate_table(legs * 2)
     if args.random:
         from ba3c_amd.evaluate import eval_with_envs, uniform_policy
         from ba3c_amd.model import Model
