@@ -8,11 +8,11 @@ One iteration is the reference's per-simulator message cycle (RL/simulator.py:95
   state (FrameHistory, RL/history.py) -> predictor forward ('logitsT', 'pred_value') ->
   action = np.random.choice semantics on the GPU from host MT19937 draws (train.py:382) ->
   RolloutBuffer.on_state -> env step -> FrameHistory.push -> RolloutBuffer.on_reward
-  (n-step returns, train.py:408-437) -> BatchQueue (BatchData) -> Ba3cTrainer.train_step
+  (n-step returns, train.py:408-437) -> a consumer of the datapoints
 
-With a PPO setting (ActorLearner(ppo=...), ba3c_amd.ppo) the datapoints go to a replay pool
-instead of the BatchQueue and every pool is trained for several passes with the clipped-surrogate
-loss; without one the loop is the reference's.
+The consumer is a BatchTrainer (BatchQueue (BatchData) -> Ba3cTrainer.train_step: the reference's
+loop) or, with a PPO setting (ActorLearner(ppo=...), ba3c_amd.ppo), a PoolTrainer: a replay pool
+whose every minibatch is trained for several passes with the clipped-surrogate loss.
 
 The synthetic environment is NOT part of the reference's hot path; it only produces frames,
 rewards and episode ends with the shapes and value ranges of the Atari pipeline (84x84
@@ -61,35 +61,118 @@ class SyntheticAtari(object):
         return self.frames(), reward, over
 
 
+class BatchTrainer(object):
+    """The A3C consumer: BatchData(B) over the datapoints, one learner step per complete batch."""
+
+    def __init__(self, trainer, batch_size, after_step):
+        self.trainer, self.after_step = trainer, after_step
+        self.queue = BatchQueue(batch_size)
+
+    def consume(self, dps):
+        self.queue.put(dps)
+        while True:
+            b = self.queue.get()
+            if b is None:
+                break
+            self.trainer.train_step(b[0].contiguous(), b[1].contiguous(), b[2].contiguous())
+            self.after_step()
+
+
+class PoolTrainer(object):
+    """The PPO consumer: a ppo.Pool of minibatches * batch_size datapoints, every minibatch it
+    yields trained with the clipped-surrogate loss of `setting` (a ppo.Setting).
+    last_ratio: the last step's per-sample ratio, on the device.
+    last_adv_stats: with norm_adv, the {mean, std} of the last minibatch normalised, two doubles on
+      the device (the pool's own rows keep 0 in column 3); None without.
+    pool_epochs: per pool left, the epochs it ran (steps / minibatches).
+    epoch_kls: with target_kl > 0, every epoch's mean of ppo.stop_kl over its minibatches, read
+      once per epoch (the only host synchronisation added); ppo.should_stop on it abandons the
+      pool's remaining epochs.
+    stop_at (None: off): a pool ends early once the trainer's global_step reaches it."""
+
+    def __init__(self, trainer, setting, batch_size, seed, after_step, stop_at=None):
+        self.trainer, self.setting, self.after_step = trainer, setting, after_step
+        self.stop_at = stop_at
+        self.pool = ppo_rules.Pool(batch_size, minibatches=setting.minibatches,
+                                   epochs=setting.epochs, seed=seed)
+        self.last_ratio = None
+        self.last_adv_stats = torch.zeros(
+            2, dtype=torch.float64, device=trainer.engine.device) if setting.norm_adv else None
+        self.pool_epochs = []
+        self.epoch_kls = []
+        self._kl = None                   # the running epoch's sum of step KLs, on the device
+
+    def consume(self, dps):
+        self.pool.put(dps)
+        while True:
+            batches = self.pool.get()
+            if batches is None:
+                break
+            self.pool_epochs.append(self._train(batches) / float(self.pool.M))
+
+    def _train(self, batches):
+        """The steps run on one pool's minibatches."""
+        ran, self._kl = 0, None
+        for st, ac, rows in batches:
+            if self._cut_off():
+                break
+            self._normalise(rows)
+            self._step(st, ac, rows)
+            ran += 1
+            if self._kl_stops(ran):
+                break
+        return ran
+
+    def _cut_off(self):
+        return self.stop_at is not None and self.trainer.global_step >= self.stop_at
+
+    def _normalise(self, rows):
+        if self.setting.norm_adv:
+            self.trainer.engine.ppo_norm_adv(rows, self.last_adv_stats)    # the gathered copy, in place
+
+    def _step(self, st, ac, rows):
+        s = self.setting
+        self.trainer.train_step(st, ac, None, rows=rows, clip=s.clip, vclip=s.vclip,
+                                adv_from_row=s.norm_adv)
+        self.last_ratio = self.trainer.model.ratio
+        self.after_step()
+
+    def _kl_stops(self, ran):
+        """Adds the step's KL to the epoch's sum; at an epoch's end (the one host read) whether
+        its mean stops the pool."""
+        if not self.setting.target_kl > 0:
+            return False
+        step_kl = ppo_rules.stop_kl_device(self.last_ratio)
+        self._kl = step_kl if self._kl is None else self._kl + step_kl
+        if ran % self.pool.M:
+            return False
+        self.epoch_kls.append(float((self._kl / self.pool.M).item()))
+        self._kl = None
+        return ppo_rules.should_stop(self.epoch_kls[-1], self.setting.target_kl)
+
+
 class ActorLearner(object):
     """The loop above around an existing Ba3cTrainer (whose model engine also serves as the
     predictor: the reference's towerp0 reads the same variables, train.py:355-362)."""
 
     def __init__(self, trainer, n_envs, batch_size, seed=0, rs=None, on_train_step=None,
                  dummy_predictor=False, env=None, local_time_max=LOCAL_TIME_MAX, gamma=GAMMA,
-                 gae_lambda=1.0, ppo=None):
-        """ppo: None is the A3C loop; a ppo.Setting(clip, epochs, minibatches) records each action's
-        log-probability under the policy that drew it (sample_logp on the forward's 'logitsT' /
-        'logits'), feeds a ppo.Pool of minibatches * batch_size datapoints instead of the
-        BatchQueue, trains every minibatch the pool yields with the clipped-surrogate loss and
-        keeps the last step's per-sample ratio on the device (last_ratio).  stop_at (an attribute, None: off) ends a pool early once the trainer's
-        global_step reaches it.
-        The setting's norm_adv normalises each gathered minibatch's advantages on the device
-        before its step (the pool's own rows keep 0 in column 3) and keeps the batch's {mean, std}
-        on the device (last_adv_stats); vclip > 0 is the clipped value loss; target_kl > 0 reads
-        the mean of ppo.stop_kl (mean((rho - 1) - log rho)) over an epoch's minibatches once per
-        epoch — the only host synchronisation it adds — and abandons the pool's remaining epochs
-        when ppo.should_stop says so.  pool_epochs lists, per pool left, the epochs it ran
-        (steps / minibatches), epoch_kls every epoch mean that was read.
-        local_time_max, gamma, gae_lambda: the rollout length, discount and GAE lambda of the
-        RolloutBuffer's returns (--local_time_max, --gamma, --gae_lambda; the defaults are the
-        reference's 5-step, 0.99, n-step recipe).
-        env: the vector of simulators (None: SyntheticAtari, as before); an env with
-        `step_into(actions, hist)` (BreakoutVec, BoxingVec) is stepped through it, the
-        frame-history push fused into the env's launch.
-        on_train_step(trainer): called after every learner step (callbacks / metrics);
-        dummy_predictor: --dummy_predictor 1 (predict/base.py:94-105) — uniform policy and
-        U(0,1) values instead of the network forward."""
+                 gae_lambda=1.0, ppo=None, stop_at=None):
+        """trainer: the Ba3cTrainer that takes the learner steps.
+        n_envs, batch_size: simulators stepped per iteration, datapoints per learner step.
+        seed, rs: of the synthetic environment and the PPO pool; the host stream of the action
+          draws (None: RandomState(seed)).
+        on_train_step(trainer): called after every learner step (callbacks / metrics).
+        dummy_predictor: --dummy_predictor 1 (predict/base.py:94-105), a uniform policy and
+          U(0,1) values instead of the network forward.
+        env: the vector of simulators (None: SyntheticAtari); one with `step_into(actions, hist)`
+          (BreakoutVec, BoxingVec) has the frame-history push fused into its launch.
+        local_time_max, gamma, gae_lambda: the RolloutBuffer's rollout length, discount and GAE
+          lambda (the defaults are the reference's 5-step, 0.99, n-step recipe).
+        ppo: None is the A3C loop (`queue`, a BatchTrainer's); a ppo.Setting records each action's
+          log-probability under the policy that drew it and feeds a PoolTrainer (`pool_trainer`,
+          whose Pool is `pool`).
+        stop_at: the PoolTrainer's; unused without ppo."""
         eng = trainer.engine
         assert eng.channels == 4, "synthetic loop is grayscale x FRAME_HISTORY=4"
         self.trainer = trainer
@@ -105,15 +188,12 @@ class ActorLearner(object):
             raise ValueError("PPO records log pi of the policy it samples from: explore_factor must be 1")
         self.buf = RolloutBuffer(n_envs, channels=4, local_time_max=local_time_max, gamma=gamma,
                                  gae_lambda=gae_lambda, device=eng.device, logp=ppo is not None)
-        self.queue = BatchQueue(batch_size)
-        self.pool = None if ppo is None else ppo_rules.Pool(
-            batch_size, minibatches=ppo.minibatches, epochs=ppo.epochs, seed=seed)
-        self.last_ratio = None
-        self.last_adv_stats = None
-        self._adv_stats = None
-        self.pool_epochs = []
-        self.epoch_kls = []               # every epoch mean read for the KL stop, in order
-        self.stop_at = None
+        if ppo is None:
+            self.consumer = BatchTrainer(trainer, batch_size, self._after_step)
+            self.queue, self.pool_trainer, self.pool = self.consumer.queue, None, None
+        else:
+            self.consumer = PoolTrainer(trainer, ppo, batch_size, seed, self._after_step, stop_at)
+            self.queue, self.pool_trainer, self.pool = None, self.consumer, self.consumer.pool
         self.rs = rs if rs is not None else np.random.RandomState(seed)
         self.hist.push(self.env.frames(), torch.ones(n_envs, dtype=torch.bool, device=eng.device))
         self.steps = 0
@@ -123,20 +203,13 @@ class ActorLearner(object):
         self.dummy_predictor = dummy_predictor
 
     def _predict(self, state):
+        """(sampled_from, recorded, value): the distribution the action is drawn from, the one
+        whose log is kept (PPO) and the value."""
         eng = self.engine
         if self.dummy_predictor:
             E, A = self.env.E, eng.num_actions
             probs = torch.full((E, A), 1.0 / A, dtype=torch.float32, device=eng.device)
             value = torch.from_numpy(self.rs.uniform(size=E).astype(np.float32)).to(eng.device)
-            return probs, value
-        _, probsT, value = eng.forward(state, explore_factor=self.trainer.model.explore_factor)
-        return probsT, value
-
-    def _predict_both(self, state):
-        """(probsT, probs, value): the distribution sampled from and the one whose log is kept."""
-        eng = self.engine
-        if self.dummy_predictor:
-            probs, value = self._predict(state)
             return probs, probs, value
         probs, probsT, value = eng.forward(state, explore_factor=self.trainer.model.explore_factor)
         return probsT, probs, value
@@ -147,72 +220,23 @@ class ActorLearner(object):
         if self.on_train_step is not None:
             self.on_train_step(self.trainer)
 
-    def _iterate_ppo(self):
-        eng, clip = self.engine, self.ppo.clip
-        state = self.hist.state
-        probsT, probs, value = self._predict_both(state)
-        u = torch.from_numpy(self.rs.random_sample(self.env.E)).to(eng.device)
-        actions, logp, flag = eng.sample_logp(probsT, probs, u)
-        self.buf.on_state(state, actions, value, logp=logp)
-        if self._fused:
-            reward, over = self.env.step_into(actions, self.hist)
-        else:
-            frames, reward, over = self.env.step(actions)
-            self.hist.push(frames, over)
-        self.pool.put(self.buf.on_reward(reward, over))
-        while True:
-            batches = self.pool.get()
-            if batches is None:
-                break
-            M, kl, ran = self.pool.M, None, 0
-            for st, ac, rows in batches:
-                if self.stop_at is not None and self.trainer.global_step >= self.stop_at:
-                    break
-                if self.ppo.norm_adv:
-                    if self._adv_stats is None:
-                        self._adv_stats = torch.zeros(2, dtype=torch.float64, device=eng.device)
-                    eng.ppo_norm_adv(rows, self._adv_stats)       # the gathered copy, in place
-                    self.last_adv_stats = self._adv_stats
-                self.trainer.train_step(st, ac, None, rows=rows, clip=clip, vclip=self.ppo.vclip,
-                                        adv_from_row=self.ppo.norm_adv)
-                self.last_ratio = self.trainer.model.ratio
-                self._after_step()
-                ran += 1
-                if self.ppo.target_kl > 0:
-                    rho = self.last_ratio.double()
-                    step_kl = ((rho - 1.0) - torch.log(rho)).mean()      # ppo.stop_kl, on the device
-                    kl = step_kl if kl is None else kl + step_kl
-                    if ran % M == 0:                              # an epoch's end: the one host read
-                        self.epoch_kls.append(float((kl / M).item()))
-                        if ppo_rules.should_stop(self.epoch_kls[-1], self.ppo.target_kl):
-                            break
-                        kl = None
-            self.pool_epochs.append(ran / float(M))
-        self.steps += 1
-        if int(flag.item()) & 1:
-            raise AssertionError("non-finite action distribution (train.py:381)")
-
     def iterate(self):
-        if self.ppo is not None:
-            return self._iterate_ppo()
         eng = self.engine
         state = self.hist.state
-        probsT, value = self._predict(state)
+        sampled_from, recorded, value = self._predict(state)
         u = torch.from_numpy(self.rs.random_sample(self.env.E)).to(eng.device)
-        actions, flag = eng.sample(probsT, u)
-        self.buf.on_state(state, actions, value)
+        if self.ppo is not None:
+            actions, logp, flag = eng.sample_logp(sampled_from, recorded, u)
+            self.buf.on_state(state, actions, value, logp=logp)
+        else:
+            actions, flag = eng.sample(sampled_from, u)
+            self.buf.on_state(state, actions, value)
         if self._fused:
             reward, over = self.env.step_into(actions, self.hist)
         else:
             frames, reward, over = self.env.step(actions)
             self.hist.push(frames, over)
-        self.queue.put(self.buf.on_reward(reward, over))
-        while True:
-            b = self.queue.get()
-            if b is None:
-                break
-            self.trainer.train_step(b[0].contiguous(), b[1].contiguous(), b[2].contiguous())
-            self._after_step()
+        self.consumer.consume(self.buf.on_reward(reward, over))
         self.steps += 1
         if int(flag.item()) & 1:
             raise AssertionError("non-finite action distribution (train.py:381)")

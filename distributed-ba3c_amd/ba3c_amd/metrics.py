@@ -6,12 +6,14 @@ message tuples ('loss', cost, policy_loss, xentropy_loss, value_loss, advantage,
 max_logit), ('other', active_relus, dp_per_s) and ('delays', (mean, max, min)); the
 CsvChannels sink replaces the Neptune metrics server's _dump_to_channels
 (neptune_mp_server.py:169-233) writing one `<channel>.csv` ("x,y" rows, x = hours since start)
-per channel as utils/neptune_utils.py:38-57 does.
+per channel as utils/neptune_utils.py:38-57 does.  StepMetrics is the launcher's per-step
+callback in front of both, PpoMetrics its PPO channels.
 """
 import os
 import time
 
 import numpy as np
+import torch
 
 
 class StatCounter(object):
@@ -136,3 +138,103 @@ class DebugLogCallback(object):
         self.dp_per_s.reset()
         self.delays = []
         return True
+
+
+class PpoMetrics(object):
+    """The PPO channels of a StepMetrics, from the ratios a PoolTrainer's steps leave on the device.
+    Per flushed batch of steps: ppo_clip_fraction = mean(|rho - 1| > clip), ppo_approx_kl =
+    mean(-log rho) and, when the consumer normalises advantages, ppo_adv_mean / ppo_adv_std: the
+    means of its {mean, std} over the flushed steps.
+    ppo_epochs_run (with a target KL only) is not a per-step channel: it is the mean epochs per
+    pool over the pools left since the last flush, and a pool is left after its last step's
+    callback.  So flush_epochs writes it at every flush before which a pool was left, pending
+    steps or not, and flush_steps never does; last_ppo carries the latest of both."""
+
+    def __init__(self, clip, consumer, client=None):
+        self.clip, self.consumer, self.client = clip, consumer, client
+        self.ratios = []
+        self.adv_stats = []
+        self.pools_seen = 0
+        self.epochs_run = None
+        self.last_ppo = None
+
+    def on_step(self, trainer):
+        if trainer.model.ratio is not None:
+            self.ratios.append(trainer.model.ratio.clone())
+            if self.consumer.last_adv_stats is not None:
+                self.adv_stats.append(self.consumer.last_adv_stats.clone())
+
+    def flush_epochs(self):
+        left = self.consumer.pool_epochs
+        if not self.consumer.setting.target_kl > 0 or len(left) == self.pools_seen:
+            return
+        self.epochs_run = float(np.mean(left[self.pools_seen:]))
+        self.pools_seen = len(left)
+        if self.last_ppo is not None:
+            self.last_ppo["ppo_epochs_run"] = self.epochs_run
+        if self.client is not None:
+            self.client.write_scalar("ppo_epochs_run", self.epochs_run)
+
+    def flush_steps(self):
+        if not self.ratios:
+            return
+        from . import ppo
+        rho = torch.cat(self.ratios).cpu().numpy()
+        self.ratios = []
+        per_step = {"ppo_clip_fraction": ppo.clip_fraction(rho, self.clip),
+                    "ppo_approx_kl": ppo.approx_kl(rho)}
+        if self.adv_stats:
+            m = torch.stack(self.adv_stats).cpu().numpy().mean(axis=0)
+            self.adv_stats = []
+            per_step.update(ppo_adv_mean=float(m[0]), ppo_adv_std=float(m[1]))
+        if self.client is not None:
+            for name, v in per_step.items():
+                self.client.write_scalar(name, v)
+        self.last_ppo = per_step
+        if self.epochs_run is not None:
+            self.last_ppo["ppo_epochs_run"] = self.epochs_run
+
+
+class StepMetrics(object):
+    """DebugLogCallback over device-resident step scalars: each learner step's 8 scalars are
+    kept on the GPU and fetched once per `every` (--send_debug_every) steps (no per-step host
+    sync).  ppo: a PpoMetrics fed and flushed along (None: off)."""
+
+    def __init__(self, trainer, batch_size, every, client, ppo=None):
+        self.trainer, self.B, self.ppo = trainer, batch_size, ppo
+        self.every = max(1, int(every))
+        self.cb = DebugLogCallback(client, worker_id=0, nr_send=self.every) if client else None
+        self.pending = []
+        self.t0 = time.time()
+        self.last = None
+
+    @property
+    def last_ppo(self):
+        return self.ppo.last_ppo if self.ppo is not None else None
+
+    def __call__(self, trainer):
+        self.pending.append(trainer.model.scalars.clone())
+        if self.ppo is not None:
+            self.ppo.on_step(trainer)
+        if len(self.pending) >= self.every:
+            self.flush()
+
+    def flush(self):
+        if self.ppo is not None:
+            self.ppo.flush_epochs()
+        if not self.pending:
+            return
+        from ._lib import SCALAR_NAMES
+        vals = torch.stack(self.pending).cpu().numpy()
+        self.trainer.check_device_errors()           # the host has synchronised anyway
+        dt = time.time() - self.t0
+        dp_per_s = len(self.pending) * self.B / max(dt, 1e-9)      # multigpu.py:307-313
+        for row in vals:
+            d = dict(zip(SCALAR_NAMES, row.tolist()))
+            self.last = d
+            if self.cb is not None:
+                self.cb.trigger_step(d, dp_per_s)
+        self.pending = []
+        if self.ppo is not None:
+            self.ppo.flush_steps()
+        self.t0 = time.time()

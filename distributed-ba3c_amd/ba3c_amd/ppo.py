@@ -193,6 +193,13 @@ def stop_kl(rho):
     return float(np.mean((rho - 1.0) - np.log(rho)))
 
 
+def stop_kl_device(rho):
+    """stop_kl of a torch tensor as a float64 scalar on the tensor's device; no host read."""
+    import torch
+    rho = rho.double()
+    return ((rho - 1.0) - torch.log(rho)).mean()
+
+
 def device_gather(src, idx):
     """src[idx] along the first axis with `ba3c_gather_rows` (rows of any byte size the kernel
     moves: states, 8-byte actions, 16-byte rows); idx: an int32 device tensor."""

@@ -1,19 +1,22 @@
-"""`python -m ba3c_amd.train` — the single-node launcher on the reference's flag surface.
+"""`python -m ba3c_amd.train` — the single-node launcher on the reference's flag surface
+(run_job.py:13-148 -> distributed_tensorpack_mkl.sh -> OpenAIGym/train.py:649-724, get_config
+:505-638).  What it builds, per flag group:
 
-Replaces run_job.py:13-148 -> distributed_tensorpack_mkl.sh -> OpenAIGym/train.py:649-724
-(get_config :505-638): from the same flags it builds the Model (train.py:517), the optimizer
-(`-o`, :582-597), SyncReplicasOptimizer for `--use_sync -g N` (:598-606, here an RCCL
-all-reduce over the node's GPUs), the trainer and the actor-learner loop (simulator master +
-predictor + BatchData, :520-534 — with the synthetic on-device environment, gym/ALE being
-absent, or with `-e GridBreakout-v0` / `-e GridBoxing-v0` the on-device Breakout / Boxing of
-flags.GAMES (`--frame_skip` / `--sticky`: ALE's frame skip and sticky actions, for training and
-evaluation alike; `--self_play`: two-player GridBoxing, ba3c_amd.duel, every game's two sides
-both played by the learner, with `--duel_frame_skip` / `--duel_sticky` per side and `--duel_start`, the gap
-between the boxers of a fresh episode; `--local_time_max` / `--gamma` / `--gae_lambda`: the rollout length,
-discount and GAE lambda of the returns, ba3c_amd.returns; `--ppo_clip` / `--ppo_epochs` /
-`--ppo_minibatches`: the clipped-surrogate loss over replayed pools of datapoints, ba3c_amd.ppo) and, for `--nr_eval N`, the Evaluator callback every --steps_per_epoch steps), plus
-the DebugLogCallback metrics channels and PeriodicPerStepCallback(ModelSaver) (:608-630) and
-`--load` (SaverRestore, :706-707).
+- model geometry and `-b`: the Model (train.py:517).
+- `-o` and its hyper-parameters: the optimizer (:582-597).
+- `--use_sync -g N`: SyncReplicasOptimizer (:598-606), here an RCCL all-reduce over the node's GPUs.
+- `-e`, `--simulator_procs`: the actor-learner loop (simulator master + predictor + BatchData,
+  :520-534) on the synthetic on-device environment or on a game of flags.GAMES.
+- `--frame_skip` / `--sticky`: ALE's frame skip and sticky actions, for training and evaluation.
+- `--self_play`, `--duel_frame_skip` / `--duel_sticky` / `--duel_start`: two-player GridBoxing
+  (ba3c_amd.duel), both sides played by the learner.
+- `--local_time_max` / `--gamma` / `--gae_lambda`: the returns' rollout length, discount and GAE
+  lambda (ba3c_amd.returns).
+- `--ppo_clip` and the other `--ppo_*`: the clipped-surrogate loss over replayed pools (ba3c_amd.ppo).
+- `--nr_eval N`: the Evaluator callback every --steps_per_epoch steps.
+- `--send_debug_every`, `--experiment_dir`: DebugLogCallback's metrics channels (ba3c_amd.metrics).
+- `--save_every`, `--models_dir`, `--load`: PeriodicPerStepCallback(ModelSaver) (:608-630) and
+  SaverRestore (:706-707).
 
 One process per GPU: launch N > 1 with
     torchrun --nproc-per-node N --master-addr 127.0.0.1 -m ba3c_amd.train --use_sync -g N ...
@@ -99,88 +102,6 @@ def build(args, rank=0, world=1, device=None):
     return model, trainer, savers
 
 
-class _Metrics(object):
-    """DebugLogCallback over device-resident step scalars: each learner step's 8 scalars are
-    kept on the GPU and fetched once per --send_debug_every steps (no per-step host sync)."""
-
-    def __init__(self, trainer, batch_size, every, client, ppo_clip=None):
-        """ppo_clip (eps, None: off): each PPO step's per-sample ratio is kept on the device too, and
-        every flush writes two more channels from them: ppo_clip_fraction = mean(|rho - 1| > eps)
-        and ppo_approx_kl = mean(-log rho) over the flushed steps.  With a `learner` attached
-        (an ActorLearner) whose setting normalises advantages, each step's device-held
-        {mean, std} is kept as well and a flush writes their means over the flushed steps as
-        ppo_adv_mean / ppo_adv_std; with a target KL it writes ppo_epochs_run, the mean epochs
-        per pool over the pools left since the last flush."""
-        from .metrics import DebugLogCallback
-        self.ppo_clip, self.client = ppo_clip, client
-        self.ratios = []
-        self.adv_stats = []
-        self.learner = None
-        self.pools_seen = 0
-        self.epochs_run = None
-        self.last_ppo = None
-        self.trainer, self.B = trainer, batch_size
-        self.every = max(1, int(every))
-        self.cb = DebugLogCallback(client, worker_id=0, nr_send=self.every) if client else None
-        self.pending = []
-        self.t0 = time.time()
-        self.last = None
-
-    def __call__(self, trainer):
-        self.pending.append(trainer.model.scalars.clone())
-        if self.ppo_clip is not None and trainer.model.ratio is not None:
-            self.ratios.append(trainer.model.ratio.clone())
-            if self.learner is not None and self.learner.last_adv_stats is not None:
-                self.adv_stats.append(self.learner.last_adv_stats.clone())
-        if len(self.pending) >= self.every:
-            self.flush()
-
-    def _flush_epochs(self):
-        # a pool is left after its last step's callback, so this runs with nothing pending too
-        al = self.learner
-        if al is None or not al.ppo.target_kl > 0 or len(al.pool_epochs) == self.pools_seen:
-            return
-        self.epochs_run = float(np.mean(al.pool_epochs[self.pools_seen:]))
-        self.pools_seen = len(al.pool_epochs)
-        if self.last_ppo is not None:
-            self.last_ppo["ppo_epochs_run"] = self.epochs_run
-        if self.client is not None:
-            self.client.write_scalar("ppo_epochs_run", self.epochs_run)
-
-    def flush(self):
-        self._flush_epochs()
-        if not self.pending:
-            return
-        from ._lib import SCALAR_NAMES
-        vals = torch.stack(self.pending).cpu().numpy()
-        self.trainer.check_device_errors()           # the host has synchronised anyway
-        dt = time.time() - self.t0
-        dp_per_s = len(self.pending) * self.B / max(dt, 1e-9)      # multigpu.py:307-313
-        for row in vals:
-            d = dict(zip(SCALAR_NAMES, row.tolist()))
-            self.last = d
-            if self.cb is not None:
-                self.cb.trigger_step(d, dp_per_s)
-        self.pending = []
-        if self.ratios:
-            from . import ppo
-            rho = torch.cat(self.ratios).cpu().numpy()
-            self.ratios = []
-            self.last_ppo = {"ppo_clip_fraction": ppo.clip_fraction(rho, self.ppo_clip),
-                             "ppo_approx_kl": ppo.approx_kl(rho)}
-            if self.adv_stats:
-                m = torch.stack(self.adv_stats).cpu().numpy().mean(axis=0)
-                self.adv_stats = []
-                self.last_ppo.update(ppo_adv_mean=float(m[0]), ppo_adv_std=float(m[1]))
-            if self.epochs_run is not None:
-                self.last_ppo["ppo_epochs_run"] = self.epochs_run
-            if self.client is not None:
-                for name, v in self.last_ppo.items():
-                    if name != "ppo_epochs_run":                  # written where it is taken
-                        self.client.write_scalar(name, v)
-        self.t0 = time.time()
-
-
 def main(argv=None):
     args = resolve(build_parser().parse_args(argv))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -204,12 +125,10 @@ def main(argv=None):
 
 def _run(args, rank, world):
     from .actor_learner import ActorLearner
-    from .metrics import CsvChannels
+    from .metrics import CsvChannels, PpoMetrics, StepMetrics
     np.random.seed(rank)                                      # train.py:679
     model, trainer, savers = build(args, rank, world)
     client = CsvChannels(args.experiment_dir) if rank == 0 else None
-    metrics = _Metrics(trainer, args.batch_size, args.send_debug_every, client,
-                       ppo_clip=args.ppo.clip if args.ppo is not None else None)
 
     evaluator = None
     if args.nr_eval and rank == 0:
@@ -219,7 +138,7 @@ def _run(args, rank, world):
                               sticky=args.play_sticky)
 
     def on_step(tr):
-        metrics(tr)
+        metrics(tr)                                           # built below, before the first step
         for cb in savers:
             cb.trigger_step(tr)
         if evaluator is not None and tr.global_step % args.steps_per_epoch == 0:
@@ -227,18 +146,8 @@ def _run(args, rank, world):
 
     max_steps = args.max_steps or args.steps_per_epoch * args.max_epoch
     t0 = time.time()
-    if args.dummy:
-        # --dummy 1: a constant synthetic batch, no simulators (train/multigpu.py:70-75)
-        dev = trainer.engine.device
-        B = args.batch_size
-        state = torch.ones(B, 84, 84, trainer.engine.channels, dtype=torch.uint8, device=dev)
-        action = torch.zeros(B, dtype=torch.int64, device=dev)
-        R = torch.zeros(B, dtype=torch.float32, device=dev)
-        while trainer.global_step < max_steps:
-            trainer.train_step(state, action, R)
-            on_step(trainer)
-        sim_steps = 0
-    else:
+    al = None
+    if not args.dummy:
         env = None
         if args.self_play:
             # --simulator_procs players in half as many two-player games; both sides learn
@@ -254,9 +163,22 @@ def _run(args, rank, world):
                           seed=rank, rs=np.random.RandomState(rank), on_train_step=on_step,
                           dummy_predictor=bool(args.dummy_predictor), env=env,
                           local_time_max=args.local_time_max, gamma=args.gamma,
-                          gae_lambda=args.gae_lambda, ppo=args.ppo)
-        al.stop_at = max_steps if args.ppo is not None else None
-        metrics.learner = al if args.ppo is not None else None
+                          gae_lambda=args.gae_lambda, ppo=args.ppo, stop_at=max_steps)
+    pool_trainer = al.pool_trainer if al is not None else None
+    metrics = StepMetrics(trainer, args.batch_size, args.send_debug_every, client,
+                          ppo=PpoMetrics(args.ppo.clip, pool_trainer, client) if pool_trainer else None)
+    if al is None:
+        # --dummy 1: a constant synthetic batch, no simulators (train/multigpu.py:70-75)
+        dev = trainer.engine.device
+        B = args.batch_size
+        state = torch.ones(B, 84, 84, trainer.engine.channels, dtype=torch.uint8, device=dev)
+        action = torch.zeros(B, dtype=torch.int64, device=dev)
+        R = torch.zeros(B, dtype=torch.float32, device=dev)
+        while trainer.global_step < max_steps:
+            trainer.train_step(state, action, R)
+            on_step(trainer)
+        sim_steps = 0
+    else:
         while trainer.global_step < max_steps:
             al.iterate()
         sim_steps = al.steps

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from loop_mirror import LoopMirror
 from oracle import ba3c_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -24,26 +25,7 @@ def test_actor_learner_runs_and_feeds_the_reference_datapoints():
     loop = ActorLearner(tr, n_envs=E, batch_size=B, seed=1)
 
     # mirror the simulator master on the host from what the loop's components produce
-    mirror = O.SimulatorMasterMirror()
-    consumed = []
-    orig_put = loop.queue.put
-
-    def put(dps):
-        consumed.extend(zip(dps.action.cpu().numpy().tolist(), dps.R.cpu().numpy().tolist()))
-        orig_put(dps)
-    loop.queue.put = put
-    orig_on_state, orig_on_reward = loop.buf.on_state, loop.buf.on_reward
-
-    def on_state(states, actions, values):
-        for e, (a, v) in enumerate(zip(actions.cpu().numpy(), values.cpu().numpy())):
-            mirror.on_state(e, None, int(a), np.float32(v))
-        orig_on_state(states, actions, values)
-
-    def on_reward(rew, over):
-        for e, (r, o) in enumerate(zip(rew.cpu().numpy(), over.cpu().numpy())):
-            mirror.on_message(e, float(r), bool(o))
-        return orig_on_reward(rew, over)
-    loop.buf.on_state, loop.buf.on_reward = on_state, on_reward
+    taps = LoopMirror(loop, O.SimulatorMasterMirror())
 
     loop.run(40)
     torch.cuda.synchronize()
@@ -51,8 +33,8 @@ def test_actor_learner_runs_and_feeds_the_reference_datapoints():
     sc = loop.last_scalars.cpu().numpy()
     assert np.all(np.isfinite(sc))
     assert not torch.equal(m.engine.params, p0)
-    want = [(k["action"], float(np.float32(R))) for k, R, _, _ in mirror.queue]
-    assert consumed == want and len(want) >= B * loop.train_steps
+    want = taps.queued()
+    assert taps.consumed == want and len(want) >= B * loop.train_steps
 
 
 def test_launcher_runs_sync_training_and_saves_a_checkpoint(tmp_path):

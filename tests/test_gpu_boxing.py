@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from boxing_policy import PUNCH, QUIET, history_push_numpy, make_row, player_from_row, trajectory
+from loop_mirror import LoopMirror
 from oracle import ba3c_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -186,44 +187,20 @@ def test_actor_learner_on_boxing_samples_18_actions_and_feeds_the_reference_data
     loop = ActorLearner(tr, n_envs=E, batch_size=B, seed=1, env=env)
     assert loop.env is env and loop.hist.state[..., 3].any() and not loop.hist.state[..., :3].any()
 
-    mirror = O.SimulatorMasterMirror()
-    consumed = []
-    orig_put = loop.queue.put
-
-    def put(dps):
-        consumed.extend(zip(dps.action.cpu().numpy().tolist(), dps.R.cpu().numpy().tolist()))
-        orig_put(dps)
-    loop.queue.put = put
-    orig_on_state, orig_on_reward = loop.buf.on_state, loop.buf.on_reward
-    sampled, rewards = [], []
-
-    def on_state(states, actions, values):
-        sampled.extend(actions.cpu().numpy().tolist())
-        for e, (a, v) in enumerate(zip(actions.cpu().numpy(), values.cpu().numpy())):
-            mirror.on_state(e, None, int(a), np.float32(v))
-        orig_on_state(states, actions, values)
-
-    overs = []
-
-    def on_reward(rew, over):
-        overs.append(int(over.sum()))
-        rewards.extend(rew.cpu().numpy().tolist())
-        for e, (r, o) in enumerate(zip(rew.cpu().numpy(), over.cpu().numpy())):
-            mirror.on_message(e, float(r), bool(o))
-        return orig_on_reward(rew, over)
-    loop.buf.on_state, loop.buf.on_reward = on_state, on_reward
+    taps = LoopMirror(loop, O.SimulatorMasterMirror())
 
     loop.run(90)
     torch.cuda.synchronize()
-    assert loop.train_steps >= 4 and sum(overs) == 3 * E          # every env hit limit 25 thrice
+    assert loop.train_steps >= 4 and taps.episodes_over() == 3 * E      # every env hit limit 25 thrice
     sc = loop.last_scalars.cpu().numpy()
     assert np.all(np.isfinite(sc))
     assert not torch.equal(m.engine.params, p0)
-    want = [(k["action"], float(np.float32(R))) for k, R, _, _ in mirror.queue]
-    assert consumed == want and len(want) >= B * loop.train_steps
+    want = taps.queued()
+    assert taps.consumed == want and len(want) >= B * loop.train_steps
     assert int(env.game[:, 8].max()) == 15                        # t = 90 - 75
+    sampled = np.concatenate([a for a, _, _ in taps.drawn])
     assert 0 <= min(sampled) and max(sampled) < A and max(sampled) >= 4
-    assert min(rewards) < 0
+    assert np.stack(taps.rewards).min() < 0
 
 
 def test_launcher_trains_on_boxing_and_writes_mean_score(tmp_path):

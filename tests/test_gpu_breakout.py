@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from breakout_policy import (EVENTS, history_push_numpy, make_row, player_from_row, trajectory)
+from loop_mirror import LoopMirror
 from oracle import ba3c_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -182,38 +183,16 @@ def test_actor_learner_on_breakout_feeds_the_reference_datapoints():
     loop = ActorLearner(tr, n_envs=E, batch_size=B, seed=1, env=env)
     assert loop.env is env and loop.hist.state[..., 3].any() and not loop.hist.state[..., :3].any()
 
-    mirror = O.SimulatorMasterMirror()
-    consumed = []
-    orig_put = loop.queue.put
-
-    def put(dps):
-        consumed.extend(zip(dps.action.cpu().numpy().tolist(), dps.R.cpu().numpy().tolist()))
-        orig_put(dps)
-    loop.queue.put = put
-    orig_on_state, orig_on_reward = loop.buf.on_state, loop.buf.on_reward
-
-    def on_state(states, actions, values):
-        for e, (a, v) in enumerate(zip(actions.cpu().numpy(), values.cpu().numpy())):
-            mirror.on_state(e, None, int(a), np.float32(v))
-        orig_on_state(states, actions, values)
-
-    overs = []
-
-    def on_reward(rew, over):
-        overs.append(int(over.sum()))
-        for e, (r, o) in enumerate(zip(rew.cpu().numpy(), over.cpu().numpy())):
-            mirror.on_message(e, float(r), bool(o))
-        return orig_on_reward(rew, over)
-    loop.buf.on_state, loop.buf.on_reward = on_state, on_reward
+    taps = LoopMirror(loop, O.SimulatorMasterMirror())
 
     loop.run(40)
     torch.cuda.synchronize()
-    assert loop.train_steps >= 4 and sum(overs) == E              # every env hit limit 25 once
+    assert loop.train_steps >= 4 and taps.episodes_over() == E      # every env hit limit 25 once
     sc = loop.last_scalars.cpu().numpy()
     assert np.all(np.isfinite(sc))
     assert not torch.equal(m.engine.params, p0)
-    want = [(k["action"], float(np.float32(R))) for k, R, _, _ in mirror.queue]
-    assert consumed == want and len(want) >= B * loop.train_steps
+    want = taps.queued()
+    assert taps.consumed == want and len(want) >= B * loop.train_steps
     assert int(env.game[:, 8].max()) == 15                        # t = 40 - 25
 
 

@@ -15,6 +15,7 @@ import torch
 
 from boxing_policy import history_push_numpy
 from duel_policy import ODD_ACTIONS, crafted_rows, hit_and_run_policy, noop_policy, trajectory
+from loop_mirror import LoopMirror
 from oracle import ba3c_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -179,40 +180,18 @@ def test_self_play_through_the_actor_learner_feeds_each_player_its_own_rewards()
     assert loop.env is env and loop.hist.state[..., 3].any() and not loop.hist.state[..., :3].any()
     assert torch.equal(loop.hist.state[..., 3], env.frames()[..., 0])
 
-    mirror = O.SimulatorMasterMirror()
-    consumed = []
-    orig_put = loop.queue.put
-
-    def put(dps):
-        consumed.extend(zip(dps.action.cpu().numpy().tolist(), dps.R.cpu().numpy().tolist()))
-        orig_put(dps)
-    loop.queue.put = put
-    orig_on_state, orig_on_reward = loop.buf.on_state, loop.buf.on_reward
-    rewards, overs = [], []
-
-    def on_state(states, actions, values):
-        for e, (a, v) in enumerate(zip(actions.cpu().numpy(), values.cpu().numpy())):
-            mirror.on_state(e, None, int(a), np.float32(v))
-        orig_on_state(states, actions, values)
-
-    def on_reward(rew, over):
-        r, o = rew.cpu().numpy(), over.cpu().numpy()
+    def zero_sum(r, o):
         assert (r[:G] == -r[G:]).all() and (o[:G] == o[G:]).all()  # zero-sum, one clock per game
-        rewards.append(r)
-        overs.append(int(o.sum()))
-        for e in range(E):                                         # player e's OWN rewards
-            mirror.on_message(e, float(r[e]), bool(o[e]))
-        return orig_on_reward(rew, over)
-    loop.buf.on_state, loop.buf.on_reward = on_state, on_reward
+    taps = LoopMirror(loop, O.SimulatorMasterMirror(), on_step=zero_sum)   # player e's OWN rewards
 
     loop.run(90)
     torch.cuda.synchronize()
-    assert loop.train_steps >= 4 and sum(overs) >= 3 * E          # limit 25: at least thrice each
+    assert loop.train_steps >= 4 and taps.episodes_over() >= 3 * E      # limit 25: at least thrice each
     assert np.all(np.isfinite(loop.last_scalars.cpu().numpy()))
     assert not torch.equal(m.engine.params, p0)
-    want = [(k["action"], float(np.float32(R))) for k, R, _, _ in mirror.queue]
-    assert consumed == want and len(want) >= B * loop.train_steps
-    assert np.abs(np.stack(rewards)).max() > 0                    # punches landed
+    want = taps.queued()
+    assert taps.consumed == want and len(want) >= B * loop.train_steps
+    assert np.abs(np.stack(taps.rewards)).max() > 0               # punches landed
 
 
 def test_match_is_won_by_the_better_script_from_either_side():

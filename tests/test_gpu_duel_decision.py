@@ -17,6 +17,7 @@ from boxing_policy import history_push_numpy
 from duel_decision import SKIPS, STARTS, assert_covered, trajectory
 from duel_policy import crafted_rows
 from duel_policy import trajectory as step_trajectory
+from loop_mirror import LoopMirror
 from oracle import ba3c_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -197,42 +198,22 @@ def test_self_play_with_frame_skip_and_drawn_starts_feeds_each_player_its_own_re
     loop = ActorLearner(tr, n_envs=E, batch_size=B, seed=1, env=env)
     assert loop.env is env and torch.equal(loop.hist.state[..., 3], env.frames()[..., 0])
 
-    mirror = O.SimulatorMasterMirror()
-    consumed = []
-    orig_put = loop.queue.put
+    gaps = []
 
-    def put(dps):
-        consumed.extend(zip(dps.action.cpu().numpy().tolist(), dps.R.cpu().numpy().tolist()))
-        orig_put(dps)
-    loop.queue.put = put
-    orig_on_state, orig_on_reward = loop.buf.on_state, loop.buf.on_reward
-    rewards, overs, gaps = [], [], []
-
-    def on_state(states, actions, values):
-        for e, (a, v) in enumerate(zip(actions.cpu().numpy(), values.cpu().numpy())):
-            mirror.on_state(e, None, int(a), np.float32(v))
-        orig_on_state(states, actions, values)
-
-    def on_reward(rew, over):
-        r, o = rew.cpu().numpy(), over.cpu().numpy()
+    def zero_sum(r, o):
         assert (r[:G] == -r[G:]).all() and (o[:G] == o[G:]).all()  # zero-sum, one clock per game
-        rewards.append(r)
-        overs.append(int(o.sum()))
         g = env.game.cpu().numpy()
         gaps.extend((g[o[:G], 2] - g[o[:G], 0]).tolist())          # the fresh rows: drawn
-        for e in range(E):                                         # player e's OWN rewards
-            mirror.on_message(e, float(r[e]), bool(o[e]))
-        return orig_on_reward(rew, over)
-    loop.buf.on_state, loop.buf.on_reward = on_state, on_reward
+    taps = LoopMirror(loop, O.SimulatorMasterMirror(), on_step=zero_sum)   # player e's OWN rewards
 
     loop.run(90)
     torch.cuda.synchronize()
-    assert loop.train_steps >= 4 and sum(overs) >= 3 * E          # limit 25, k >= 2: often
+    assert loop.train_steps >= 4 and taps.episodes_over() >= 3 * E      # limit 25, k >= 2: often
     assert np.all(np.isfinite(loop.last_scalars.cpu().numpy()))
     assert not torch.equal(m.engine.params, p0)
-    want = [(k["action"], float(np.float32(R))) for k, R, _, _ in mirror.queue]
-    assert consumed == want and len(want) >= B * loop.train_steps
-    assert np.abs(np.stack(rewards)).max() > 0                    # punches landed
+    want = taps.queued()
+    assert taps.consumed == want and len(want) >= B * loop.train_steps
+    assert np.abs(np.stack(taps.rewards)).max() > 0               # punches landed
     assert gaps and set(gaps) <= {8, 10, 12, 14} and len(set(gaps)) > 1
 
 

@@ -210,6 +210,7 @@ def test_gather_rows_beyond_65535(row_bytes):
 def test_actor_learner_feeds_the_lambda_datapoints():
     """As test_actor_learner_runs_and_feeds_the_reference_datapoints, at lambda = 0.95 and
     8-step rollouts: what the learner consumes is what the host master would have queued."""
+    from loop_mirror import LoopMirror
     from oracle import ba3c_oracle as O
 
     from ba3c_amd.actor_learner import ActorLearner
@@ -223,33 +224,14 @@ def test_actor_learner_feeds_the_lambda_datapoints():
     tr = Ba3cTrainer(TrainConfig(model=m, optimizer=AdamOptimizer(1e-3, 0.8, 0.75, 1e-8)))
     loop = ActorLearner(tr, n_envs=E, batch_size=B, seed=1, local_time_max=8, gae_lambda=0.95)
     assert (loop.buf.T, loop.buf.gae_lambda, loop.buf.gamma) == (9, 0.95, 0.99)
-    mirror = LambdaMasterMirror(8, 0.99, 0.95)
-    consumed = []
-    orig_put = loop.queue.put
-
-    def put(dps):
-        consumed.extend(zip(dps.action.cpu().numpy().tolist(), dps.R.cpu().numpy().tolist()))
-        orig_put(dps)
-    loop.queue.put = put
-    orig_on_state, orig_on_reward = loop.buf.on_state, loop.buf.on_reward
-
-    def on_state(states, actions, values):
-        for e, (a, v) in enumerate(zip(actions.cpu().numpy(), values.cpu().numpy())):
-            mirror.on_state(e, None, int(a), np.float32(v))
-        orig_on_state(states, actions, values)
-
-    def on_reward(rew, over):
-        for e, (r, o) in enumerate(zip(rew.cpu().numpy(), over.cpu().numpy())):
-            mirror.on_message(e, float(r), bool(o))
-        return orig_on_reward(rew, over)
-    loop.buf.on_state, loop.buf.on_reward = on_state, on_reward
+    taps = LoopMirror(loop, LambdaMasterMirror(8, 0.99, 0.95))
 
     loop.run(40)
     torch.cuda.synchronize()
     assert loop.train_steps >= 4
     assert np.all(np.isfinite(loop.last_scalars.cpu().numpy()))
-    want = [(k["action"], float(np.float32(R))) for k, R, _, _ in mirror.queue]
-    assert consumed == want and len(want) >= B * loop.train_steps
+    want = taps.queued()
+    assert taps.consumed == want and len(want) >= B * loop.train_steps
 
 
 def test_launcher_takes_the_three_flags(tmp_path, monkeypatch):

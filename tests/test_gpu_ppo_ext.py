@@ -255,31 +255,31 @@ def _loop(setting, iters=12):
 
 def test_loop_with_normalised_advantages_and_the_value_clip():
     loop, eng, p0, stored = _loop(ppo.Setting(0.2, K, M, norm_adv=True, vclip=0.2))
-    assert loop.train_steps == len(loop.pool_epochs) * K * M > 0
+    assert loop.train_steps == len(loop.pool_trainer.pool_epochs) * K * M > 0
     assert torch.isfinite(loop.last_scalars).all() and not torch.equal(eng.params, p0)
     assert torch.isfinite(eng.params).all() and eng.device_errors() == 0
     assert stored and all(bool((s[:, 3] == 0).all()) for s in stored)     # the pool's rows keep 0
-    mean, std = loop.last_adv_stats.tolist()
+    mean, std = loop.pool_trainer.last_adv_stats.tolist()
     assert np.isfinite(mean) and np.isfinite(std) and std >= 0.0
 
 
 def test_loop_stops_a_pool_after_one_epoch_at_a_tiny_target_kl():
     loop, eng, p0, _ = _loop(ppo.Setting(0.2, K, M, target_kl=1e-9))
-    pools = len(loop.pool_epochs)
-    print("epochs per pool %r\nepoch KLs %r" % (loop.pool_epochs, ["%.3e" % k for k in loop.epoch_kls]))
-    assert pools > 1 and loop.pool_epochs == [1.0] * pools and loop.train_steps == pools * M
+    pools = len(loop.pool_trainer.pool_epochs)
+    print("epochs per pool %r\nepoch KLs %r" % (loop.pool_trainer.pool_epochs, ["%.3e" % k for k in loop.pool_trainer.epoch_kls]))
+    assert pools > 1 and loop.pool_trainer.pool_epochs == [1.0] * pools and loop.train_steps == pools * M
 
 
 def test_loop_runs_every_epoch_at_a_huge_target_kl():
     loop, eng, p0, _ = _loop(ppo.Setting(0.2, K, M, target_kl=1e9))
-    pools = len(loop.pool_epochs)
-    assert pools > 1 and loop.pool_epochs == [float(K)] * pools and loop.train_steps == pools * K * M
+    pools = len(loop.pool_trainer.pool_epochs)
+    assert pools > 1 and loop.pool_trainer.pool_epochs == [float(K)] * pools and loop.train_steps == pools * K * M
 
 
 def test_loop_with_the_new_fields_at_their_defaults_is_the_loop_it_was():
     a = _loop(ppo.Setting(0.2, K, M))
     b = _loop(ppo.Setting(0.2, K, M, False, 0.0, 0.0))
-    assert a[0].train_steps == b[0].train_steps > 0 and a[0].last_adv_stats is None
+    assert a[0].train_steps == b[0].train_steps > 0 and a[0].pool_trainer.last_adv_stats is None
     assert torch.equal(a[1].params, b[1].params) and not torch.equal(a[1].params, a[2])
 
 
