@@ -38,10 +38,10 @@ class Ba3cOptParams(ctypes.Structure):
 
 
 _lib = None
-# roofline-accounting queries and the PPO entry points an alternative A/B build (BA3C_LIB) may
-# predate
+# roofline-accounting queries, the PPO entry points and the episode log an alternative A/B build
+# (BA3C_LIB) may predate
 AB_OPTIONAL = {"ba3c_kernel_merged", "ba3c_probe_every", "ba3c_train_grads_ppo", "ba3c_sample_logp",
-               "ba3c_train_grads_ppo_ext", "ba3c_ppo_norm_adv"}
+               "ba3c_train_grads_ppo_ext", "ba3c_ppo_norm_adv", "ba3c_episode_stats"}
 PPO_ADV_FROM_ROW = 1       # BA3C_PPO_ADV_FROM_ROW
 
 
@@ -107,6 +107,7 @@ def load():
                                       P, P, P, P, P]),
         "ba3c_gather_rows": (i32, [P, P, P, i32, i64, P]),
         "ba3c_history_push": (i32, [P, P, P, P, i32, i32, i32, i32]),
+        "ba3c_episode_stats": (i32, [P, P, P, i32, P, P, P, P, P, i32, P]),
         "ba3c_breakout_step": (i32, [P, P, P, i32, i32, P, P, P, P, P]),
         "ba3c_breakout_render": (i32, [P, P, i32, P, P]),
         "ba3c_boxing_step": (i32, [P, P, P, i32, i32, P, P, P, P, P]),

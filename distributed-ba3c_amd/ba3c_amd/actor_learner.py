@@ -157,7 +157,7 @@ class ActorLearner(object):
 
     def __init__(self, trainer, n_envs, batch_size, seed=0, rs=None, on_train_step=None,
                  dummy_predictor=False, env=None, local_time_max=LOCAL_TIME_MAX, gamma=GAMMA,
-                 gae_lambda=1.0, ppo=None, stop_at=None):
+                 gae_lambda=1.0, ppo=None, stop_at=None, episodes=None):
         """trainer: the Ba3cTrainer that takes the learner steps.
         n_envs, batch_size: simulators stepped per iteration, datapoints per learner step.
         seed, rs: of the synthetic environment and the PPO pool; the host stream of the action
@@ -172,7 +172,11 @@ class ActorLearner(object):
         ppo: None is the A3C loop (`queue`, a BatchTrainer's); a ppo.Setting records each action's
           log-probability under the policy that drew it and feeds a PoolTrainer (`pool_trainer`,
           whose Pool is `pool`).
-        stop_at: the PoolTrainer's; unused without ppo."""
+        stop_at: the PoolTrainer's; unused without ppo.
+        episodes: an episodes.EpisodeLog over the n_envs simulators (for a two-player vector its
+          E = 2G players, player p of game g at p * G + g): one more launch per iteration, right
+          after the environment step, logs the episodes that step finished; no host read.  None:
+          no call differs."""
         eng = trainer.engine
         assert eng.channels == 4, "synthetic loop is grayscale x FRAME_HISTORY=4"
         self.trainer = trainer
@@ -201,6 +205,9 @@ class ActorLearner(object):
         self.last_scalars = None
         self.on_train_step = on_train_step
         self.dummy_predictor = dummy_predictor
+        if episodes is not None and episodes.E != n_envs:
+            raise ValueError("the episode log is of %d simulators, the loop of %d" % (episodes.E, n_envs))
+        self.episodes = episodes
 
     def _predict(self, state):
         """(sampled_from, recorded, value): the distribution the action is drawn from, the one
@@ -236,6 +243,8 @@ class ActorLearner(object):
         else:
             frames, reward, over = self.env.step(actions)
             self.hist.push(frames, over)
+        if self.episodes is not None:
+            self.episodes.update(reward, over)
         self.consumer.consume(self.buf.on_reward(reward, over))
         self.steps += 1
         if int(flag.item()) & 1:

@@ -121,6 +121,11 @@ def build_parser():
     p.add_argument("--ppo_target_kl", type=float, default=0.0,
                    help="abandon a pool's remaining epochs once an epoch's mean KL estimate "
                         "(ppo.stop_kl) exceeds this, >= 0; 0: off; needs --ppo_clip (single replica)")
+    p.add_argument("--online_score", type=int, default=0,
+                   help="log the episodes the training simulators finish, on the device, and write "
+                        "their mean per N consecutive episodes to the online_score channel (the "
+                        "reference: 10) with train_score_mean / train_score_max / "
+                        "train_episode_length / train_episodes per flush; 0: off; not with --dummy")
     p.add_argument("--dummy", type=int, default=0)
     p.add_argument("--dummy_predictor", type=int, default=0)
     p.add_argument("--models_dir", default="models")
@@ -157,7 +162,8 @@ def resolve(args, duel_tool=False):
     --ppo_clip > 0 (default 4 each); the pool's --ppo_minibatches x --batch_size states at most
     16 GiB; not with --dummy (no simulators, nothing to replay).  --ppo_norm_adv, --ppo_vclip
     (>= 0 and finite, 0: off) and --ppo_target_kl (the same) only with --ppo_clip > 0.  args.ppo
-    is the run's ppo.Setting, or None when off; it applies to every -e and to --self_play."""
+    is the run's ppo.Setting, or None when off; it applies to every -e and to --self_play.
+    --online_score >= 0 (0: off), for every -e and --self_play; not with --dummy (no simulators)."""
     if args.replace_with_conv is None:
         args.replace_with_conv = not args.use_normal_fc
     if args.adam_debug:
@@ -231,6 +237,11 @@ def resolve(args, duel_tool=False):
             raise SystemExit("--%s needs --ppo_clip > 0" % name)
     if args.ppo_norm_adv and not on:
         raise SystemExit("--ppo_norm_adv needs --ppo_clip > 0")
+    if args.online_score < 0:
+        raise SystemExit("--online_score %d: episodes per online_score row, must be >= 0 (0: off)"
+                         % args.online_score)
+    if args.online_score and args.dummy:
+        raise SystemExit("--online_score logs the simulators' episodes: it cannot go with --dummy")
     args.ppo = None
     if on:
         if args.dummy:

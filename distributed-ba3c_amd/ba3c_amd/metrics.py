@@ -7,7 +7,8 @@ max_logit), ('other', active_relus, dp_per_s) and ('delays', (mean, max, min)); 
 CsvChannels sink replaces the Neptune metrics server's _dump_to_channels
 (neptune_mp_server.py:169-233) writing one `<channel>.csv` ("x,y" rows, x = hours since start)
 per channel as utils/neptune_utils.py:38-57 does.  StepMetrics is the launcher's per-step
-callback in front of both, PpoMetrics its PPO channels.
+callback in front of both, PpoMetrics its PPO channels; the channels of the training simulators'
+episodes (`online_score`, the reference's ('online', ...) message) are episodes.EpisodeMetrics'.
 """
 import os
 import time
@@ -198,10 +199,11 @@ class PpoMetrics(object):
 class StepMetrics(object):
     """DebugLogCallback over device-resident step scalars: each learner step's 8 scalars are
     kept on the GPU and fetched once per `every` (--send_debug_every) steps (no per-step host
-    sync).  ppo: a PpoMetrics fed and flushed along (None: off)."""
+    sync).  ppo: a PpoMetrics fed and flushed along (None: off).  episodes: an
+    episodes.EpisodeMetrics flushed after the fetch, when the host has synchronised (None: off)."""
 
-    def __init__(self, trainer, batch_size, every, client, ppo=None):
-        self.trainer, self.B, self.ppo = trainer, batch_size, ppo
+    def __init__(self, trainer, batch_size, every, client, ppo=None, episodes=None):
+        self.trainer, self.B, self.ppo, self.episodes = trainer, batch_size, ppo, episodes
         self.every = max(1, int(every))
         self.cb = DebugLogCallback(client, worker_id=0, nr_send=self.every) if client else None
         self.pending = []
@@ -237,4 +239,6 @@ class StepMetrics(object):
         self.pending = []
         if self.ppo is not None:
             self.ppo.flush_steps()
+        if self.episodes is not None:
+            self.episodes.flush()
         self.t0 = time.time()

@@ -13,6 +13,7 @@
 - `--local_time_max` / `--gamma` / `--gae_lambda`: the returns' rollout length, discount and GAE
   lambda (ba3c_amd.returns).
 - `--ppo_clip` and the other `--ppo_*`: the clipped-surrogate loss over replayed pools (ba3c_amd.ppo).
+- `--online_score N`: the training simulators' own episodes, logged on the device (ba3c_amd.episodes).
 - `--nr_eval N`: the Evaluator callback every --steps_per_epoch steps.
 - `--send_debug_every`, `--experiment_dir`: DebugLogCallback's metrics channels (ba3c_amd.metrics).
 - `--save_every`, `--models_dir`, `--load`: PeriodicPerStepCallback(ModelSaver) (:608-630) and
@@ -146,9 +147,12 @@ def _run(args, rank, world):
 
     max_steps = args.max_steps or args.steps_per_epoch * args.max_epoch
     t0 = time.time()
-    al = None
+    al = log = None
     if not args.dummy:
         env = None
+        if args.online_score:
+            from .episodes import EpisodeLog, EpisodeMetrics
+            log = EpisodeLog(args.simulator_procs, device=trainer.engine.device)
         if args.self_play:
             # --simulator_procs players in half as many two-player games; both sides learn
             from .duel import BoxingDuelDecisionVec, start_from_gap
@@ -163,10 +167,11 @@ def _run(args, rank, world):
                           seed=rank, rs=np.random.RandomState(rank), on_train_step=on_step,
                           dummy_predictor=bool(args.dummy_predictor), env=env,
                           local_time_max=args.local_time_max, gamma=args.gamma,
-                          gae_lambda=args.gae_lambda, ppo=args.ppo, stop_at=max_steps)
+                          gae_lambda=args.gae_lambda, ppo=args.ppo, stop_at=max_steps, episodes=log)
     pool_trainer = al.pool_trainer if al is not None else None
     metrics = StepMetrics(trainer, args.batch_size, args.send_debug_every, client,
-                          ppo=PpoMetrics(args.ppo.clip, pool_trainer, client) if pool_trainer else None)
+                          ppo=PpoMetrics(args.ppo.clip, pool_trainer, client) if pool_trainer else None,
+                          episodes=EpisodeMetrics(log, args.online_score, client) if log is not None else None)
     if al is None:
         # --dummy 1: a constant synthetic batch, no simulators (train/multigpu.py:70-75)
         dev = trainer.engine.device
@@ -183,6 +188,8 @@ def _run(args, rank, world):
             al.iterate()
         sim_steps = al.steps
     metrics.flush()
+    if metrics.episodes is not None:
+        metrics.episodes.flush()                              # what finished after the last fetch
     torch.cuda.synchronize()
     wall = time.time() - t0
     if client is not None:
@@ -193,6 +200,8 @@ def _run(args, rank, world):
            "last": metrics.last}
     if args.ppo is not None:
         out["ppo"] = dict(args.ppo._asdict(), **(metrics.last_ppo or {}))
+    if metrics.episodes is not None:
+        out["episodes"] = metrics.episodes.as_dict()
     if evaluator is not None:
         out["eval"] = evaluator.history
     if rank == 0:

@@ -26,6 +26,7 @@
 #include "ba3c_conv3.h"
 #include "ba3c_duel.h"
 #include "ba3c_envview.h"
+#include "ba3c_episodes.h"
 #include "ba3c_gemm6.h"
 #include "ba3c_launch.h"
 #include "ba3c_multi.h"
@@ -1830,6 +1831,25 @@ int ba3c_history_push(void* stream, const uint8_t* frame, uint8_t* state, const 
   HistoryArgs a{frame, state, is_over, n_envs, pixels, hist_len, channels};
   const int groups = (pixels + 3) / 4;
   hipLaunchKernelGGL(history_push_kernel, dim3((groups + 255) / 256, n_envs), dim3(256), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return BA3C_OK;
+}
+
+int ba3c_episode_stats(void* stream, const double* reward, const uint8_t* over, int32_t n_envs,
+                       double* ret, int32_t* len, double* log_score, int32_t* log_len,
+                       int32_t* log_env, int32_t cap, int64_t* head) {
+  if (!reward || !over || !ret || !len || !log_score || !log_len || !log_env || !head)
+    return fail(BA3C_ERR_INVALID, "null pointer (every buffer of the episode log is required)");
+  if (n_envs < 1) return fail(BA3C_ERR_INVALID, "n_envs must be >= 1");
+  if (cap < n_envs)
+    return fail(BA3C_ERR_INVALID, "cap must be >= the simulators: one launch must not overwrite its own entries");
+  auto off = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
+  if (off(reward, 8) || off(ret, 8) || off(log_score, 8) || off(head, 8) || off(len, 4) || off(log_len, 4) ||
+      off(log_env, 4))
+    return fail(BA3C_ERR_INVALID,
+                "reward / ret / log_score / head must be 8-byte aligned, len / log_len / log_env 4-byte");
+  const EpisodeArgs a{reward, over, n_envs, ret, len, log_score, log_len, log_env, cap, head};
+  hipLaunchKernelGGL(episode_stats_kernel, dim3(1), dim3(kEpisodeThreads), 0, static_cast<hipStream_t>(stream), a);
   HIP_TRY(hipGetLastError());
   return BA3C_OK;
 }

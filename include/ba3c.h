@@ -381,6 +381,25 @@ int ba3c_gather_rows(void* stream, const void* rows, const int32_t* idx, int32_t
 int ba3c_history_push(void* stream, const uint8_t* frame, uint8_t* state, const uint8_t* is_over,
                       int32_t n_envs, int32_t pixels, int32_t hist_len, int32_t channels);
 
+/* The episodes the training simulators finish (MySimulatorMaster's self.stats[ident] fed to
+ * self.games at every episode end, OpenAIGym/train.py:394-412), for n_envs simulators in one
+ * launch; ba3c_amd/episodes.py (update_numpy) is the bit-exact statement.  For every e:
+ *   ret[e] += reward[e] (float64, one rounding; the raw, unclipped reward);  len[e] += 1
+ *   where over[e]: ring slot (*head + k) % cap, k = the number of e' < e with over[e'] in this
+ *     launch, receives log_score = ret[e], log_len = len[e], log_env = e; then ret[e] = +0.0
+ *     and len[e] = 0
+ *   *head += the number of e with over[e]
+ * so one launch's episodes are logged in increasing e (a scan over the flags, no atomics: two
+ * runs log identical rings).  *head (device int64, episodes ever logged) is read and written by
+ * the device only; the host reads it when it drains the ring.  Refused before any launch, in
+ * this order (BA3C_ERR_INVALID): a null pointer (all are required); n_envs < 1; cap < n_envs
+ * (one launch must never overwrite its own entries); reward / ret / log_score / head not
+ * 8-byte or len / log_len / log_env not 4-byte aligned.  Never synchronises, never allocates.
+ * One workgroup: latency-bound (21 bytes per simulator). */
+int ba3c_episode_stats(void* stream, const double* reward, const uint8_t* over, int32_t n_envs,
+                       double* ret, int32_t* len, double* log_score, int32_t* log_len,
+                       int32_t* log_env, int32_t cap, int64_t* head);
+
 /* ---- GridBreakout: an on-device game (stands in for RL/gymenv.py + the 84x84 resize) ----- */
 
 /* A small integer-only Breakout for n_envs simulators; ba3c_amd/breakout.py states the rules

@@ -32,12 +32,17 @@ method (medians of event-bracketed batches of steps, alternating), and ms per
 --ppo_norm_adv and / or --ppo_vclip EPS the extended step (the normalisation launch and
 `ba3c_train_grads_ppo_ext`) and the normalisation launch alone are timed in the same alternation,
 and the loop once more with those settings.
+With --episodes also the episode log of the training simulators (`ba3c_episode_stats`,
+ba3c_amd.episodes) alone at 100, 4096 and 65536 simulators (one flag in a hundred set), by the same
+medians of event-bracketed batches, and ms per `ActorLearner.iterate` on GridBreakout at 100 and
+4096 simulators without and with a log, alternating in the same call; --episodes_only skips the
+environment tables.
 Prints one JSON line.
 
     python scripts/env_throughput.py [--game boxing] [--envs 8192 64] [--iters 200] [--random 20]
                                      [--frame_skip 2-4] [--sticky 0.25] [--view 1 3] [--duel]
                                      [--duel_start 8-14] [--duel_only] [--returns] [--ppo] [--ppo_only]
-                                     [--ppo_norm_adv] [--ppo_vclip 0.2]
+                                     [--ppo_norm_adv] [--ppo_vclip 0.2] [--episodes] [--episodes_only]
 """
 import argparse
 import json
@@ -286,8 +291,77 @@ def iterate_table(settings, iters=420, warmup=42, E=100):
     return out
 
 
+EPISODE_SIZES = [100, 4096, 65536]
+# (simulators, batch size, timed iterations): windows of about two seconds each
+EPISODE_LOOPS = [(100, 32, 2000), (4096, 1024, 300)]
+
+
+def episodes_table(repeats):
+    """--episodes: µs per `ba3c_episode_stats` launch, the entry point alone on buffers built once;
+    one flag in a hundred is set, so the ring takes entries at every launch."""
+    import ctypes
+
+    from ba3c_amd import _lib
+    from ba3c_amd.episodes import EpisodeLog
+    lib = _lib.load()
+    P = lambda t: ctypes.c_void_p(t.data_ptr())
+    out = {}
+    for E in EPISODE_SIZES:
+        g = torch.Generator(device="cuda").manual_seed(E)
+        reward = torch.randint(-2, 3, (E,), generator=g, device="cuda").to(torch.float64)
+        over = (torch.arange(E, device="cuda") % 100 == 7).to(torch.uint8)
+        log = EpisodeLog(E)
+        a = [ctypes.c_void_p(torch.cuda.current_stream().cuda_stream), P(reward), P(over), E, P(log.ret),
+             P(log.len), P(log.log_score), P(log.log_len), P(log.log_env), log.cap, P(log.head)]
+        fn = lambda: lib.ba3c_episode_stats(*a)
+        _lib.check(fn())
+        us = [timed_median(fn) for _ in range(repeats)]
+        out[str(E)] = {"us": [round(v, 2) for v in us], "flags_set": int(over.sum().item()),
+                       "bytes": 21 * E, "cap": log.cap}
+    return out
+
+
+def episodes_iterate_table(repeats=3, warmup=42):
+    """--episodes: ms per ActorLearner.iterate on GridBreakout (F = 128, S = 4, Adam) without and
+    with an EpisodeLog, fresh loops of the same seed, alternating; a host clock around the
+    iterations ending in a device synchronise, as iterate_table."""
+    import time
+
+    from ba3c_amd.actor_learner import ActorLearner
+    from ba3c_amd.breakout import BreakoutVec
+    from ba3c_amd.episodes import EpisodeLog
+    from ba3c_amd.model import Model
+    from ba3c_amd.optimizer import AdamOptimizer
+    from ba3c_amd.trainer import Ba3cTrainer, TrainConfig
+    out = {}
+    for E, B, iters in EPISODE_LOOPS:
+        row = {"batch_size": B, "iterations": iters, "without_ms": [], "with_ms": []}
+        for _ in range(repeats):
+            for key in ("without_ms", "with_ms"):
+                m = Model(num_actions=4, fc_neurons=128, fc_splits=4, batch_size=B, max_batch=max(B, E), seed=0)
+                tr = Ba3cTrainer(TrainConfig(model=m, optimizer=AdamOptimizer(1e-3, 0.8, 0.75, 1e-8)))
+                log = EpisodeLog(E) if key == "with_ms" else None
+                al = ActorLearner(tr, n_envs=E, batch_size=B, seed=0, env=BreakoutVec(E, seed=0), episodes=log)
+                al.run(warmup)
+                torch.cuda.synchronize()
+                t0 = time.time()
+                al.run(iters)
+                torch.cuda.synchronize()
+                row[key].append(round((time.time() - t0) * 1e3 / iters, 4))
+                if log is not None:
+                    row["episodes_logged"] = int(log.head.item())
+                del al, tr, m
+        row["with_over_without"] = round(min(row["with_ms"]) / min(row["without_ms"]), 4)
+        out[str(E)] = row
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--episodes", action="store_true",
+                    help="also time ba3c_episode_stats alone and one ActorLearner iteration on "
+                         "GridBreakout without and with an episode log")
+    ap.add_argument("--episodes_only", action="store_true", help="--episodes: skip the environment tables")
     ap.add_argument("--returns", action="store_true",
                     help="also time ba3c_lambda_returns next to ba3c_nstep_returns, and one "
                          "ActorLearner iteration with 5-step n-step and 20-step GAE(0.95) returns")
@@ -344,7 +418,8 @@ def main(argv=None):
         out["fill_GBps"] = round(fill.numel() / us / 1e3, 1)
         del fill
 
-    for E in ([] if (args.duel and args.duel_only) or (args.ppo and args.ppo_only) else args.envs):
+    for E in ([] if (args.duel and args.duel_only) or (args.ppo and args.ppo_only)
+              or (args.episodes and args.episodes_only) else args.envs):
         g = torch.Generator(device="cuda").manual_seed(0)
         actions = torch.randint(0, A, (E,), generator=g, device="cuda")
         env, hist = Vec(E, seed=0), FrameHistory(E, 4, 1)
@@ -417,6 +492,9 @@ def main(argv=None):
         if args.ppo_norm_adv or args.ppo_vclip:
             legs.append((5, 1.0, on._replace(norm_adv=args.ppo_norm_adv, vclip=args.ppo_vclip)))
         out["ppo_iterate"] = iterate_table(legs * 2)
+    if args.episodes:
+        out["episode_stats"] = episodes_table(args.repeats)
+        out["episodes_iterate"] = episodes_iterate_table()
     if args.random:
         from ba3c_amd.evaluate import eval_with_envs, uniform_policy
         from ba3c_amd.model import Model
