@@ -38,10 +38,11 @@ class Ba3cOptParams(ctypes.Structure):
 
 
 _lib = None
-# roofline-accounting queries, the PPO entry points and the episode log an alternative A/B build
-# (BA3C_LIB) may predate
+# roofline-accounting queries, the PPO entry points, the episode log and the global-norm clip an
+# alternative A/B build (BA3C_LIB) may predate
 AB_OPTIONAL = {"ba3c_kernel_merged", "ba3c_probe_every", "ba3c_train_grads_ppo", "ba3c_sample_logp",
-               "ba3c_train_grads_ppo_ext", "ba3c_ppo_norm_adv", "ba3c_episode_stats"}
+               "ba3c_train_grads_ppo_ext", "ba3c_ppo_norm_adv", "ba3c_episode_stats",
+               "ba3c_global_clip_scratch", "ba3c_clip_grads_global"}
 PPO_ADV_FROM_ROW = 1       # BA3C_PPO_ADV_FROM_ROW
 
 
@@ -75,6 +76,8 @@ def load():
         "ba3c_train_grads": (i32, [P, P, P, P, P, P, i32, f32, P, P, P]),
         "ba3c_clip_grads": (i32, [P, P, P, P]),
         "ba3c_clip_grads_range": (i32, [P, P, P, P, i32, i32]),
+        "ba3c_global_clip_scratch": (i64, [P]),
+        "ba3c_clip_grads_global": (i32, [P, P, P, ctypes.c_double, P, i64]),
         "ba3c_train_grads_phase": (i32, [P, P, P, P, P, P, i32, f32, P, P, P, i32]),
         "ba3c_train_grads_ppo": (i32, [P, P, P, P, P, P, i32, f32, f32, P, P, P, P, i32]),
         "ba3c_train_grads_ppo_ext": (i32, [P, P, P, P, P, P, i32, f32, f32, f32, ctypes.c_uint32, P, P,

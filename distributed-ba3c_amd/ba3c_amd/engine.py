@@ -248,6 +248,20 @@ class Ba3cEngine(object):
         _lib.check(self.lib.ba3c_clip_grads(self.h, _stream(), _ptr(grads),
                                             _ptr(self._workspace(True))))
 
+    _gclip = None      # clip_grads_global's scratch (float64 [nchunks + 2]), on first use
+
+    def clip_grads_global(self, max_norm, grads=None):
+        """The clip of the whole gradient's norm, in place (ba3c_clip_grads_global; the rule:
+        ba3c_amd.gradclip).  Returns the device view of {norm, f} (float64 [2]), which the next
+        call overwrites."""
+        grads = self.grads if grads is None else grads
+        if self._gclip is None:
+            n = int(self.lib.ba3c_global_clip_scratch(self.h))
+            self._gclip = torch.zeros(n, dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.ba3c_clip_grads_global(self.h, _stream(), _ptr(grads), float(max_norm),
+                                                   _ptr(self._gclip), self._gclip.numel()))
+        return self._gclip[-2:]
+
     def apply_update(self, opt, slot0, slot1, hp, grad_scale=1.0, fuse_clip=False, grads=None,
                      dev_powers=None):
         """One optimizer apply; dev_powers (float32 device tensor [2]) keeps Adam's

@@ -3,8 +3,9 @@ OpenAIGym/parse.py:9-70 (worker flags), reduced to what the learner/predictor ho
 its single-node launcher (`python -m ba3c_amd.train`) consume.  Slurm / TF-server / Neptune
 flags are accepted and ignored."""
 import argparse
+import math
 
-from . import duel, frameskip, ppo
+from . import duel, frameskip, ppo, schedule
 from .boxing import BoxingVec
 from .breakout import BreakoutVec
 
@@ -15,6 +16,7 @@ GAMES = {GRID_BREAKOUT: (BreakoutVec, 4, "breakout"), GRID_BOXING: (BoxingVec, 1
 MAX_LOCAL_TIME = 128                  # ba3c_lambda_returns holds local_time_max + 1 <= 129 ring slots
 STATE_BYTES = 84 * 84 * 4             # one stacked state of the rollout ring
 MAX_RING_BYTES = 16 * 2 ** 30         # simulator_procs x (local_time_max + 1) states
+DEFAULT_ENTROPY_BETA = 0.01           # Model.entropy_beta (train.py:296-297)
 
 
 def string_to_bool(s):        # parse.py:5-6
@@ -126,6 +128,20 @@ def build_parser():
                         "their mean per N consecutive episodes to the online_score channel (the "
                         "reference: 10) with train_score_mean / train_score_max / "
                         "train_episode_length / train_episodes per flush; 0: off; not with --dummy")
+    p.add_argument("--max_grad_norm", type=float, default=0.0,
+                   help="clip the whole gradient's norm to this (ba3c_amd.gradclip; PPO codebases: "
+                        "0.5) in place of the reference's per-tensor clip_by_average_norm(g, 0.1); "
+                        "finite and > 0; 0: off")
+    p.add_argument("--entropy_beta", type=float, default=None,
+                   help="the entropy coefficient (default %g, train.py:296), finite and >= 0"
+                        % DEFAULT_ENTROPY_BETA)
+    p.add_argument("--lr_schedule", default=None, metavar="SPEC",
+                   help="the learning rate over the run, from --lr (ba3c_amd.schedule): const, "
+                        "linear:END (reached at the run's last step) or steps:E1=V1,E2=V2,... (Vk "
+                        "from epoch Ek on; the reference's: steps:20=0.0005,60=0.0001)")
+    p.add_argument("--entropy_schedule", default=None, metavar="SPEC",
+                   help="the entropy coefficient over the run, from --entropy_beta, in "
+                        "--lr_schedule's forms (the reference's: steps:40=0.005,80=0.001)")
     p.add_argument("--dummy", type=int, default=0)
     p.add_argument("--dummy_predictor", type=int, default=0)
     p.add_argument("--models_dir", default="models")
@@ -163,7 +179,14 @@ def resolve(args, duel_tool=False):
     16 GiB; not with --dummy (no simulators, nothing to replay).  --ppo_norm_adv, --ppo_vclip
     (>= 0 and finite, 0: off) and --ppo_target_kl (the same) only with --ppo_clip > 0.  args.ppo
     is the run's ppo.Setting, or None when off; it applies to every -e and to --self_play.
-    --online_score >= 0 (0: off), for every -e and --self_play; not with --dummy (no simulators)."""
+    --online_score >= 0 (0: off), for every -e and --self_play; not with --dummy (no simulators).
+    --max_grad_norm finite and >= 0 (0: off; args.max_grad_norm is then None); --entropy_beta finite
+    and >= 0; --lr_schedule / --entropy_schedule in ba3c_amd.schedule's forms with finite values, a
+    learning rate > 0 (but linear:0) and a coefficient >= 0; linear needs the run's step count
+    (--max_steps, or --steps_per_epoch x --max_epoch) >= 1.  args.schedules is the trainer's
+    {"learning_rate": fn, "entropy_beta": fn} when either schedule was given, else None;
+    args.log_schedule whether --entropy_beta or a schedule was given (the learning_rate and
+    entropy_beta channels are then written).  --schedule_hyper stays accepted and ignored."""
     if args.replace_with_conv is None:
         args.replace_with_conv = not args.use_normal_fc
     if args.adam_debug:
@@ -242,6 +265,37 @@ def resolve(args, duel_tool=False):
                          % args.online_score)
     if args.online_score and args.dummy:
         raise SystemExit("--online_score logs the simulators' episodes: it cannot go with --dummy")
+    # written so that a NaN or an infinity fails
+    if not 0.0 <= args.max_grad_norm < float("inf"):
+        raise SystemExit("--max_grad_norm %r: must be finite and > 0 (0: off)" % args.max_grad_norm)
+    args.max_grad_norm = args.max_grad_norm or None
+    args.log_schedule = (args.entropy_beta is not None or args.lr_schedule is not None
+                         or args.entropy_schedule is not None)
+    if args.entropy_beta is None:
+        args.entropy_beta = DEFAULT_ENTROPY_BETA
+    if not 0.0 <= args.entropy_beta < float("inf"):
+        raise SystemExit("--entropy_beta %r: must be finite and >= 0" % args.entropy_beta)
+    if args.lr_schedule is not None and not (math.isfinite(args.lr) and args.lr > 0.0):
+        raise SystemExit("--lr_schedule starts from --lr %r: it must be finite and > 0" % args.lr)
+    run_steps = args.max_steps or args.steps_per_epoch * args.max_epoch     # as train._run
+    fns = {}
+    for flag, key, start in (("lr_schedule", "learning_rate", args.lr),
+                             ("entropy_schedule", "entropy_beta", args.entropy_beta)):
+        try:
+            fn = schedule.parse(getattr(args, flag), start, max_steps=run_steps,
+                                steps_per_epoch=args.steps_per_epoch)
+        except ValueError as e:
+            raise SystemExit("--%s: %s (linear needs --max_steps or --steps_per_epoch x "
+                             "--max_epoch >= 1)" % (flag, e))
+        for v in fn.values:
+            if key == "learning_rate" and not (v > 0.0 or (fn.kind == "linear" and v == 0.0)):
+                raise SystemExit("--%s %s: a learning rate must be > 0 (only linear:0 may end at 0)"
+                                 % (flag, getattr(args, flag)))
+            if key == "entropy_beta" and not v >= 0.0:
+                raise SystemExit("--%s %s: an entropy coefficient must be >= 0"
+                                 % (flag, getattr(args, flag)))
+        fns[key] = fn
+    args.schedules = fns if (args.lr_schedule is not None or args.entropy_schedule is not None) else None
     args.ppo = None
     if on:
         if args.dummy:

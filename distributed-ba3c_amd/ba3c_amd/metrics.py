@@ -9,6 +9,9 @@ CsvChannels sink replaces the Neptune metrics server's _dump_to_channels
 per channel as utils/neptune_utils.py:38-57 does.  StepMetrics is the launcher's per-step
 callback in front of both, PpoMetrics its PPO channels; the channels of the training simulators'
 episodes (`online_score`, the reference's ('online', ...) message) are episodes.EpisodeMetrics'.
+ScheduleMetrics sends the reference's ('schedule', learning_rate, entropy_beta) message
+(common.py:221-224, neptune_mp_server.py:204-206) and GradClipMetrics writes the global-norm clip's
+grad_norm / grad_clip_fraction channels.
 """
 import os
 import time
@@ -94,6 +97,9 @@ class CsvChannels(object):
             self._send("score_max", x, content[2])
         elif kind == "online":
             self._send("online_score", x, content[1])
+        elif kind == "schedule":
+            self._send("learning_rate", x, content[1])
+            self._send("entropy_beta", x, content[2])
 
     def close(self):
         for fd in self._fd.values():
@@ -196,14 +202,68 @@ class PpoMetrics(object):
             self.last_ppo["ppo_epochs_run"] = self.epochs_run
 
 
+class ScheduleMetrics(object):
+    """The learning_rate and entropy_beta channels: each step's values (host numbers, as the step
+    took them) are kept and one ('schedule', mean lr, mean beta) message is sent per flush, the
+    means over the flushed steps, as the reference averages them.  last: the last step's values."""
+
+    def __init__(self, client=None, worker_id=0):
+        self.client, self.worker_id = client, worker_id
+        self.values = []
+        self.last = None
+
+    def on_step(self, trainer):
+        self.values.append((float(trainer.optimizer.learning_rate), float(trainer.model.entropy_beta)))
+
+    def flush(self):
+        if not self.values:
+            return
+        v = np.asarray(self.values, np.float64)
+        self.values = []
+        self.last = {"learning_rate": float(v[-1, 0]), "entropy_beta": float(v[-1, 1])}
+        if self.client is not None:
+            self.client.send((self.worker_id, ("schedule", float(v[:, 0].mean()),
+                                               float(v[:, 1].mean()))))
+
+
+class GradClipMetrics(object):
+    """The channels of the global-norm clip (model_desc.ClipByGlobalNorm `proc`): each step's
+    {norm, f} is cloned on the device (no host read per step); a flush writes grad_norm, the mean
+    norm over the flushed steps, and grad_clip_fraction, the share of them with f < 1."""
+
+    def __init__(self, proc, client=None):
+        self.proc, self.client = proc, client
+        self.stats = []
+        self.last = None
+
+    def on_step(self, trainer):
+        if self.proc.last_stats is not None:
+            self.stats.append(self.proc.last_stats.clone())
+
+    def flush(self):
+        if not self.stats:
+            return
+        v = torch.stack(self.stats).cpu().numpy()
+        self.stats = []
+        self.last = {"max_norm": self.proc.max_norm, "grad_norm": float(v[:, 0].mean()),
+                     "clip_fraction": float((v[:, 1] < 1.0).mean())}
+        if self.client is not None:
+            self.client.write_scalar("grad_norm", self.last["grad_norm"])
+            self.client.write_scalar("grad_clip_fraction", self.last["clip_fraction"])
+
+
 class StepMetrics(object):
     """DebugLogCallback over device-resident step scalars: each learner step's 8 scalars are
     kept on the GPU and fetched once per `every` (--send_debug_every) steps (no per-step host
     sync).  ppo: a PpoMetrics fed and flushed along (None: off).  episodes: an
-    episodes.EpisodeMetrics flushed after the fetch, when the host has synchronised (None: off)."""
+    episodes.EpisodeMetrics flushed after the fetch, when the host has synchronised (None: off).
+    gradclip / schedule: a GradClipMetrics / ScheduleMetrics fed and flushed along (None: off)."""
 
-    def __init__(self, trainer, batch_size, every, client, ppo=None, episodes=None):
+    def __init__(self, trainer, batch_size, every, client, ppo=None, episodes=None, gradclip=None,
+                 schedule=None):
         self.trainer, self.B, self.ppo, self.episodes = trainer, batch_size, ppo, episodes
+        self.extra = [m for m in (gradclip, schedule) if m is not None]
+        self.gradclip, self.schedule = gradclip, schedule
         self.every = max(1, int(every))
         self.cb = DebugLogCallback(client, worker_id=0, nr_send=self.every) if client else None
         self.pending = []
@@ -218,6 +278,8 @@ class StepMetrics(object):
         self.pending.append(trainer.model.scalars.clone())
         if self.ppo is not None:
             self.ppo.on_step(trainer)
+        for m in self.extra:
+            m.on_step(trainer)
         if len(self.pending) >= self.every:
             self.flush()
 
@@ -239,6 +301,8 @@ class StepMetrics(object):
         self.pending = []
         if self.ppo is not None:
             self.ppo.flush_steps()
+        for m in self.extra:
+            m.flush()
         if self.episodes is not None:
             self.episodes.flush()
         self.t0 = time.time()

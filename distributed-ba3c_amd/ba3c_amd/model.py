@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from .engine import Ba3cEngine
-from .model_desc import (InputVar, MapGradient, ModelDesc, clip_by_average_norm,
+from .model_desc import (ClipByGlobalNorm, InputVar, MapGradient, ModelDesc, clip_by_average_norm,
                          get_current_tower_context)
 
 IMAGE_SIZE = (84, 84)     # train.py:92
@@ -23,11 +23,13 @@ GAMMA = 0.99              # train.py:94
 class Model(ModelDesc):
     def __init__(self, num_actions, channels=1, fc_neurons=512, fc_splits=1,
                  replace_with_conv=True, ps=1, batch_size=128, max_batch=None, engine=None,
-                 seed=0, conv_init="normal", fc_init="uniform"):
+                 seed=0, conv_init="normal", fc_init="uniform", max_grad_norm=None):
         """channels: the reference's --channels (frames per history step; CHANNEL =
         FRAME_HISTORY*channels, train.py:95).  BASELINE's 84x84x4 input is channels=1.
         A new engine starts from the reference initialisers (--conv_init / --fc_init,
-        initializers.py) drawn with `seed`; a caller-supplied engine keeps its variables."""
+        initializers.py) drawn with `seed`; a caller-supplied engine keeps its variables.
+        max_grad_norm: the clip of the whole gradient's norm (ba3c_amd.gradclip) in place of the
+        reference's per-tensor clip_by_average_norm(g, 0.1); None: the reference's."""
         self.num_actions = num_actions
         self.channel = FRAME_HISTORY * channels
         self.batch_size = batch_size
@@ -46,6 +48,8 @@ class Model(ModelDesc):
         # sets it for the step's passes); None: the A3C loss
         self.ppo = None
         self.ratio = None             # the last PPO pass's per-sample rho (device, [B])
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self._global_clip = None if max_grad_norm is None else ClipByGlobalNorm(max_grad_norm)
 
     def _get_input_vars(self):
         return [InputVar(torch.uint8, (None,) + IMAGE_SIZE + (self.channel,), "state"),
@@ -80,6 +84,8 @@ class Model(ModelDesc):
         self.cost = sc[0]
 
     def get_gradient_processor(self):
+        if self._global_clip is not None:
+            return [self._global_clip]
         return [MapGradient(clip_by_average_norm(0.1))]
 
     def get_predict_func(self, input_names=("state",), output_names=("logitsT", "pred_value")):

@@ -90,6 +90,22 @@ def clip_by_average_norm(clip_norm=0.1):
     return ClipByAverageNorm(clip_norm)
 
 
+class ClipByGlobalNorm(GradientProcessor):
+    """The clip of the whole gradient's norm (ba3c_amd.gradclip; PPO codebases' max_grad_norm),
+    two HIP launches over the flat gradient buffer.  last_stats: the device view of the last
+    call's {norm, f} (float64 [2])."""
+
+    def __init__(self, max_norm):
+        max_norm = float(max_norm)
+        if not (max_norm > 0.0 and max_norm < float("inf")):     # written so that a NaN fails
+            raise ValueError("max_norm %r: must be finite and > 0" % max_norm)
+        self.max_norm = max_norm
+        self.last_stats = None
+
+    def process(self, engine):
+        self.last_stats = engine.clip_grads_global(self.max_norm)
+
+
 class MapGradient(GradientProcessor):
     """gradproc.py:34-67: apply `func` to every gradient whose variable name matches regex.
     ClipByAverageNorm over '.*' runs as one HIP kernel over the flat gradient buffer; any

@@ -13,6 +13,9 @@
 - `--local_time_max` / `--gamma` / `--gae_lambda`: the returns' rollout length, discount and GAE
   lambda (ba3c_amd.returns).
 - `--ppo_clip` and the other `--ppo_*`: the clipped-surrogate loss over replayed pools (ba3c_amd.ppo).
+- `--max_grad_norm`: the clip of the whole gradient's norm (ba3c_amd.gradclip) in place of the
+  reference's per-tensor clip; `--entropy_beta`, `--lr_schedule` / `--entropy_schedule`: the entropy
+  coefficient and the two schedules (ba3c_amd.schedule).
 - `--online_score N`: the training simulators' own episodes, logged on the device (ba3c_amd.episodes).
 - `--nr_eval N`: the Evaluator callback every --steps_per_epoch steps.
 - `--send_debug_every`, `--experiment_dir`: DebugLogCallback's metrics channels (ba3c_amd.metrics).
@@ -85,7 +88,9 @@ def build(args, rank=0, world=1, device=None):
     mc = model_config(args)
     seed = rank if args.seed is None else args.seed
     model = Model(conv_init=args.conv_init, fc_init=args.fc_init, seed=seed,
-                  max_batch=max(args.batch_size, args.simulator_procs), **mc)
+                  max_batch=max(args.batch_size, args.simulator_procs),
+                  max_grad_norm=args.max_grad_norm, **mc)
+    model.entropy_beta = args.entropy_beta
     oc = optimizer_config(args)
     opt = make_optimizer(oc["name"], oc["lr"], beta1=oc["beta1"], beta2=oc["beta2"],
                          epsilon=oc["epsilon"])
@@ -93,6 +98,7 @@ def build(args, rank=0, world=1, device=None):
         opt = SyncReplicasOptimizer(opt, replicas_to_aggregate=args.ngrads, total_num_replicas=world)
     trainer = Ba3cTrainer(TrainConfig(model=model, optimizer=opt, step_per_epoch=args.steps_per_epoch,
                                       max_epoch=args.max_epoch))
+    trainer.schedules = args.schedules
     if args.load:
         SaverRestore(args.load).init(trainer)
         if isinstance(opt, SyncReplicasOptimizer):
@@ -126,7 +132,7 @@ def main(argv=None):
 
 def _run(args, rank, world):
     from .actor_learner import ActorLearner
-    from .metrics import CsvChannels, PpoMetrics, StepMetrics
+    from .metrics import CsvChannels, GradClipMetrics, PpoMetrics, ScheduleMetrics, StepMetrics
     np.random.seed(rank)                                      # train.py:679
     model, trainer, savers = build(args, rank, world)
     client = CsvChannels(args.experiment_dir) if rank == 0 else None
@@ -171,7 +177,10 @@ def _run(args, rank, world):
     pool_trainer = al.pool_trainer if al is not None else None
     metrics = StepMetrics(trainer, args.batch_size, args.send_debug_every, client,
                           ppo=PpoMetrics(args.ppo.clip, pool_trainer, client) if pool_trainer else None,
-                          episodes=EpisodeMetrics(log, args.online_score, client) if log is not None else None)
+                          episodes=EpisodeMetrics(log, args.online_score, client) if log is not None else None,
+                          gradclip=(GradClipMetrics(model.get_gradient_processor()[0], client)
+                                    if args.max_grad_norm else None),
+                          schedule=ScheduleMetrics(client) if args.log_schedule else None)
     if al is None:
         # --dummy 1: a constant synthetic batch, no simulators (train/multigpu.py:70-75)
         dev = trainer.engine.device
@@ -202,6 +211,10 @@ def _run(args, rank, world):
         out["ppo"] = dict(args.ppo._asdict(), **(metrics.last_ppo or {}))
     if metrics.episodes is not None:
         out["episodes"] = metrics.episodes.as_dict()
+    if metrics.gradclip is not None:
+        out["grad_clip"] = metrics.gradclip.last or {"max_norm": args.max_grad_norm}
+    if metrics.schedule is not None:
+        out["schedule"] = metrics.schedule.last
     if evaluator is not None:
         out["eval"] = evaluator.history
     if rank == 0:

@@ -140,7 +140,27 @@ class Ba3cTrainer(object):
         finally:
             self.model.ppo = None
 
+    # None, or {"learning_rate": fn, "entropy_beta": fn} (either key may be missing): functions of
+    # the 0-based global_step before the step (ba3c_amd.schedule).  Both values are kernel
+    # arguments read again at every launch, so writing them here is the whole mechanism.
+    schedules = None
+
+    def apply_schedules(self):
+        """Write optimizer.learning_rate and model.entropy_beta from global_step (before the
+        step's first launch); returns what it wrote.  Nothing is touched with schedules None."""
+        if not self.schedules:
+            return {}
+        out = {}
+        fn = self.schedules.get("learning_rate")
+        if fn is not None:
+            out["learning_rate"] = self.optimizer.learning_rate = float(fn(self.global_step))
+        fn = self.schedules.get("entropy_beta")
+        if fn is not None:
+            out["entropy_beta"] = self.model.entropy_beta = float(fn(self.global_step))
+        return out
+
     def _train_step(self, state, action, futurereward):
+        self.apply_schedules()
         opt = self.optimizer
         # backup workers pick the first k ranks once the whole gradient is ready: flat path
         if (isinstance(opt, SyncReplicasOptimizer) and self._fused_clip and opt.bucketed
@@ -217,9 +237,15 @@ class Ba3cTrainer(object):
         beta powers move to the device so every replay uses the right bias correction.
         The `warmup` eager steps that precede the capture (allocator / library warm-up) are
         undone: parameters, optimizer slots and beta powers are restored afterwards, so
-        capturing does not train the model.  A PPO step (rows / clip) is refused."""
+        capturing does not train the model.  A PPO step (rows / clip) is refused, and so is a
+        non-constant schedule (`schedules`); a global-norm clip captures like any other launch."""
         if rows is not None or clip is not None or self.model.ppo is not None:
             raise ValueError("graph capture of a PPO step (rows / clip) is not supported")
+        for name, fn in (self.schedules or {}).items():
+            if fn is not None and not getattr(fn, "constant", False):
+                raise ValueError("the %s schedule is not constant: the learning rate and the "
+                                 "entropy coefficient are kernel arguments frozen into a "
+                                 "captured graph" % name)
         opt = self.optimizer
         if isinstance(opt, SyncReplicasOptimizer) and opt.backup_workers:
             raise ValueError("backup workers choose the aggregated ranks on the host each "

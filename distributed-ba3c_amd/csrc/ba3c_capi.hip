@@ -1617,6 +1617,31 @@ int ba3c_clip_grads(ba3c_handle* h, void* stream, float* grads, void* workspace)
   return BA3C_OK;
 }
 
+int64_t ba3c_global_clip_scratch(const ba3c_handle* h) { return h ? (int64_t)h->table.nchunks + 2 : 0; }
+
+int ba3c_clip_grads_global(ba3c_handle* h, void* stream, float* grads, double max_norm,
+                           double* scratch, int64_t scratch_doubles) {
+  if (!h) return fail(BA3C_ERR_INVALID, "null handle");
+  if (!check_ptr(grads)) return fail(BA3C_ERR_INVALID, "grads must be non-null and 16-byte aligned");
+  // written so that a NaN fails
+  if (!(max_norm > 0.0 && std::isfinite(max_norm)))
+    return fail(BA3C_ERR_INVALID, "max_norm must be finite and > 0");
+  if (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 7))
+    return fail(BA3C_ERR_INVALID, "scratch must be non-null and 8-byte aligned");
+  const int nc = h->table.nchunks;
+  if (scratch_doubles < (int64_t)nc + 2)
+    return fail(BA3C_ERR_INVALID, "scratch_doubles " + std::to_string((long long)scratch_doubles) +
+                                      " is below nchunks + 2 = " + std::to_string(nc + 2));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  {
+    ProbeScope ps(h, s, BA3C_K_CLIP);
+    hipLaunchKernelGGL(gnorm_partials_kernel, dim3(nc), dim3(256), 0, s, (const float*)grads, h->table, scratch);
+    hipLaunchKernelGGL(gnorm_scale_kernel, dim3(nc), dim3(256), 0, s, grads, h->table, scratch, max_norm);
+  }
+  HIP_TRY(hipGetLastError());
+  return BA3C_OK;
+}
+
 static int apply_update_impl(ba3c_handle* h, void* stream, int32_t opt, float* params,
                              const float* grads, float* slot0, float* slot1,
                              const ba3c_opt_params* hp, float* dev_powers, float grad_scale,

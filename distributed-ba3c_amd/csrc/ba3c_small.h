@@ -817,6 +817,82 @@ __global__ void __launch_bounds__(256) clip_kernel(float* __restrict__ g, const 
   for (int i = beg + threadIdx.x; i < end; i += 256) gt[i] = (gt[i] * 0.1f) * f;
 }
 
+// ---------------------------------------------------------------------------------------
+// Global-norm clip of the whole flat gradient (ba3c_amd/gradclip.py states the rule), two plain
+// launches of one workgroup per chunk: gnorm_partials_kernel leaves each chunk's float64 sum
+// of squares in scratch[chunk], gnorm_scale_kernel sums all of them in one fixed order in
+// every workgroup (so each holds the same norm and factor to the bit) and scales its chunk.
+// No in-launch waits, no atomics; the gaps between tensors are never read or written.
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ double block_sum_256_d(double v, double* red) {
+  v = wave_sum_d(v);
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) red[w] = v;
+  __syncthreads();
+  const double r = (red[0] + red[1]) + (red[2] + red[3]);
+  __syncthreads();
+  return r;
+}
+
+// the thread's UPD_CHUNK / 256 elements i = beg + tid + 256 j of the chunk, all loads issued
+// before any use (past the chunk's end: its last element again, then zeroed, as in update_kernel)
+__device__ __forceinline__ void chunk_load(const float* __restrict__ gt, int beg, int end,
+                                           float (&gv)[UPD_CHUNK / 256]) {
+  constexpr int PER = UPD_CHUNK / 256;
+#pragma unroll
+  for (int j = 0; j < PER; ++j) gv[j] = gt[min(beg + (int)threadIdx.x + 256 * j, end - 1)];
+#pragma unroll
+  for (int j = 0; j < PER; ++j)
+    if (beg + (int)threadIdx.x + 256 * j >= end) gv[j] = 0.f;
+}
+
+__global__ void __launch_bounds__(256) gnorm_partials_kernel(const float* __restrict__ g, const TensorTable tt,
+                                                             double* __restrict__ part) {
+  __shared__ double red[4];
+  constexpr int PER = UPD_CHUNK / 256;
+  const int b = blockIdx.x;
+  const int t = table_find(tt, b);
+  const int beg = (b - tt.chunk0[t]) * UPD_CHUNK;
+  const int end = min(tt.numel[t], beg + UPD_CHUNK);
+  float gv[PER];
+  chunk_load(g + tt.off[t], beg, end, gv);
+  // the product of two float32 values is exact in float64; increasing j (a zero adds nothing)
+  double s = 0.0;
+#pragma unroll
+  for (int j = 0; j < PER; ++j) s += (double)gv[j] * (double)gv[j];
+  s = block_sum_256_d(s, red);
+  if (threadIdx.x == 0) part[b] = s;
+}
+
+// scratch: [0, nchunks) the partials; workgroup 0 stores {norm, f} behind them
+__global__ void __launch_bounds__(256) gnorm_scale_kernel(float* __restrict__ g, const TensorTable tt,
+                                                          double* __restrict__ scratch, double max_norm) {
+  __shared__ double red[4];
+  constexpr int PER = UPD_CHUNK / 256;
+  const int b = blockIdx.x;
+  const int t = table_find(tt, b);
+  const int beg = (b - tt.chunk0[t]) * UPD_CHUNK;
+  const int end = min(tt.numel[t], beg + UPD_CHUNK);
+  float* gt = g + tt.off[t];
+  float gv[PER];
+  chunk_load(gt, beg, end, gv);   // in flight while the partials are summed
+  double ss = 0.0;
+  for (int k = threadIdx.x; k < tt.nchunks; k += 256) ss += scratch[k];
+  ss = block_sum_256_d(ss, red);
+  const double norm = sqrt(ss);
+  const double f = norm > max_norm ? max_norm / norm : 1.0;   // a NaN norm compares false
+  if (b == 0 && threadIdx.x == 0) {
+    scratch[tt.nchunks] = norm;
+    scratch[tt.nchunks + 1] = f;
+  }
+  if (f == 1.0) return;           // the unclipped gradient keeps its bits
+#pragma unroll
+  for (int j = 0; j < PER; ++j) {
+    const int i = beg + threadIdx.x + 256 * j;
+    if (i < end) gt[i] = (float)((double)gv[j] * f);
+  }
+}
+
 struct UpdateArgs {
   float* p;
   const float* g;

@@ -226,6 +226,22 @@ int ba3c_clip_grads(ba3c_handle* h, void* stream, float* grads, void* workspace)
  * + clip launches; bit-identical. */
 int ba3c_clip_grads_range(ba3c_handle* h, void* stream, float* grads, void* workspace, int32_t t0,
                           int32_t t1);
+/* Clip of the whole gradient's norm (tf.clip_by_global_norm, torch's clip_grad_norm_, up to
+ * rounding; the rule is stated in ba3c_amd/gradclip.py), in place over every tensor of the flat
+ * buffer; it replaces ba3c_clip_grads, it does not follow it:
+ *   norm = sqrt(sum of (double)g^2 over every element of every tensor)   (alignment gaps: not elements)
+ *   f    = norm > max_norm ? max_norm / norm : 1.0      (double; a NaN norm leaves f = 1.0)
+ *   g    = (float)((double)g * f)                       (f == 1.0: g keeps its bits)
+ * Two plain launches, no in-launch waits and no atomics; the sums run in a fixed order, so a
+ * repeat gives the same bits.  scratch: device memory of the caller's, 8-byte aligned, of
+ * scratch_doubles >= ba3c_global_clip_scratch(h) = nchunks + 2 doubles; after the call
+ * scratch[nchunks] = norm and scratch[nchunks + 1] = f.  The workspace is not touched.
+ * Refused with BA3C_ERR_INVALID before any launch, the first failure reported: a null handle;
+ * grads NULL or not 16-byte aligned; max_norm not finite or not > 0 (a NaN included); scratch
+ * NULL or not 8-byte aligned; scratch_doubles < nchunks + 2. */
+int64_t ba3c_global_clip_scratch(const ba3c_handle* h);     /* host only */
+int ba3c_clip_grads_global(ba3c_handle* h, void* stream, float* grads, double max_norm,
+                           double* scratch, int64_t scratch_doubles);
 
 /* One optimizer apply over the flat buffers: g_eff = grads*grad_scale (1/world after an
  * all-reduce-sum), or, with fuse_clip=1, clip_by_average_norm(grads) fused in (single

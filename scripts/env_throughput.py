@@ -37,12 +37,17 @@ ba3c_amd.episodes) alone at 100, 4096 and 65536 simulators (one flag in a hundre
 medians of event-bracketed batches, and ms per `ActorLearner.iterate` on GridBreakout at 100 and
 4096 simulators without and with a log, alternating in the same call; --episodes_only skips the
 environment tables.
+With --gradclip also the learner step with the reference's fused per-tensor clip next to the step
+with the global-norm clip (`Model(max_grad_norm=0.5)`, ba3c_amd.gradclip) on identical batches at
+(B, F, S) = (32, 128, 4) and (2048, 512, 1), fresh trainers, alternating, by the same medians; and
+the clip's two launches alone at both flat sizes; --gradclip_only skips the environment tables.
 Prints one JSON line.
 
     python scripts/env_throughput.py [--game boxing] [--envs 8192 64] [--iters 200] [--random 20]
                                      [--frame_skip 2-4] [--sticky 0.25] [--view 1 3] [--duel]
                                      [--duel_start 8-14] [--duel_only] [--returns] [--ppo] [--ppo_only]
                                      [--ppo_norm_adv] [--ppo_vclip 0.2] [--episodes] [--episodes_only]
+                                     [--gradclip] [--gradclip_only]
 """
 import argparse
 import json
@@ -253,6 +258,69 @@ def ppo_step_table(repeats, clip=0.2, norm_adv=False, vclip=0.0):
     return out
 
 
+def gradclip_table(repeats, max_norm=0.5):
+    """--gradclip: ms per learner step (pass + clip + Adam apply) with the reference's fused
+    per-tensor clip and with the global-norm clip (`Model(max_grad_norm=)`: two launches, then the
+    unfused apply) on the same batch, fresh trainers, alternating, by medians of event-bracketed
+    batches of steps; and the clip's two launches alone on the step's gradient, µs per call of
+    both and per launch: with every call clipping (max_norm shrinks by 0.1 % per call, so the
+    stores run) and with none (max_norm far above the norm: the stores are skipped)."""
+    from ba3c_amd.model import Model
+    from ba3c_amd.optimizer import AdamOptimizer
+    from ba3c_amd.trainer import Ba3cTrainer, TrainConfig
+    out = {}
+    for B, F, S in PPO_SHAPES:
+        g = torch.Generator(device="cuda").manual_seed(B)
+        st = torch.randint(0, 256, (B, 84, 84, 4), generator=g, device="cuda").to(torch.uint8)
+        ac = torch.randint(0, 4, (B,), generator=g, device="cuda")
+        R = torch.randn(B, generator=g, device="cuda")
+
+        def trainer(m):
+            model = Model(num_actions=4, fc_neurons=F, fc_splits=S, batch_size=B, max_batch=B, seed=0,
+                          max_grad_norm=m)
+            return Ba3cTrainer(TrainConfig(model=model, optimizer=AdamOptimizer(1e-5, 0.8, 0.75, 1e-8)))
+        plain, clipped = trainer(None), trainer(max_norm)
+        legs = {"fused_average_norm_clip_ms": lambda: plain.train_step(st, ac, R),
+                "global_norm_clip_ms": lambda: clipped.train_step(st, ac, R)}
+        t = {k: [] for k in legs}
+        for _ in range(repeats):
+            for k, fn in legs.items():
+                t[k].append(timed_median(fn) / 1e3)
+        row = {k: [round(v, 4) for v in vs] for k, vs in t.items()}
+        row["global_over_fused"] = round(min(t["global_norm_clip_ms"]) / min(t["fused_average_norm_clip_ms"]), 4)
+        row["added_us"] = round((min(t["global_norm_clip_ms"]) - min(t["fused_average_norm_clip_ms"])) * 1e3, 2)
+        norm, f = clipped._procs[0].last_stats.tolist()
+        row["last_norm"], row["last_f"] = norm, f
+        eng = clipped.engine
+        row["flat_bytes"] = 4 * eng.flat_size
+        shrink = [min(norm, max_norm)]                    # the norm the step's clip left
+
+        def clipping():
+            shrink[0] *= 0.999
+            eng.clip_grads_global(shrink[0])
+        kernels = {"clipping_us": clipping, "not_clipping_us": lambda: eng.clip_grads_global(1e30)}
+        tk = {k: [] for k in kernels}
+        for _ in range(repeats):
+            for k, fn in kernels.items():
+                tk[k].append(timed_median(fn))
+        for k, vs in tk.items():
+            row[k] = [round(v, 2) for v in vs]
+            row[k.replace("_us", "_us_per_launch")] = round(min(vs) / 2.0, 2)
+        # the back-to-back calls above are bound by the host's issue rate (a Python call per pair of
+        # launches); the probe brackets each pair with events on the device (their 5-6 us gap included)
+        for k, fn in kernels.items():
+            eng.probe_enable("clip")
+            for _ in range(200):
+                fn()
+            ms, n = eng.probe_read()
+            eng.probe_enable(None)
+            row[k.replace("_us", "_probe_us")] = round(1e3 * ms / max(n, 1), 2)
+        out["B%d_F%d_S%d" % (B, F, S)] = row
+        plain.check_device_errors()
+        clipped.check_device_errors()
+    return out
+
+
 def iterate_table(settings, iters=420, warmup=42, E=100):
     """--returns / --ppo: ms per ActorLearner.iterate on GridBoxing at E simulators (README flags:
     B = 32, F = 128, S = 4, Adam) per (local_time_max, gae_lambda[, ppo.Setting]) setting: a host
@@ -373,6 +441,10 @@ def main(argv=None):
                     help="--ppo: also time the extended step with the advantage normalisation launch")
     ap.add_argument("--ppo_vclip", type=float, default=0.0,
                     help="--ppo: also time the extended step with this value clip (0: off)")
+    ap.add_argument("--gradclip", action="store_true",
+                    help="also time the learner step without and with --max_grad_norm 0.5, and the "
+                         "global-norm clip's two launches alone")
+    ap.add_argument("--gradclip_only", action="store_true", help="--gradclip: skip the environment tables")
     ap.add_argument("--duel", action="store_true",
                     help="also time two-player GridBoxing at G = E / 2 games against BoxingVec at E")
     ap.add_argument("--envs", type=int, nargs="+", default=[8192, 64])
@@ -419,7 +491,8 @@ def main(argv=None):
         del fill
 
     for E in ([] if (args.duel and args.duel_only) or (args.ppo and args.ppo_only)
-              or (args.episodes and args.episodes_only) else args.envs):
+              or (args.episodes and args.episodes_only)
+              or (args.gradclip and args.gradclip_only) else args.envs):
         g = torch.Generator(device="cuda").manual_seed(0)
         actions = torch.randint(0, A, (E,), generator=g, device="cuda")
         env, hist = Vec(E, seed=0), FrameHistory(E, 4, 1)
@@ -495,6 +568,8 @@ def main(argv=None):
     if args.episodes:
         out["episode_stats"] = episodes_table(args.repeats)
         out["episodes_iterate"] = episodes_iterate_table()
+    if args.gradclip:
+        out["gradclip"] = gradclip_table(args.repeats)
     if args.random:
         from ba3c_amd.evaluate import eval_with_envs, uniform_policy
         from ba3c_amd.model import Model
