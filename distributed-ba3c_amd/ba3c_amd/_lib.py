@@ -39,7 +39,8 @@ class Ba3cOptParams(ctypes.Structure):
 
 _lib = None
 # roofline-accounting queries, the PPO entry points, the episode log and the global-norm clip an
-# alternative A/B build (BA3C_LIB) may predate
+# alternative A/B build (BA3C_LIB) may predate.  Every PPO step of the engine is one
+# ba3c_train_grads_ppo_ext call: a build older than that entry point runs none.
 AB_OPTIONAL = {"ba3c_kernel_merged", "ba3c_probe_every", "ba3c_train_grads_ppo", "ba3c_sample_logp",
                "ba3c_train_grads_ppo_ext", "ba3c_ppo_norm_adv", "ba3c_episode_stats",
                "ba3c_global_clip_scratch", "ba3c_clip_grads_global"}

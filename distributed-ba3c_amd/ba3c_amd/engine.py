@@ -164,16 +164,20 @@ class Ba3cEngine(object):
         """Forward + loss + backward; raw gradients into `grads` (default self.grads).
         Returns the device float64 scalars tensor (order: _lib.SCALAR_NAMES).  phase 1 / 2
         split the pass at the fc1 + heads bucket (ba3c_train_grads_phase)."""
+        B, action, grads, ws = self._check_train(state, action, grads)
+        assert futurereward.dtype == torch.float32 and futurereward.shape == (B,)
+        _lib.check(self.lib.ba3c_train_grads_phase(self.h, _stream(), _ptr(self.params), _ptr(state),
+                                                   _ptr(action), _ptr(futurereward.contiguous()), B,
+                                                   float(entropy_beta), _ptr(ws), _ptr(grads),
+                                                   _ptr(self.scalars), int(phase)))
+        return self.scalars
+
+    def _check_train(self, state, action, grads):
+        """A training pass's checked inputs: (B, contiguous action, grads or self.grads, the
+        training workspace)."""
         B = self._check_state(state)
         assert action.dtype == torch.int64 and action.shape == (B,) and action.is_cuda
-        assert futurereward.dtype == torch.float32 and futurereward.shape == (B,)
-        grads = self.grads if grads is None else grads
-        _lib.check(self.lib.ba3c_train_grads_phase(self.h, _stream(), _ptr(self.params), _ptr(state),
-                                                   _ptr(action.contiguous()),
-                                                   _ptr(futurereward.contiguous()), B,
-                                                   float(entropy_beta), _ptr(self._workspace(True)),
-                                                   _ptr(grads), _ptr(self.scalars), int(phase)))
-        return self.scalars
+        return B, action.contiguous(), self.grads if grads is None else grads, self._workspace(True)
 
     def ppo_norm_adv(self, rows, stats=None):
         """Per-minibatch advantage normalisation in place (ba3c_ppo_norm_adv, ba3c_amd.ppo): writes
@@ -189,17 +193,14 @@ class Ba3cEngine(object):
 
     def train_grads_ppo(self, state, action, rows, clip_eps, entropy_beta=0.01, grads=None,
                         phase=0, ratio=True, vclip=0.0, adv_from_row=False):
-        """train_grads with the clipped-surrogate policy term (ba3c_train_grads_ppo, ba3c_amd.ppo):
-        rows float32 [B, 4] = {R, V_old, l_old, 0}; the phases are train_grads'.  ratio: True
-        writes each sample's rho into self.ratio[:B] (a tensor: into it; None / False: not
-        stored).  vclip > 0: the clipped value loss; adv_from_row: the advantage is rows[:, 3]
-        (ppo_norm_adv) — either one takes ba3c_train_grads_ppo_ext, neither the call as it was.
-        Returns the scalars tensor."""
-        B = self._check_state(state)
-        assert action.dtype == torch.int64 and action.shape == (B,) and action.is_cuda
+        """train_grads with the clipped-surrogate policy term (ba3c_train_grads_ppo_ext,
+        ba3c_amd.ppo): rows float32 [B, 4] = {R, V_old, l_old, w}; the phases are train_grads'.
+        ratio: True writes each sample's rho into self.ratio[:B] (a tensor: into it; None / False:
+        not stored).  vclip > 0: the clipped value loss; adv_from_row: the advantage is
+        rows[:, 3] (ppo_norm_adv).  Returns the scalars tensor."""
+        B, action, grads, ws = self._check_train(state, action, grads)
         assert rows.dtype == torch.float32 and rows.shape == (B, 4) and rows.is_cuda \
             and rows.is_contiguous()
-        grads = self.grads if grads is None else grads
         if ratio is True:
             if self.ratio is None:
                 self.ratio = torch.ones(self.max_batch, dtype=torch.float32, device=self.device)
@@ -207,18 +208,11 @@ class Ba3cEngine(object):
         elif ratio is False:
             ratio = None
         assert ratio is None or (ratio.dtype == torch.float32 and ratio.numel() >= B)
-        if vclip or adv_from_row:
-            _lib.check(self.lib.ba3c_train_grads_ppo_ext(
-                self.h, _stream(), _ptr(self.params), _ptr(state), _ptr(action.contiguous()),
-                _ptr(rows), B, float(entropy_beta), float(clip_eps), float(vclip),
-                _lib.PPO_ADV_FROM_ROW if adv_from_row else 0, _ptr(self._workspace(True)),
-                _ptr(grads), _ptr(self.scalars), _ptr(ratio), int(phase)))
-            return self.scalars
-        _lib.check(self.lib.ba3c_train_grads_ppo(self.h, _stream(), _ptr(self.params), _ptr(state),
-                                                 _ptr(action.contiguous()), _ptr(rows), B,
-                                                 float(entropy_beta), float(clip_eps),
-                                                 _ptr(self._workspace(True)), _ptr(grads),
-                                                 _ptr(self.scalars), _ptr(ratio), int(phase)))
+        _lib.check(self.lib.ba3c_train_grads_ppo_ext(
+            self.h, _stream(), _ptr(self.params), _ptr(state), _ptr(action), _ptr(rows), B,
+            float(entropy_beta), float(clip_eps), float(vclip),
+            _lib.PPO_ADV_FROM_ROW if adv_from_row else 0, _ptr(ws), _ptr(grads), _ptr(self.scalars),
+            _ptr(ratio), int(phase)))
         return self.scalars
 
     def occupy_cus(self, stream, n_cus, usec):

@@ -6,6 +6,8 @@ outputs, :302-304), `get_cost`, `get_gradient_processor` (train.py:329-330) and
 `vars_for_save` (checkpoint keys).  `_build_graph` executes the fused HIP forward (+ loss
 + backward when training) on the current stream; the results are device tensors.
 """
+from collections import namedtuple
+
 import numpy as np
 import torch
 
@@ -18,6 +20,9 @@ IMAGE_SIZE = (84, 84)     # train.py:92
 FRAME_HISTORY = 4         # train.py:93
 LOCAL_TIME_MAX = 5        # train.py:102
 GAMMA = 0.99              # train.py:94
+
+# the clipped-surrogate loss of one step (ba3c_amd.ppo; Ba3cTrainer.train_step's arguments)
+PpoStep = namedtuple("PpoStep", ["rows", "clip", "vclip", "adv_from_row"])
 
 
 class Model(ModelDesc):
@@ -44,9 +49,6 @@ class Model(ModelDesc):
         self.explore_factor = 1.0     # non-trainable var 'explore_factor' (train.py:294-295)
         self.vars_for_save = {n: n for n in self.engine.tensor_names}
         self.cost = None
-        # (rows, clip, vclip, adv_from_row) of a clipped-surrogate step (Ba3cTrainer.train_step
-        # sets it for the step's passes); None: the A3C loss
-        self.ppo = None
         self.ratio = None             # the last PPO pass's per-sample rho (device, [B])
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self._global_clip = None if max_grad_norm is None else ClipByGlobalNorm(max_grad_norm)
@@ -59,7 +61,10 @@ class Model(ModelDesc):
                 InputVar(torch.float32, (None,), "init_R"),
                 InputVar(torch.bool, (None,), "isOver")]
 
-    def _build_graph(self, inputs):
+    def _build_graph(self, inputs, phase=0, ppo=None):
+        """phase 1 / 2: the two halves of the training pass around the fc1 + heads gradient bucket
+        (Ba3cTrainer's bucketed data-parallel step), 0: the whole pass.  ppo: a PpoStep, the
+        pass's loss; None: the A3C loss."""
         state, action, futurereward = inputs[0], inputs[1], inputs[2]
         ctx = get_current_tower_context()
         is_training = True if ctx is None else ctx.is_training
@@ -68,14 +73,10 @@ class Model(ModelDesc):
                 state, explore_factor=self.explore_factor)
             return
         self.delay = inputs[3] if len(inputs) > 3 else None
-        # train_phase 1 / 2: the two halves of the pass around the fc1 + heads gradient bucket
-        # (Ba3cTrainer's bucketed data-parallel step); 0: the whole pass
-        phase = getattr(self, "train_phase", 0)
-        if self.ppo is not None:
-            rows, clip, vclip, adv_from_row = self.ppo
-            sc = self.engine.train_grads_ppo(state, action, rows, clip,
+        if ppo is not None:
+            sc = self.engine.train_grads_ppo(state, action, ppo.rows, ppo.clip,
                                              entropy_beta=self.entropy_beta, phase=phase,
-                                             vclip=vclip, adv_from_row=adv_from_row)
+                                             vclip=ppo.vclip, adv_from_row=ppo.adv_from_row)
             self.ratio = self.engine.ratio[:state.shape[0]]
         else:
             sc = self.engine.train_grads(state, action, futurereward,

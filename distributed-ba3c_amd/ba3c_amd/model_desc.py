@@ -55,8 +55,9 @@ class ModelDesc(object):
     def _get_input_vars(self):
         raise NotImplementedError
 
-    def build_graph(self, model_inputs):
-        self._build_graph(model_inputs)
+    def build_graph(self, model_inputs, **step):
+        """step: what one call computes besides its inputs (Model: phase=, ppo=)."""
+        self._build_graph(model_inputs, **step)
 
     def _build_graph(self, inputs):
         raise NotImplementedError

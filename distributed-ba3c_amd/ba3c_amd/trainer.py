@@ -11,6 +11,7 @@ import time
 import numpy as np
 import torch
 
+from .model import PpoStep
 from .model_desc import ClipByAverageNorm, MapGradient
 from . import hipevent
 from .optimizer import SyncReplicasOptimizer
@@ -134,11 +135,8 @@ class Ba3cTrainer(object):
             raise ValueError("vclip and adv_from_row belong to a PPO step (rows and clip)")
         if rows is None:
             return self._train_step(state, action, futurereward)
-        self.model.ppo = (rows, float(clip), float(vclip), bool(adv_from_row))
-        try:
-            return self._train_step(state, action, futurereward)
-        finally:
-            self.model.ppo = None
+        return self._train_step(state, action, futurereward,
+                                ppo=PpoStep(rows, float(clip), float(vclip), bool(adv_from_row)))
 
     # None, or {"learning_rate": fn, "entropy_beta": fn} (either key may be missing): functions of
     # the 0-based global_step before the step (ba3c_amd.schedule).  Both values are kernel
@@ -159,16 +157,17 @@ class Ba3cTrainer(object):
             out["entropy_beta"] = self.model.entropy_beta = float(fn(self.global_step))
         return out
 
-    def _train_step(self, state, action, futurereward):
+    def _train_step(self, state, action, futurereward, **loss):
+        """loss: the step's loss as Model.build_graph takes it (ppo=PpoStep); none: A3C."""
         self.apply_schedules()
         opt = self.optimizer
         # backup workers pick the first k ranks once the whole gradient is ready: flat path
         if (isinstance(opt, SyncReplicasOptimizer) and self._fused_clip and opt.bucketed
                 and not opt.backup_workers):
-            self._bucketed_sync_step(state, action, futurereward)
+            self._bucketed_sync_step(state, action, futurereward, **loss)
             self.global_step += 1
             return
-        self.model.build_graph([state, action, futurereward])
+        self.model.build_graph([state, action, futurereward], **loss)
         if isinstance(opt, SyncReplicasOptimizer):
             if self._fused_clip:
                 opt.aggregate(self.engine)
@@ -183,7 +182,7 @@ class Ba3cTrainer(object):
             opt.apply_gradients(self.engine)
         self.global_step += 1
 
-    def _bucketed_sync_step(self, state, action, futurereward):
+    def _bucketed_sync_step(self, state, action, futurereward, **loss):
         """Data-parallel step with the gradient exchange in two buckets: phase 1 of the pass
         (forward, loss, heads + fc1 backward) -> clip + async RCCL sum of the fc1 + heads
         bucket -> phase 2 (conv backward, overlapping that all-reduce) -> clip + RCCL sum of
@@ -203,15 +202,10 @@ class Ba3cTrainer(object):
                                           | hipevent.HIP_EVENT_RELEASE_TO_DEVICE)
             eng.set_phase2_event(self._mid)
         mark("start")
-        try:
-            m.train_phase = 1
-            m.build_graph(inputs)
-            mark("phase1_end")
-            eng.clip_grads_range(tb, nt)     # the bucket's clip (one launch)
-            m.train_phase = 2
-            m.build_graph(inputs)
-        finally:
-            m.train_phase = 0
+        m.build_graph(inputs, phase=1, **loss)
+        mark("phase1_end")
+        eng.clip_grads_range(tb, nt)     # the bucket's clip (one launch)
+        m.build_graph(inputs, phase=2, **loss)
         # the fc1 + heads bucket's sum on the exchange stream from the phase-2 event on, beside
         # conv2..conv0's backward
         work = opt.aggregate_fc1_bucket_async(
@@ -239,7 +233,7 @@ class Ba3cTrainer(object):
         undone: parameters, optimizer slots and beta powers are restored afterwards, so
         capturing does not train the model.  A PPO step (rows / clip) is refused, and so is a
         non-constant schedule (`schedules`); a global-norm clip captures like any other launch."""
-        if rows is not None or clip is not None or self.model.ppo is not None:
+        if rows is not None or clip is not None:
             raise ValueError("graph capture of a PPO step (rows / clip) is not supported")
         for name, fn in (self.schedules or {}).items():
             if fn is not None and not getattr(fn, "constant", False):

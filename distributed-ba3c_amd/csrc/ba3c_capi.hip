@@ -1053,15 +1053,12 @@ struct BackwardPass {
   }
 };
 
-// the PPO form of a training heads launch (ba3c_train_grads_ppo): rows replaces R
+// the PPO form of a training heads launch (ba3c_train_grads_ppo_ext): rows replaces R
 struct PpoArgs {
-  const float* rows;   // [B][4] {R, V_old, l_old, 0}
+  const float* rows;   // [B][4] {R, V_old, l_old, w}
   float* ratio;        // [B] or null
-  float clip_eps;
-  // ba3c_train_grads_ppo_ext: the LOSS_PPO_EXT heads (at vclip_eps = 0, flags = 0 too)
-  bool ext = false;
-  float vclip_eps = 0.f;
-  unsigned flags = 0;
+  float clip_eps, vclip_eps;
+  unsigned flags;
 };
 
 // the heads instantiation of (F, A) for one loss: features per lane unrolled (heads_sample),
@@ -1084,7 +1081,7 @@ int run_heads(ba3c_handle* h, hipStream_t s, const float* prm, const Workspace& 
               const int64_t* action, const float* R, float beta, float explore, bool train,
               float* probs, float* probsT, float* value, double* scalars = nullptr,
               bool defer_scalars = false, const PpoArgs* ppo = nullptr) {
-  HeadsArgsPpoExt a{};
+  HeadsArgsPpo a{};
   if (ppo) {
     a.rows = reinterpret_cast<const float4*>(ppo->rows);
     a.ratio = ppo->ratio;
@@ -1127,8 +1124,7 @@ int run_heads(ba3c_handle* h, hipStream_t s, const float* prm, const Workspace& 
   a.invB = 1.0f / (float)B;
   {
     ProbeScope ps(h, s, BA3C_K_HEADS);
-    if (ppo && train && ppo->ext) launch_heads<LOSS_PPO_EXT>(s, B, a);
-    else if (ppo && train) launch_heads<LOSS_PPO>(s, B, a);
+    if (ppo && train) launch_heads<LOSS_PPO>(s, B, a);
     else launch_heads<LOSS_A3C>(s, B, a);
   }
   HIP_TRY(hipGetLastError());
@@ -1478,40 +1474,20 @@ int ba3c_forward(ba3c_handle* h, void* stream, const float* params, const uint8_
                    probsT, value);
 }
 
-static int train_grads_impl(ba3c_handle* h, void* stream, const float* params, const uint8_t* state,
-                            const int64_t* action, const float* futurereward, int32_t batch,
-                            float entropy_beta, void* workspace, float* grads, double* scalars,
-                            int32_t phase, const PpoArgs* ppo = nullptr);
-
 int ba3c_set_phase2_event(ba3c_handle* h, void* event) {
   if (!h) return fail(BA3C_ERR_INVALID, "null handle");
   h->ev_mid = static_cast<hipEvent_t>(event);
   return BA3C_OK;
 }
 
-int ba3c_train_grads(ba3c_handle* h, void* stream, const float* params, const uint8_t* state,
-                     const int64_t* action, const float* futurereward, int32_t batch,
-                     float entropy_beta, void* workspace, float* grads, double* scalars) {
-  return train_grads_impl(h, stream, params, state, action, futurereward, batch, entropy_beta, workspace,
-                          grads, scalars, 0);
-}
-
-int ba3c_train_grads_phase(ba3c_handle* h, void* stream, const float* params, const uint8_t* state,
-                           const int64_t* action, const float* futurereward, int32_t batch,
-                           float entropy_beta, void* workspace, float* grads, double* scalars,
-                           int32_t phase) {
-  if (phase < 0 || phase > 2) return fail(BA3C_ERR_INVALID, "phase must be 0, 1 or 2");
-  return train_grads_impl(h, stream, params, state, action, futurereward, batch, entropy_beta, workspace,
-                          grads, scalars, phase);
-}
-
 int ba3c_bucket_tensor(const ba3c_handle* h) { return h ? h->idx_fc1 : -1; }
 
+// ppo: the clipped-surrogate heads (ba3c_train_grads_ppo_ext); its rows stand in for futurereward
 static int train_grads_impl(ba3c_handle* h, void* stream, const float* params, const uint8_t* state,
                             const int64_t* action, const float* futurereward, int32_t batch,
                             float entropy_beta, void* workspace, float* grads, double* scalars,
-                            int32_t phase, const PpoArgs* ppo) {
-  // ppo: the clipped-surrogate heads (ba3c_train_grads_ppo); its rows stand in for futurereward
+                            int32_t phase, const PpoArgs* ppo = nullptr) {
+  if (phase < 0 || phase > 2) return fail(BA3C_ERR_INVALID, "phase must be 0, 1 or 2");
   if (!h || !check_ptr(params) || !check_ptr(state) || !check_ptr(workspace) || !check_ptr(grads) ||
       !action || (!futurereward && !ppo))
     return fail(BA3C_ERR_INVALID, "null or misaligned pointer");
@@ -1540,18 +1516,19 @@ static int train_grads_impl(ba3c_handle* h, void* stream, const float* params, c
   return backward();
 }
 
-int ba3c_train_grads_ppo(ba3c_handle* h, void* stream, const float* params, const uint8_t* state,
-                         const int64_t* action, const float* rows, int32_t batch,
-                         float entropy_beta, float clip_eps, void* workspace, float* grads,
-                         double* scalars, float* ratio, int32_t phase) {
-  if (!check_ptr(rows)) return fail(BA3C_ERR_INVALID, "rows must be non-null and 16-byte aligned");
-  if (ratio && !check_ptr(ratio)) return fail(BA3C_ERR_INVALID, "ratio must be 16-byte aligned (or null)");
-  // written so that a NaN fails it
-  if (!(clip_eps > 0.f && clip_eps < 1.f)) return fail(BA3C_ERR_INVALID, "clip_eps must be in (0, 1)");
-  if (phase < 0 || phase > 2) return fail(BA3C_ERR_INVALID, "phase must be 0, 1 or 2");
-  const PpoArgs ppo{rows, ratio, clip_eps};
-  return train_grads_impl(h, stream, params, state, action, nullptr, batch, entropy_beta, workspace,
-                          grads, scalars, phase, &ppo);
+int ba3c_train_grads_phase(ba3c_handle* h, void* stream, const float* params, const uint8_t* state,
+                           const int64_t* action, const float* futurereward, int32_t batch,
+                           float entropy_beta, void* workspace, float* grads, double* scalars,
+                           int32_t phase) {
+  return train_grads_impl(h, stream, params, state, action, futurereward, batch, entropy_beta, workspace,
+                          grads, scalars, phase);
+}
+
+int ba3c_train_grads(ba3c_handle* h, void* stream, const float* params, const uint8_t* state,
+                     const int64_t* action, const float* futurereward, int32_t batch,
+                     float entropy_beta, void* workspace, float* grads, double* scalars) {
+  return ba3c_train_grads_phase(h, stream, params, state, action, futurereward, batch, entropy_beta,
+                                workspace, grads, scalars, 0);
 }
 
 int ba3c_train_grads_ppo_ext(ba3c_handle* h, void* stream, const float* params, const uint8_t* state,
@@ -1566,11 +1543,18 @@ int ba3c_train_grads_ppo_ext(ba3c_handle* h, void* stream, const float* params, 
   if (!(vclip_eps >= 0.f && std::isfinite(vclip_eps)))
     return fail(BA3C_ERR_INVALID, "vclip_eps must be finite and >= 0 (0: no value clipping)");
   if (flags & ~BA3C_PPO_ADV_FROM_ROW) return fail(BA3C_ERR_INVALID, "unknown flags bits");
-  if (phase < 0 || phase > 2) return fail(BA3C_ERR_INVALID, "phase must be 0, 1 or 2");
   static_assert(BA3C_PPO_ADV_FROM_ROW == PPO_ADV_FROM_ROW, "the header's bit is the kernel's");
-  const PpoArgs ppo{rows, ratio, clip_eps, true, vclip_eps, flags};
+  const PpoArgs ppo{rows, ratio, clip_eps, vclip_eps, flags};
   return train_grads_impl(h, stream, params, state, action, nullptr, batch, entropy_beta, workspace,
                           grads, scalars, phase, &ppo);
+}
+
+int ba3c_train_grads_ppo(ba3c_handle* h, void* stream, const float* params, const uint8_t* state,
+                         const int64_t* action, const float* rows, int32_t batch,
+                         float entropy_beta, float clip_eps, void* workspace, float* grads,
+                         double* scalars, float* ratio, int32_t phase) {
+  return ba3c_train_grads_ppo_ext(h, stream, params, state, action, rows, batch, entropy_beta, clip_eps,
+                                  0.f, 0, workspace, grads, scalars, ratio, phase);
 }
 
 int ba3c_ppo_norm_adv(void* stream, float* rows, int32_t n, double* stats) {

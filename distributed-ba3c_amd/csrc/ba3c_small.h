@@ -36,22 +36,20 @@ __device__ __forceinline__ unsigned long long ld_agent(const unsigned long long*
 // terms[n] = {log(p_a+1e-6)*adv, sum p log(p+1e-6), (V-R)^2, adv, V, max p, 0, 0}
 //
 // LOSS_PPO: the clipped-surrogate policy term (Schulman et al. 2017; ba3c_amd/ppo.py states it
-// and is its oracle).  Per sample rows[n] = {R, V_old, l_old, 0} with l_old =
+// and is its oracle).  Per sample rows[n] = {R, V_old, l_old, w} with l_old =
 // log(pi_old(a) + 1e-6):
 //   Adv = R - V_old,  rho = exp(log(p_a+1e-6) - l_old),  rc = clip(rho, 1-eps, 1+eps)
 //   s = -min(rho Adv, rc Adv),  c = (rho Adv <= rc Adv) ? -Adv rho : 0   (a tie is unclipped)
 // and dL/dp is the A3C one with `adv` replaced by `c`; terms[n][0] = s, the entropy and value
 // terms and terms 1-5 are the A3C ones (term 3 stays V - R with the current V).  At rho = 1
-// and V_old = V this is the A3C gradient.
-//
-// LOSS_PPO_EXT: LOSS_PPO with two more choices, each uniform over the launch (ppo.py states them):
+// and V_old = V this is the A3C gradient.  Two more choices, each uniform over the launch and
+// off at 0 (ppo.py states them):
 //   flags bit 0: Adv = rows[n].w (a normalised advantage, ba3c_ppo_norm_adv) instead of R - V_old;
 //   vclip_eps > 0: the clipped value loss.  d = V - V_old, Vc = V_old + sign(d) vclip_eps,
 //     use_clipped = |d| > vclip_eps and (Vc - R)^2 > (V - R)^2   (a tie is unclipped);
 //     terms[n][2] = use_clipped ? (Vc - R)^2 : (V - R)^2,  dV = use_clipped ? 0 : (V - R) / B.
-// With vclip_eps = 0 and flags = 0 every stored value is LOSS_PPO's, bit for bit.
 // ---------------------------------------------------------------------------------------
-constexpr int LOSS_A3C = 0, LOSS_PPO = 1, LOSS_PPO_EXT = 2;
+constexpr int LOSS_A3C = 0, LOSS_PPO = 1;
 struct HeadsArgs {
   float* h;
   const float* piW;
@@ -79,23 +77,18 @@ struct HeadsArgs {
   unsigned long long* done;  // completion counter (zero on entry; reset by the last workgroup)
   double* scalars;           // null: no scalars
 };
-// The LOSS_PPO instantiations' arguments: HeadsArgs grown by the PPO inputs.  A type of its own
-// so that the LOSS_A3C kernels keep the kernel-argument block, and with it the code, they had.
+// The LOSS_PPO instantiations' arguments: HeadsArgs and the loss's inputs (the LOSS_A3C kernels
+// take HeadsArgs alone).
+constexpr unsigned PPO_ADV_FROM_ROW = 1u;   // flags bit 0: Adv is rows[n].w
 struct HeadsArgsPpo : HeadsArgs {
-  const float4* rows;        // [B] {R, V_old, l_old, 0}: replaces R
+  const float4* rows;        // [B] {R, V_old, l_old, w}: replaces R
   float* ratio;              // [B] rho, may be null
   float clip_eps;
-};
-// The LOSS_PPO_EXT instantiations' arguments, again a type of their own: the LOSS_A3C and
-// LOSS_PPO kernels keep their argument blocks.
-constexpr unsigned PPO_ADV_FROM_ROW = 1u;   // flags bit 0: Adv is rows[n].w
-struct HeadsArgsPpoExt : HeadsArgsPpo {
   float vclip_eps;           // 0: no value clipping
   unsigned flags;
 };
 template <int LOSS>
-using HeadsArgsOf = std::conditional_t<LOSS == LOSS_PPO_EXT, HeadsArgsPpoExt,
-                                       std::conditional_t<LOSS == LOSS_PPO, HeadsArgsPpo, HeadsArgs>>;
+using HeadsArgsOf = std::conditional_t<LOSS == LOSS_PPO, HeadsArgsPpo, HeadsArgs>;
 
 // The per-sample head arithmetic runs in fp64: the softmax gradient
 // p_k (g_k - sum_j p_j g_j) cancels catastrophically when the policy saturates, and fp64 here
@@ -116,9 +109,8 @@ __device__ __forceinline__ double wave_max_d(double v, int w = 64) { return wave
 // ~80 dependent global round trips per sample (r04 ISA) — the heads launch's whole time.  With
 // AT every weight load of a lane's features is unconditional (features past F read feature
 // F - 1 and are multiplied by zero), so they are all in flight together.
-// LOSS: the policy term (LOSS_A3C / LOSS_PPO / LOSS_PPO_EXT), compile-time so that the A3C
-// instantiations carry nothing of the others; a LOSS_PPO* launch is a training launch
-// (p.train != 0).
+// LOSS: the policy term (LOSS_A3C / LOSS_PPO), compile-time so that the A3C instantiations
+// carry nothing of the other; a LOSS_PPO launch is a training launch (p.train != 0).
 template <int FCH, int NZ, int AT, int LOSS>
 __device__ __forceinline__ void heads_sample(const HeadsArgsOf<LOSS>& p, int n, int lane) {
   const int A = AT ? AT : p.A;
@@ -141,7 +133,7 @@ __device__ __forceinline__ void heads_sample(const HeadsArgsOf<LOSS>& p, int n, 
   float bpre[PRE ? AT + 1 : 1];                  // pi biases, v bias
   float blg[PRE ? FCH : 1];                      // legacy FC bias of the lane's features
   float Rpre = 0.f;
-  constexpr bool ROWS = LOSS != LOSS_A3C;            // LOSS_PPO*: the sample's row replaces R
+  constexpr bool ROWS = LOSS != LOSS_A3C;            // LOSS_PPO: the sample's row replaces R
   float4 rowpre = make_float4(0.f, 0.f, 0.f, 0.f);   // one 16-byte load
   int apre = 0;
   float hv32[FCH > 0 ? FCH : 1];
@@ -301,7 +293,7 @@ __device__ __forceinline__ void heads_sample(const HeadsArgsOf<LOSS>& p, int n, 
   double c = adv, t0 = lpa * adv;                   // the policy term's coefficient and value
   if constexpr (ROWS) {
     double Adv = Rn - (double)rowpre.y;
-    if constexpr (LOSS == LOSS_PPO_EXT) Adv = (p.flags & PPO_ADV_FROM_ROW) ? (double)rowpre.w : Adv;
+    Adv = (p.flags & PPO_ADV_FROM_ROW) ? (double)rowpre.w : Adv;
     const double rho = exp(lpa - (double)rowpre.z);
     const double eps = (double)p.clip_eps;
     const double su = rho * Adv, sc = fmin(fmax(rho, 1.0 - eps), 1.0 + eps) * Adv;
@@ -312,18 +304,18 @@ __device__ __forceinline__ void heads_sample(const HeadsArgsOf<LOSS>& p, int n, 
   const double gp = mine ? ((lane == act ? c / pe : 0.0) + beta * (lp + pr / pe)) * invB : 0.0;
   const double sgp = wave_sum_d(gp * pr, A);
   const double dz = mine ? pr * (gp - sgp) : 0.0;
-  // LOSS_PPO_EXT, the clipped value loss: the larger of the two squared errors, and no value
+  // LOSS_PPO, the clipped value loss: the larger of the two squared errors, and no value
   // gradient where it is the clipped one (selects, uniform in p.vclip_eps; 0 switches the clip
-  // off).  The other forms compile to what they were: use_clipped is a constant there.
+  // off).  LOSS_A3C compiles to what it was: use_clipped is a constant there.
   bool use_clipped = false;
   double csq = 0.0;
-  if constexpr (LOSS == LOSS_PPO_EXT) {
+  if constexpr (LOSS == LOSS_PPO) {
     const double ve = (double)p.vclip_eps, Vold = (double)rowpre.y;
     const double d = V - Vold, Vc = Vold + copysign(ve, d);
     csq = (Vc - Rn) * (Vc - Rn);
     use_clipped = ve > 0.0 && fabs(d) > ve && csq > (V - Rn) * (V - Rn);
   }
-  const double dV = LOSS == LOSS_PPO_EXT && use_clipped ? 0.0 : (V - Rn) * invB;
+  const double dV = LOSS == LOSS_PPO && use_clipped ? 0.0 : (V - Rn) * invB;
   // [dz | dV | 0...] row for the head weight-gradient product
   if (lane < MAXA) p.dzv[(size_t)n * MAXA + lane] = (float)(lane == A ? dV : dz);
   double dza[NA];
@@ -370,7 +362,7 @@ __device__ __forceinline__ void heads_sample(const HeadsArgsOf<LOSS>& p, int n, 
     double t = 0.0;
     t = lane == 0 ? t0 : t;
     t = lane == 1 ? xent : t;
-    t = lane == 2 ? (LOSS == LOSS_PPO_EXT && use_clipped ? csq : (V - Rn) * (V - Rn)) : t;
+    t = lane == 2 ? (LOSS == LOSS_PPO && use_clipped ? csq : (V - Rn) * (V - Rn)) : t;
     t = lane == 3 ? adv : t;
     t = lane == 4 ? V : t;
     t = lane == 5 ? pmax : t;
@@ -1202,9 +1194,15 @@ __global__ void __launch_bounds__(64) occupy_kernel(unsigned long long ticks) {
   asm volatile("" ::"v"(v));   // keeps the LDS declaration (and so the CU) allocated
 }
 
-__global__ void __launch_bounds__(256) sample_kernel(const float* __restrict__ probs,
-                                                     const double* __restrict__ u, int B, int A,
-                                                     int64_t* __restrict__ actions, int* flag) {
+// One row of both samplers (thread n, row n of `probs`): two passes over the row — the flag bits
+// (1: a non-finite entry, 4: a negative one, 2: the sum is off 1 by more than numpy.random.choice
+// tolerates) with the total, then the cumulative sums again against the uniform u[n] — and
+// actions[n].  LOGP: also logp[n] = log(pi[n][min(a, A - 1)] + 1e-6) in fp64, the heads'
+// log(p_a + 1e-6) of the PPO ratio.  The whole row, stores included, is one function: with only
+// the two passes factored out the compiler laid the kernels' blocks out differently.
+template <bool LOGP>
+__device__ __forceinline__ void sample_row(const float* probs, const float* pi, const double* u,
+                                           int B, int A, int64_t* actions, float* logp, int* flag) {
   const int n = blockIdx.x * 256 + threadIdx.x;
   if (n >= B) return;
   const float* pn = probs + (size_t)n * A;
@@ -1228,41 +1226,24 @@ __global__ void __launch_bounds__(256) sample_kernel(const float* __restrict__ p
     a += (c / tot <= un) ? 1 : 0;
   }
   actions[n] = a;
+  if constexpr (LOGP) logp[n] = (float)log((double)pi[(size_t)n * A + min((int)a, A - 1)] + 1e-6);
   if (bad && flag) atomicOr(flag, bad);
 }
 
-// sample_kernel that also records the behaviour policy's log-probability of the drawn action:
-// the same two passes over `probs` in the same order (the same actions and flag), then
-// logp[n] = log(pi[n][min(a, A - 1)] + 1e-6) in fp64 — the heads' log(p_a + 1e-6) of the PPO
-// ratio.  probs: the distribution sampled from ('logitsT'), pi: the one whose log is recorded
-// ('logits'); they may be the same array (no __restrict__ on either).
+__global__ void __launch_bounds__(256) sample_kernel(const float* __restrict__ probs,
+                                                     const double* __restrict__ u, int B, int A,
+                                                     int64_t* __restrict__ actions, int* flag) {
+  sample_row<false>(probs, nullptr, u, B, A, actions, nullptr, flag);
+}
+
+// sample_kernel that also records the behaviour policy's log-probability of the drawn action (the
+// same actions and flag).  probs: the distribution sampled from ('logitsT'), pi: the one whose
+// log is recorded ('logits'); they may be the same array (no __restrict__ on either).
 __global__ void __launch_bounds__(256) sample_logp_kernel(const float* probs, const float* pi,
                                                           const double* __restrict__ u, int B, int A,
                                                           int64_t* __restrict__ actions,
                                                           float* __restrict__ logp, int* flag) {
-  const int n = blockIdx.x * 256 + threadIdx.x;
-  if (n >= B) return;
-  const float* pn = probs + (size_t)n * A;
-  double cum = 0.0;
-  int bad = 0;
-  for (int k = 0; k < A; ++k) {
-    const float pk = pn[k];
-    if (!isfinite(pk)) bad |= 1;
-    if (pk < 0.f) bad |= 4;
-    cum += (double)pk;
-  }
-  if (fabs(cum - 1.0) > 3.4526698300124393e-04) bad |= 2;
-  const double tot = cum;
-  const double un = u[n];
-  int64_t a = 0;
-  double c = 0.0;
-  for (int k = 0; k < A; ++k) {
-    c += (double)pn[k];
-    a += (c / tot <= un) ? 1 : 0;
-  }
-  actions[n] = a;
-  logp[n] = (float)log((double)pi[(size_t)n * A + min((int)a, A - 1)] + 1e-6);
-  if (bad && flag) atomicOr(flag, bad);
+  sample_row<true>(probs, pi, u, B, A, actions, logp, flag);
 }
 
 // Evaluation players' action (OpenAIGym/common.py:24-33): numpy argmax of the policy (first

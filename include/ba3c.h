@@ -159,10 +159,10 @@ int ba3c_train_grads_phase(ba3c_handle* h, void* stream, const float* params, co
 /* ba3c_train_grads_phase with the clipped-surrogate (PPO, Schulman et al. 2017) policy term in
  * place of the A3C one; every other launch, the phases 0-2 and their meaning, the scalars and
  * their scaling are ba3c_train_grads_phase's (the heads run in phase 1).
- * rows: fp32 [B][4], row n = {R, V_old, l_old, 0} — the return (the value target, the A3C
- * futurereward), the predictor's value when the action was taken and l_old =
- * log(pi_old(a) + 1e-6) (ba3c_sample_logp).  With p = softmax(z), lp = log(p + 1e-6) and the
- * current value V:
+ * rows: fp32 [B][4], row n = {R, V_old, l_old, w} — the return (the value target, the A3C
+ * futurereward), the predictor's value when the action was taken, l_old =
+ * log(pi_old(a) + 1e-6) (ba3c_sample_logp) and a caller-supplied advantage (read only with
+ * BA3C_PPO_ADV_FROM_ROW).  With p = softmax(z), lp = log(p + 1e-6) and the current value V:
  *   Adv  = R - V_old                                   (a constant of the sample)
  *   rho  = exp(lp[a] - l_old)
  *   s    = -min(rho Adv, clip(rho, 1 - clip_eps, 1 + clip_eps) Adv)
@@ -172,16 +172,8 @@ int ba3c_train_grads_phase(ba3c_handle* h, void* stream, const float* params, co
  * at rho = 1 and V_old = V it is ba3c_train_grads' gradient.  scalars[1] (policy_loss) is
  * sum_n s * 128 / B; scalars[4] (advantage) stays mean(V - R) with the current V.
  * ratio: fp32 [B] device memory, receives rho per sample; may be NULL.
- * Refused with BA3C_ERR_INVALID before any GPU call: rows NULL or not 16-byte aligned, ratio
- * given but not 16-byte aligned, clip_eps not in (0, 1) (a NaN included), phase outside 0..2,
- * then ba3c_train_grads_phase's own checks. */
-int ba3c_train_grads_ppo(ba3c_handle* h, void* stream, const float* params, const uint8_t* state,
-                         const int64_t* action, const float* rows, int32_t batch,
-                         float entropy_beta, float clip_eps, void* workspace, float* grads,
-                         double* scalars, float* ratio, int32_t phase);
-/* ba3c_train_grads_ppo with the two further pieces every PPO implementation carries (baselines
- * ppo2, CleanRL): a caller-supplied advantage and the clipped value loss.  Everything not named
- * here is ba3c_train_grads_ppo's: the launches, phases 0-2, rows, ratio, the scalars' scaling.
+ * The two further pieces every PPO implementation carries (baselines ppo2, CleanRL), both off
+ * at 0:
  *   flags & BA3C_PPO_ADV_FROM_ROW: Adv = rows[n][3] (ba3c_ppo_norm_adv writes it) instead of
  *     R - V_old, in s and in c; R and V_old keep their other uses.
  *   vclip_eps > 0: with d = V - V_old and Vc = V_old + sign(d) vclip_eps,
@@ -189,16 +181,22 @@ int ba3c_train_grads_ppo(ba3c_handle* h, void* stream, const float* params, cons
  *     and the value term of the cost and scalars[3] (value_loss) take (Vc - R)^2 where
  *     use_clipped, else (V - R)^2, i.e. 1/2 max((V - R)^2, (Vc - R)^2) per sample; dV is 0 where
  *     use_clipped, else (V - R) / B.  scalars[4] stays mean(V - R).  vclip_eps = 0: no clipping.
- * With vclip_eps = 0 and flags = 0 every output is ba3c_train_grads_ppo's, bit for bit.
- * Refused with BA3C_ERR_INVALID before any GPU call, in this order: ba3c_train_grads_ppo's rows,
- * ratio and clip_eps checks, vclip_eps negative or not finite (a NaN included), flags with a bit
- * other than BA3C_PPO_ADV_FROM_ROW, phase outside 0..2, then ba3c_train_grads_phase's checks. */
+ * Refused with BA3C_ERR_INVALID before any GPU call, in this order: rows NULL or not 16-byte
+ * aligned, ratio given but not 16-byte aligned, clip_eps not in (0, 1) (a NaN included),
+ * vclip_eps negative or not finite (a NaN included), flags with a bit other than
+ * BA3C_PPO_ADV_FROM_ROW, phase outside 0..2, then ba3c_train_grads_phase's checks. */
 #define BA3C_PPO_ADV_FROM_ROW 1u
 int ba3c_train_grads_ppo_ext(ba3c_handle* h, void* stream, const float* params, const uint8_t* state,
                              const int64_t* action, const float* rows, int32_t batch,
                              float entropy_beta, float clip_eps, float vclip_eps, uint32_t flags,
                              void* workspace, float* grads, double* scalars, float* ratio,
                              int32_t phase);
+/* ba3c_train_grads_ppo_ext with vclip_eps = 0 and flags = 0: the same call, launches, outputs and
+ * refusals (rows[n][3] is not read). */
+int ba3c_train_grads_ppo(ba3c_handle* h, void* stream, const float* params, const uint8_t* state,
+                         const int64_t* action, const float* rows, int32_t batch,
+                         float entropy_beta, float clip_eps, void* workspace, float* grads,
+                         double* scalars, float* ratio, int32_t phase);
 /* Per-minibatch advantage normalisation, in place on the n rows {R, V_old, l_old, .} of a PPO
  * step (fp32 [n][4], device): with Adv_i = (double)R_i - (double)V_old_i, mean = sum Adv / n and
  * the population std = sqrt(sum (Adv - mean)^2 / n) (two passes, fp64),

@@ -29,9 +29,9 @@ to the A3C step on identical batches at (B, F, S) = (32, 128, 4) and (2048, 512,
 method (medians of event-bracketed batches of steps, alternating), and ms per
 `ActorLearner.iterate` and samples/s on GridBoxing at 100 simulators with the A3C loop and with
 --ppo_clip 0.2 at 4 epochs x 4 minibatches; --ppo_only skips the environment tables.  With
---ppo_norm_adv and / or --ppo_vclip EPS the extended step (the normalisation launch and
-`ba3c_train_grads_ppo_ext`) and the normalisation launch alone are timed in the same alternation,
-and the loop once more with those settings.
+--ppo_norm_adv and / or --ppo_vclip EPS the extended step (the normalisation launch and the same
+PPO step with those settings on) and the normalisation launch alone are timed in the same
+alternation, and the loop once more with those settings.
 With --episodes also the episode log of the training simulators (`ba3c_episode_stats`,
 ba3c_amd.episodes) alone at 100, 4096 and 65536 simulators (one flag in a hundred set), by the same
 medians of event-bracketed batches, and ms per `ActorLearner.iterate` on GridBreakout at 100 and
@@ -219,8 +219,8 @@ def ppo_step_table(repeats, clip=0.2, norm_adv=False, vclip=0.0):
     clipped-surrogate loss on the same batch: rows = {R, the forward's value, sample_logp's logp,
     0} of the policy before the timed steps, so the ratios move as the steps train.
     norm_adv / vclip (--ppo_norm_adv / --ppo_vclip): also the extended step — the normalisation
-    launch (when asked for) and the step through ba3c_train_grads_ppo_ext — and the
-    normalisation launch alone, in the same alternation."""
+    launch (when asked for) and the same step, the same heads kernel, with those settings on —
+    and the normalisation launch alone, in the same alternation."""
     from ba3c_amd.model import Model
     from ba3c_amd.optimizer import AdamOptimizer
     from ba3c_amd.trainer import Ba3cTrainer, TrainConfig

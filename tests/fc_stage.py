@@ -242,7 +242,7 @@ def n_splits(g):
 
 def heads_form(F, A):
     """(FCH, AT) of the heads_kernel<FCH, NZ, AT, LOSS> that ba3c_capi.hip:launch_heads
-    launches for (F, A): FCH 64-lane feature chunks unrolled (0: the runtime loop), AT the
+    launches for (F, A) with either loss (A3C, PPO): FCH 64-lane feature chunks unrolled (0: the runtime loop), AT the
     compile-time action count (0: runtime)."""
     if A == 4 and 64 < F <= 128:
         return (2, 4)

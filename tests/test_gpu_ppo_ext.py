@@ -7,6 +7,7 @@ import torch
 
 from ba3c_amd import ppo
 from ba3c_amd._lib import PPO_ADV_FROM_ROW, SCALAR_NAMES
+from fc_stage import ALL_HEADS_FORMS, heads_form
 from oracle import ba3c_oracle as O
 from test_gpu_parity import FWD_TOL, GRAD_TOL, as64, case, dev, engine, gpu_decisions, rel
 from test_gpu_ppo import HEADS, _check_scalars, _lpa
@@ -62,16 +63,19 @@ def test_norm_adv_matches_the_rules(kind):
 
 # ---- the extended heads -------------------------------------------------------------------------
 def _ext(eng, state, action, rows, clip, vclip, flags, phase=0):
-    """ba3c_train_grads_ppo_ext as it is exported (the engine's method takes the plain entry when
-    both settings are off)."""
+    """ba3c_train_grads_ppo_ext as it is exported (the engine's method makes the same call);
+    vclip = None: ba3c_train_grads_ppo, the exported plain entry, which has neither setting."""
     from ba3c_amd import _lib
     from ba3c_amd.engine import _ptr, _stream
     B = state.shape[0]
     if eng.ratio is None:
         eng.ratio = torch.ones(eng.max_batch, dtype=torch.float32, device=eng.device)
-    _lib.check(eng.lib.ba3c_train_grads_ppo_ext(
-        eng.h, _stream(), _ptr(eng.params), _ptr(state), _ptr(action), _ptr(rows), B, BETA, clip, vclip,
-        flags, _ptr(eng._workspace(True)), _ptr(eng.grads), _ptr(eng.scalars), _ptr(eng.ratio), phase))
+    tail = (_ptr(eng._workspace(True)), _ptr(eng.grads), _ptr(eng.scalars), _ptr(eng.ratio), phase)
+    head = (eng.h, _stream(), _ptr(eng.params), _ptr(state), _ptr(action), _ptr(rows), B, BETA)
+    if vclip is None:
+        _lib.check(eng.lib.ba3c_train_grads_ppo(*head, clip, *tail))
+    else:
+        _lib.check(eng.lib.ba3c_train_grads_ppo_ext(*head, clip, vclip, flags, *tail))
     return eng.scalars
 
 
@@ -137,21 +141,35 @@ def test_ext_scalars_of_both_launch_forms(B):
     assert rel(eng.ratio[:B].cpu().numpy(), out["rho"]) < FWD_TOL
 
 
-@pytest.mark.parametrize("B", [32, 260])
-def test_ext_with_both_settings_off_is_the_ppo_form_bit_for_bit(B):
-    eng, params, state, action, cfg, h, V, rows, kinds, _ = _prepared(160 + B, B, A=4, F=128, S=4)
+# one configuration per heads instantiation (fc_stage.ALL_HEADS_FORMS), in launch_heads' order
+FORM_CASES = [dict(A=4, F=128, S=4), dict(A=4, F=512, S=1), dict(A=1, F=4, S=1), dict(A=18, F=128, S=4),
+              dict(A=4, F=192, S=4), dict(A=17, F=500, S=5), dict(A=31, F=516, S=3)]
+assert {heads_form(c["F"], c["A"]) for c in FORM_CASES} == ALL_HEADS_FORMS and len(FORM_CASES) == 7
+
+
+@pytest.mark.parametrize("B,cfgk", [pytest.param(32, FORM_CASES[0], id="32"),
+                                    pytest.param(260, FORM_CASES[0], id="260")]
+                         + [pytest.param(33, c, id="A%d_F%d_S%d" % (c["A"], c["F"], c["S"]))
+                            for c in FORM_CASES])    # 33: a partial last workgroup of 4 waves
+def test_ext_with_both_settings_off_is_the_ppo_form_bit_for_bit(B, cfgk):
+    """The plain entry is the extended one at (0, 0): the same bits from both exported symbols."""
+    eng, params, state, action, cfg, h, V, rows, kinds, _ = _prepared(160 + B, B, **cfgk)
     st, ac, rw = dev(state), dev(action), dev(rows)
-    eng.train_grads_ppo(st, ac, rw, EPS, entropy_beta=BETA)
+    _ext(eng, st, ac, rw, EPS, None, None)
     want = [eng.scalars.clone(), eng.ratio[:B].clone(), eng.grads.clone()]
     eng.grads.zero_()
     eng.ratio.zero_()
     _ext(eng, st, ac, rw, EPS, 0.0, 0)
     got = [eng.scalars.clone(), eng.ratio[:B].clone(), eng.grads.clone()]
     assert all(torch.equal(a, b) for a, b in zip(want, got))
-    # and each setting alone moves the gradient
+    # and each setting alone moves the gradient.  With one action p = 1 and dz = 0 whatever the
+    # advantage is: there the row's advantage moves the policy loss and leaves the gradient's bits.
     for vclip, flags in ((VCLIP, 0), (0.0, PPO_ADV_FROM_ROW)):
         _ext(eng, st, ac, rw, EPS, vclip, flags)
-        assert not torch.equal(eng.grads, want[2])
+        if flags and cfgk["A"] == 1:
+            assert torch.equal(eng.grads, want[2]) and not torch.equal(eng.scalars, want[0])
+        else:
+            assert not torch.equal(eng.grads, want[2])
 
 
 def test_ext_whole_gradient_matches_the_oracle_backward():

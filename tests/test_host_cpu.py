@@ -423,3 +423,60 @@ def test_bench_occupy_needs_full():
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--sync-path",
                         "--occupy", "16"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 2 and "--full" in r.stderr
+
+
+class RecordingEngine(OracleEngine):
+    """OracleEngine that logs each training call as (method, phase, id(rows), clip, vclip,
+    adv_from_row); fail_ppo_phase: the PPO call of that phase raises instead."""
+
+    def __init__(self, params):
+        super().__init__(params)
+        self.log, self.fail_ppo_phase = [], None
+        self.ratio = torch.ones(8)
+
+    def train_grads(self, state, action, R, entropy_beta=0.01, grads=None, phase=0):
+        self.log.append(("train_grads", phase, None, None, None, None))
+        return super().train_grads(state, action, R, entropy_beta, grads, phase)
+
+    def train_grads_ppo(self, state, action, rows, clip_eps, entropy_beta=0.01, grads=None,
+                        phase=0, ratio=True, vclip=0.0, adv_from_row=False):
+        self.log.append(("train_grads_ppo", phase, id(rows), clip_eps, vclip, adv_from_row))
+        if phase == self.fail_ppo_phase:
+            raise RuntimeError("the engine refused the call")
+        return super().train_grads(state, action, rows[:, 0].contiguous(), entropy_beta, grads, phase)
+
+
+def test_a_steps_loss_and_phase_reach_the_engine_and_do_not_outlive_the_step():
+    from ba3c_amd.model import Model
+    from ba3c_amd.optimizer import AdamOptimizer, SyncReplicasOptimizer
+    from ba3c_amd.trainer import Ba3cTrainer, TrainConfig
+    s, a, r = (torch.from_numpy(x) for x in _batch(3))
+    rows = torch.zeros(2, 4)
+    rows[:, 0] = r
+    ppo_args = (id(rows), 0.2, 0.3, True)
+    for bucketed, phases in ((True, [1, 2]), (False, [0])):
+        eng = RecordingEngine(O.init_params(16, 2, 4, seed=0, dtype=np.float32))
+        model = Model(num_actions=4, fc_neurons=16, fc_splits=2, batch_size=2, engine=eng)
+        adam = AdamOptimizer(1e-3, 0.8, 0.75, 1e-8)
+        tr = Ba3cTrainer(TrainConfig(model=model, optimizer=SyncReplicasOptimizer(adam) if bucketed else adam))
+        # (a) a PPO step: every phase of it through train_grads_ppo with the step's arguments
+        tr.train_step(s, a, None, rows=rows, clip=0.2, vclip=0.3, adv_from_row=True)
+        assert eng.log == [("train_grads_ppo", ph) + ppo_args for ph in phases]
+        # (b) the A3C step after it
+        del eng.log[:]
+        tr.train_step(s, a, r)
+        assert eng.log == [("train_grads", ph, None, None, None, None) for ph in phases]
+        # (c) a PPO step that dies in its first pass leaves nothing behind
+        del eng.log[:]
+        eng.fail_ppo_phase = phases[0]
+        with pytest.raises(RuntimeError, match="refused"):
+            tr.train_step(s, a, None, rows=rows, clip=0.2, vclip=0.3, adv_from_row=True)
+        assert eng.log == [("train_grads_ppo", phases[0]) + ppo_args]
+        del eng.log[:]
+        model.build_graph([s, a, r])               # the reference-shaped call: the whole A3C pass
+        tr.train_step(s, a, r)
+        assert eng.log == [("train_grads", ph, None, None, None, None) for ph in [0] + phases]
+        # (d) a PPO step is not captured
+        with pytest.raises(ValueError, match="PPO step"):
+            tr.capture_step(s, a, None, rows=rows, clip=0.2)
+        assert tr.global_step == 3
