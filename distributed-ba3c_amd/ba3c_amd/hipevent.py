@@ -50,6 +50,8 @@ def _hip():
 
 def _check(rc, what):
     if rc != 0:
+        # reported here; left in place, the runtime's last error fails torch's next call instead
+        _hip().hipGetLastError()
         raise RuntimeError("%s failed: %s" % (what, _hip().hipGetErrorString(rc).decode()))
 
 
@@ -135,9 +137,16 @@ def wait_stream(waiter, other, ev=None):
 
 class CuMaskedStream(object):
     """A HIP stream whose kernels may only use `n_cus` of the device's CUs
-    (hipExtStreamCreateWithCUMask), spread evenly over the CU numbering, as a torch stream
-    (`.stream`, torch.cuda.ExternalStream).  bench.py's configs[4] partition: the predictor's
-    forward on a subset of the CUs beside the learner's step."""
+    (hipExtStreamCreateWithCUMask), as a torch stream (`.stream`, torch.cuda.ExternalStream).
+    bench.py's configs[4] partition: the predictor's forward on a subset of the CUs beside the
+    learner's step.
+
+    The mask is its `n_cus` lowest bits.  The driver deals the mask's bits out round-robin,
+    first over the XCCs, then over an XCC's shader engines (bit i of an 8-XCC MI355X: XCC
+    i % 8, shader engine (i // 8) % 4), so the lowest bits are the even spread over both.  A
+    kernel's workgroups go to every XCC whatever the mask, and a driver may refuse a mask that
+    leaves an XCC without a CU (a stride over the bit numbering does: every 4th bit of 256 is
+    XCCs 0 and 4 alone); so may one with fewer CUs than XCCs, and that stays an error."""
 
     def __init__(self, n_cus, device=None):
         dev = torch.device(device or "cuda")
@@ -146,8 +155,7 @@ class CuMaskedStream(object):
             raise ValueError("n_cus must be in [1, %d]" % total)
         words = (total + 31) // 32
         mask = (ctypes.c_uint32 * words)()
-        for i in range(n_cus):
-            cu = (i * total) // n_cus
+        for cu in range(n_cus):
             mask[cu // 32] |= 1 << (cu % 32)
         self.n_cus = n_cus
         self._s = ctypes.c_void_p()
