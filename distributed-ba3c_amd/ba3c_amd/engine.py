@@ -215,6 +215,44 @@ class Ba3cEngine(object):
             _ptr(ratio), int(phase)))
         return self.scalars
 
+    # -- saliency (ba3c_amd.saliency) ------------------------------------------------------
+    _sal_grads = None   # input_grads' scratch for the backward pass's weight gradients, on first use
+
+    def _saliency_out(self, B, out, map):
+        if out is None:
+            out = torch.empty(B, 84, 84, 4, dtype=torch.float32, device=self.device)
+        if map is True:
+            map = torch.empty(B, 84, 84, dtype=torch.float32, device=self.device)
+        for t, shape in ((out, (B, 84, 84, 4)), (map, (B, 84, 84))):
+            assert t is None or (t.dtype == torch.float32 and tuple(t.shape) == shape and t.is_cuda
+                                 and t.is_contiguous())
+        return out, map
+
+    def conv0_input_grad(self, batch, out=None, map=None):
+        """conv0's input gradient alone (ba3c_conv0_input_grad) on the dp0 / c0 that the training
+        workspace of a `batch`-sized call holds.  map: None, True (allocate) or a float32
+        [B,84,84] tensor for sum_c |dX|.  -> (dX float32 [B,84,84,4], map or None)."""
+        out, map = self._saliency_out(batch, out, map)
+        _lib.check(self.lib.ba3c_conv0_input_grad(self.h, _stream(), _ptr(self.params),
+                                                  _ptr(self._workspace(True)), int(batch), _ptr(out),
+                                                  _ptr(map)))
+        return out, map
+
+    def input_grads(self, state, action, seeds, out=None, map=None):
+        """d(s_pi log pi(action) + s_v V) / d(state / 255) per sample (ba3c_input_grads): seeds
+        float32 [B, 2] = {s_pi, s_v}.  self.grads is not touched.  -> (dX, map) as
+        conv0_input_grad."""
+        B, action, _, ws = self._check_train(state, action, None)
+        assert seeds.dtype == torch.float32 and seeds.shape == (B, 2) and seeds.is_cuda \
+            and seeds.is_contiguous()
+        if self._sal_grads is None:
+            self._sal_grads = self.zeros_like_flat()
+        out, map = self._saliency_out(B, out, map)
+        _lib.check(self.lib.ba3c_input_grads(self.h, _stream(), _ptr(self.params), _ptr(state),
+                                             _ptr(action), _ptr(seeds), B, _ptr(ws),
+                                             _ptr(self._sal_grads), _ptr(out), _ptr(map)))
+        return out, map
+
     def occupy_cus(self, stream, n_cus, usec):
         """Diagnostic: hold `n_cus` CUs for `usec` microseconds on torch stream `stream`."""
         _lib.check(self.lib.ba3c_occupy_cus(ctypes.c_void_p(stream.cuda_stream), int(n_cus),

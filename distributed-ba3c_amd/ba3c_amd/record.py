@@ -14,7 +14,13 @@ rows[frame_steps[j]], with that decision's output in the HUD.
 
     python -m ba3c_amd.record --load CKPT -e GridBoxing-v0 --num_actions 18 --fc_neurons 128 \\
         --fc_splits 4 --episodes 3 --scale 3 --out DIR [--frame_skip 2-4 --sticky 0.25]
+        [--saliency v]
     python -m ba3c_amd.record --random -e GridBreakout-v0 --episodes 3 --out DIR
+
+`--saliency v` (or `pi`) adds a `saliency` array [T, 84, 84] to each trace: per decision, the
+newest frame's channel of |dV / dx| (or |d log pi(action) / dx|) of the state the policy saw
+(ba3c_amd.saliency), and tints the GIF's frames with it.  Without the flag a recording is what it
+was.
 
 Matches of two-player GridBoxing (ba3c_amd.duel) are recorded by `record_match`, along
 `duel.match`'s own decision path, as `MatchEpisode`s: the same trace with both sides' actions and
@@ -38,10 +44,11 @@ class Episode(object):
     """One recorded episode of `game` (a key of flags.GAMES) under `limit` and `skip` ((lo, hi,
     q16) of ba3c_amd.frameskip, or None: plain steps).  row0 int32 [16]; aux0 int32 [2] (None
     without skip); actions int64 [T]; rewards float64 [T]; probs float32 [T, A]; values float32
-    [T]; score, steps = T; frames uint8 [T', Hc*S, 84*S, 3]; frame_steps int64 [T']."""
+    [T]; score, steps = T; frames uint8 [T', Hc*S, 84*S, 3]; frame_steps int64 [T']; saliency
+    float32 [T, 84, 84] or None (record_episodes' `saliency`)."""
 
     def __init__(self, game, limit, skip, row0, aux0, actions, rewards, probs, values, score,
-                 frames, frame_steps):
+                 frames, frame_steps, saliency=None):
         assert game in MODULES and (aux0 is not None) == (skip is not None)
         self.game, self.limit = game, int(limit)
         self.skip = tuple(int(v) for v in skip) if skip is not None else None
@@ -56,6 +63,22 @@ class Episode(object):
         self.frames = np.asarray(frames, np.uint8)
         self.frame_steps = np.asarray(frame_steps, np.int64).reshape(-1)
         assert self.frames.shape[0] == self.frame_steps.shape[0]
+        self.saliency = (np.asarray(saliency, np.float32).reshape(self.steps, 84, 84)
+                         if saliency is not None else None)
+
+    def tinted_frames(self):
+        """The frames with each decision's saliency added to the red channel of the game part
+        (scaled to the episode's largest value); without saliency: the frames."""
+        if self.saliency is None or not self.frames.shape[0]:
+            return self.frames
+        S = self.frames.shape[2] // 84
+        top = float(self.saliency.max())
+        heat = self.saliency[self.frame_steps] * (255.0 / top if top > 0 else 0.0)
+        heat = np.repeat(np.repeat(heat, S, axis=1), S, axis=2)
+        out = self.frames.copy()
+        red = out[:, :84 * S, :, 0].astype(np.float32) + heat
+        out[:, :84 * S, :, 0] = np.minimum(red, 255.0).astype(np.uint8)
+        return out
 
     def replay(self):
         """Run the CPU oracle from row0 (and aux0) over `actions`.  -> (rows int32 [T+1, 16]
@@ -89,6 +112,8 @@ class Episode(object):
                    steps=np.int64(self.steps))
         if self.skip is not None:
             out["skip"] = np.asarray(self.skip, np.int64)
+        if self.saliency is not None:
+            out["saliency"] = self.saliency
         np.savez_compressed(path_stem + ".npz", **out)
         files = [path_stem + ".npz"]
         try:
@@ -96,7 +121,7 @@ class Episode(object):
         except ImportError:
             return files
         if self.frames.shape[0]:
-            images = [Image.fromarray(f) for f in self.frames]
+            images = [Image.fromarray(f) for f in self.tinted_frames()]
             images[0].save(path_stem + ".gif", save_all=True, append_images=images[1:],
                            duration=gif_ms, loop=0)
             files.append(path_stem + ".gif")
@@ -108,7 +133,8 @@ class Episode(object):
             d = {k: f[k] for k in f.files}
         skip = tuple(d["skip"].tolist()) if "skip" in d else None
         return cls(str(d["game"]), int(d["limit"]), skip, d["row0"], d.get("aux0"), d["actions"],
-                   d["rewards"], d["probs"], d["values"], int(d["score"]), d["frames"], d["frame_steps"])
+                   d["rewards"], d["probs"], d["values"], int(d["score"]), d["frames"], d["frame_steps"],
+                   d.get("saliency"))
 
 
 class _Open(object):
@@ -117,16 +143,18 @@ class _Open(object):
     def __init__(self, row0, aux0):
         self.row0, self.aux0 = row0, aux0
         self.actions, self.rewards, self.probs, self.values = [], [], [], []
-        self.frames, self.frame_steps = [], []
+        self.frames, self.frame_steps, self.saliency = [], [], []
 
 
 def record_episodes(engine, game, n_episodes, n_envs=None, seed=0, limit=DEFAULT_LIMIT, frame_skip=1,
-                    sticky=0.0, policy=None, scale=3, hud=True, every=1, max_frames=2000):
+                    sticky=0.0, policy=None, scale=3, hud=True, every=1, max_frames=2000, saliency=None):
     """Play `n_envs` evaluation players of `game` until `n_episodes` episodes have finished and
     return them as Episodes, in the order they finished (those finishing in the same step as the
     n_episodes-th included, as eval_with_envs counts them).  policy(state) -> probs [E, A]
     replaces the engine's forward (values are then recorded as 0).  Every `every`-th decision's
-    frame is kept, at most `max_frames` per episode; hud: draw the policy's output under it."""
+    frame is kept, at most `max_frames` per episode; hud: draw the policy's output under it.
+    saliency: None, "v" or "pi" — every decision's map of the newest frame (ba3c_amd.saliency:
+    value_map, or policy_map of the action handed to the env) on the engine's own network."""
     import torch
 
     from .evaluate import EvalPlayers
@@ -134,6 +162,7 @@ def record_episodes(engine, game, n_episodes, n_envs=None, seed=0, limit=DEFAULT
     from .view import ACTIONS, HUD_H, W, check_scale, hud_from_policy
     n_envs = int(n_envs) if n_envs else max(1, min(int(n_episodes), 20, engine.max_batch))
     assert n_episodes >= 1 and 1 <= n_envs <= engine.max_batch and every >= 1 and max_frames >= 0
+    assert saliency in (None, "v", "pi")
     scale = check_scale(scale)
     dev = engine.device
     env = GAMES[game][0](n_envs, seed=seed, limit=limit, device=dev, frame_skip=frame_skip,
@@ -161,6 +190,12 @@ def record_episodes(engine, game, n_episodes, n_envs=None, seed=0, limit=DEFAULT
             for j, e in enumerate(want):
                 live[e].frame_steps.append(len(live[e].actions))
                 live[e].frames.append(frames[j])
+        if saliency:
+            from . import saliency as sal
+            maps = (sal.value_map(engine, hist.state, newest=True) if saliency == "v"
+                    else sal.policy_map(engine, hist.state, act, newest=True)).cpu().numpy()
+            for e in range(n_envs):
+                live[e].saliency.append(maps[e])
         for e in range(n_envs):
             ep = live[e]
             ep.actions.append(act_h[e])
@@ -183,7 +218,8 @@ def record_episodes(engine, game, n_episodes, n_envs=None, seed=0, limit=DEFAULT
                 frames = (np.stack(ep.frames) if ep.frames
                           else np.zeros((0, hc * scale, W * scale, 3), np.uint8))
                 done.append(Episode(game, limit, env.skip, ep.row0, ep.aux0, ep.actions, ep.rewards,
-                                    np.stack(ep.probs), ep.values, scores[e], frames, ep.frame_steps))
+                                    np.stack(ep.probs), ep.values, scores[e], frames, ep.frame_steps,
+                                    np.stack(ep.saliency) if saliency else None))
             start(ended)                      # the rows have auto-reset: the next episodes' row0
     return done
 
@@ -357,6 +393,8 @@ def main(argv=None):
     p.add_argument("--limit", type=int, default=DEFAULT_LIMIT, help="LimitLengthPlayer's game steps")
     p.add_argument("--every", type=int, default=1, help="keep every N-th decision's frame")
     p.add_argument("--max_frames", type=int, default=2000)
+    p.add_argument("--saliency", choices=("v", "pi"), default=None,
+                   help="store each decision's input-gradient saliency map (value / chosen action)")
     args = resolve(p.parse_args(argv))
     if args.environment not in GAMES:
         raise SystemExit("recording needs an on-device game: pass -e %s" % " or -e ".join(sorted(GAMES)))
@@ -371,7 +409,8 @@ def main(argv=None):
     episodes = record_episodes(model.engine, args.environment, args.episodes,
                                seed=0 if args.seed is None else args.seed, limit=args.limit,
                                frame_skip=args.frame_skip, sticky=args.sticky, policy=policy,
-                               scale=args.scale, every=args.every, max_frames=args.max_frames)
+                               scale=args.scale, every=args.every, max_frames=args.max_frames,
+                               saliency=args.saliency)
     files = []
     for i, ep in enumerate(episodes):
         files += ep.save(os.path.join(args.out, "episode_%03d" % i))

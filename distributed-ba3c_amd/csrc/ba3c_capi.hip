@@ -23,6 +23,7 @@
 #include "ba3c_boxing.h"
 #include "ba3c_breakout.h"
 #include "ba3c_conv.h"
+#include "ba3c_conv0d.h"
 #include "ba3c_conv3.h"
 #include "ba3c_duel.h"
 #include "ba3c_envview.h"
@@ -201,6 +202,10 @@ struct Workspace {
   unsigned long long* relu;
   uint32_t* amax;  // [AMAX_N][1 + max_batch]: max |x| of split operands (global, per image)
   int* wexp;       // [8]: weight scale exponents (wprep jobs WJ_*, conv0 = WX_CONV0)
+  // conv0's input gradient (ba3c_conv0d.h): T's fragments, its scale exponent, [B][NCH] max partials
+  uint4* c0d_tb;
+  int* c0d_wexp;
+  uint32_t* c0d_amax;
   size_t bytes;
   uint32_t* am(int t, const ba3c_handle* h) const { return amax + (size_t)t * (1 + h->cfg.max_batch); }
 };
@@ -334,6 +339,10 @@ Workspace carve(const ba3c_handle* h, void* base, int B, bool train) {
     w.part_2 = (float*)take(ps.conv2 * 4);
     w.part_1 = (float*)take(ps.conv1 * 4);
     w.part0 = (float*)take(max_partials0(h, B) * 4);
+    // last, so that every other region keeps its offset
+    w.c0d_tb = (uint4*)take((size_t)Conv0D::TB_U4 * 16);
+    w.c0d_wexp = (int*)take(4);
+    w.c0d_amax = (uint32_t*)take(Bz * Conv0D::NCH * 4);
   }
   w.bytes = off;
   return w;
@@ -1080,7 +1089,7 @@ void launch_heads(hipStream_t s, int B, const HeadsArgsOf<LOSS>& a) {
 int run_heads(ba3c_handle* h, hipStream_t s, const float* prm, const Workspace& w, int B,
               const int64_t* action, const float* R, float beta, float explore, bool train,
               float* probs, float* probsT, float* value, double* scalars = nullptr,
-              bool defer_scalars = false, const PpoArgs* ppo = nullptr) {
+              bool defer_scalars = false, const PpoArgs* ppo = nullptr, const float* seeds = nullptr) {
   HeadsArgsPpo a{};
   if (ppo) {
     a.rows = reinterpret_cast<const float4*>(ppo->rows);
@@ -1124,7 +1133,12 @@ int run_heads(ba3c_handle* h, hipStream_t s, const float* prm, const Workspace& 
   a.invB = 1.0f / (float)B;
   {
     ProbeScope ps(h, s, BA3C_K_HEADS);
-    if (ppo && train) launch_heads<LOSS_PPO>(s, B, a);
+    if (seeds && train) {   // the seed form (ba3c_input_grads): no loss, no scalars
+      HeadsArgsSeed sa{};
+      static_cast<HeadsArgs&>(sa) = a;
+      sa.seeds = reinterpret_cast<const float2*>(seeds);
+      launch_heads<LOSS_SEED>(s, B, sa);
+    } else if (ppo && train) launch_heads<LOSS_PPO>(s, B, a);
     else launch_heads<LOSS_A3C>(s, B, a);
   }
   HIP_TRY(hipGetLastError());
@@ -1136,6 +1150,17 @@ int run_heads(ba3c_handle* h, hipStream_t s, const float* prm, const Workspace& 
     hipLaunchKernelGGL(scalars_kernel, dim3(1), dim3(256), 0, s, w.terms, B, beta, w.relu, scalars);
     HIP_TRY(hipGetLastError());
   }
+  return BA3C_OK;
+}
+
+// conv0's input gradient on the dP0 / c0 of `w`: the prep launch (T and the per-image maxima of
+// dP0, so the kernel depends on no producer), then persistent workgroups over (image, band) pairs
+int run_conv0d(ba3c_handle* h, hipStream_t s, const float* prm, const Workspace& w, int B, float* dstate,
+               float* map) {
+  const float* W0 = prm + h->tensors[h->idx_conv[0]].offset;
+  HIP_TRY(launch_conv0d_prep(s, Conv0DPrepArgs{W0, w.dp0, w.c0, w.c0d_tb, w.c0d_wexp, w.c0d_amax, B}));
+  const int grid = std::min(B * Conv0D::NBANDS, 2 * h->cus);
+  HIP_TRY(launch_conv0d(grid, s, Conv0DArgs{w.dp0, w.c0, w.c0d_tb, w.c0d_wexp, w.c0d_amax, dstate, map, B}));
   return BA3C_OK;
 }
 
@@ -1555,6 +1580,40 @@ int ba3c_train_grads_ppo(ba3c_handle* h, void* stream, const float* params, cons
                          double* scalars, float* ratio, int32_t phase) {
   return ba3c_train_grads_ppo_ext(h, stream, params, state, action, rows, batch, entropy_beta, clip_eps,
                                   0.f, 0, workspace, grads, scalars, ratio, phase);
+}
+
+int ba3c_conv0_input_grad(ba3c_handle* h, void* stream, const float* params, void* workspace,
+                          int32_t batch, float* dstate, float* map) {
+  if (!h || !check_ptr(params) || !check_ptr(workspace) || !check_ptr(dstate) || (map && !check_ptr(map)))
+    return fail(BA3C_ERR_INVALID, "null or misaligned pointer");
+  if (batch < 1 || batch > h->cfg.max_batch) return fail(BA3C_ERR_INVALID, "batch out of range");
+  if (h->cfg.channels != 4) return fail(BA3C_ERR_INVALID, "saliency needs channels == 4");
+  return run_conv0d(h, static_cast<hipStream_t>(stream), params, carve(h, workspace, batch, true), batch,
+                    dstate, map);
+}
+
+int ba3c_input_grads(ba3c_handle* h, void* stream, const float* params, const uint8_t* state,
+                     const int64_t* action, const float* seeds, int32_t batch, void* workspace,
+                     float* grads_scratch, float* dstate, float* map) {
+  if (!h || !check_ptr(params) || !check_ptr(state) || !action || !check_ptr(seeds) || !check_ptr(workspace) ||
+      !check_ptr(grads_scratch) || !check_ptr(dstate) || (map && !check_ptr(map)))
+    return fail(BA3C_ERR_INVALID, "null or misaligned pointer");
+  if (batch < 1 || batch > h->cfg.max_batch) return fail(BA3C_ERR_INVALID, "batch out of range");
+  if (h->cfg.channels != 4) return fail(BA3C_ERR_INVALID, "saliency needs channels == 4");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  CHECK(ensure_side_stream(h, s));
+  Workspace w = carve(h, workspace, batch, true);
+  const LaunchPlan pl = plan_launches(h->sw, batch, 4, h->cus, true);
+  std::memset(h->merged, 0, sizeof(h->merged));
+  if (!h->band) HIP_TRY(hipMemsetAsync(w.relu, 0, RELU_WORDS * 8, s));
+  // the training-mode forward (codes, ReLU masks), the seed heads in place of a loss, the ordinary
+  // backward pass (its weight gradients go to grads_scratch), then conv0's input gradient
+  CHECK(run_forward<4>(h, s, pl, params, state, batch, w, true));
+  h->pend_scalars = false;
+  CHECK(run_heads(h, s, params, w, batch, action, nullptr, 0.f, 1.0f, true, nullptr, nullptr, nullptr, nullptr,
+                  false, nullptr, seeds));
+  CHECK(BackwardPass<4>(h, s, pl, w, params, state, grads_scratch, batch, 0).run());
+  return run_conv0d(h, s, params, w, batch, dstate, map);
 }
 
 int ba3c_ppo_norm_adv(void* stream, float* rows, int32_t n, double* stats) {

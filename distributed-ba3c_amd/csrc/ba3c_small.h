@@ -48,8 +48,13 @@ __device__ __forceinline__ unsigned long long ld_agent(const unsigned long long*
 //   vclip_eps > 0: the clipped value loss.  d = V - V_old, Vc = V_old + sign(d) vclip_eps,
 //     use_clipped = |d| > vclip_eps and (Vc - R)^2 > (V - R)^2   (a tie is unclipped);
 //     terms[n][2] = use_clipped ? (Vc - R)^2 : (V - R)^2,  dV = use_clipped ? 0 : (V - R) / B.
+//
+// LOSS_SEED: no loss.  The launch differentiates, per sample, J_n = s_pi log pi(a_n) + s_v V with
+// the caller's seeds[n] = {s_pi, s_v} (ba3c_input_grads; ba3c_amd/saliency.py states it):
+//   dz_k = s_pi ([k == a] - p_k),  dV = s_v
+// with no 1/B, no 1e-6, no entropy term, no terms row and no scalars; dh follows as above.
 // ---------------------------------------------------------------------------------------
-constexpr int LOSS_A3C = 0, LOSS_PPO = 1;
+constexpr int LOSS_A3C = 0, LOSS_PPO = 1, LOSS_SEED = 2;
 struct HeadsArgs {
   float* h;
   const float* piW;
@@ -87,14 +92,71 @@ struct HeadsArgsPpo : HeadsArgs {
   float vclip_eps;           // 0: no value clipping
   unsigned flags;
 };
+// The LOSS_SEED instantiations' arguments: HeadsArgs and the seeds (R is not read)
+struct HeadsArgsSeed : HeadsArgs {
+  const float2* seeds;       // [B] {s_pi, s_v}
+};
 template <int LOSS>
-using HeadsArgsOf = std::conditional_t<LOSS == LOSS_PPO, HeadsArgsPpo, HeadsArgs>;
+using HeadsArgsOf = std::conditional_t<LOSS == LOSS_PPO, HeadsArgsPpo,
+                                       std::conditional_t<LOSS == LOSS_SEED, HeadsArgsSeed, HeadsArgs>>;
 
 // The per-sample head arithmetic runs in fp64: the softmax gradient
 // p_k (g_k - sum_j p_j g_j) cancels catastrophically when the policy saturates, and fp64 here
 // costs nothing measurable (F*(A+1) FMAs per sample) while keeping the fp32 stored results
 // within rounding of the exact values.
 __device__ __forceinline__ double wave_max_d(double v, int w = 64) { return wave_reduce_d(v, OpMax{}, w); }
+
+// The tail every training form shares: the [dz | dV | 0...] row of the head weight-gradient
+// product, and dh_f = sum_k dz_k W_pi[f][k] + dV W_v[f] (x (h_f > 0) for the legacy ReLU FC) from
+// the sample's dz (lane a < A: dz_a) and dV.  wpre / hv32: heads_sample's preloaded weights and
+// stored h values (PRE / FCH > 0).
+template <int FCH, int AT, bool PRE, class Args, class WPre, class HV>
+__device__ __forceinline__ void heads_dh(const Args& p, int n, int lane, int A, double dz, double dV,
+                                         const float* hn, const WPre& wpre, const HV& hv32) {
+  constexpr int NA = AT ? AT : MAXA;
+  // [dz | dV | 0...] row for the head weight-gradient product
+  if (lane < MAXA) p.dzv[(size_t)n * MAXA + lane] = (float)(lane == A ? dV : dz);
+  double dza[NA];
+#pragma unroll
+  for (int a = 0; a < NA; ++a) {
+    dza[a] = 0.0;
+    if (AT || a < A) {                               // uniform branch: A broadcasts only
+      const unsigned long long u = __double_as_longlong(dz);
+      const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)u, a), hi = __builtin_amdgcn_readlane((uint32_t)(u >> 32), a);
+      dza[a] = __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+    }
+  }
+  float* dhn = p.dh + (size_t)n * p.F;
+  auto dh_one = [&](int f) {
+    const float* wr = p.piW + (size_t)f * A;
+    double g = dV * (double)p.vW[f];
+#pragma unroll
+    for (int a = 0; a < NA; ++a)
+      if (AT || a < A) g = fma(dza[a], (double)wr[a], g);
+    if (p.legacy && !(hn[f] > 0.f)) g = 0.0;
+    dhn[f] = (float)g;
+  };
+  if constexpr (PRE) {
+    // the preloaded weights; the legacy ReLU mask from the h values this lane stored
+#pragma unroll
+    for (int i = 0; i < FCH; ++i) {
+      const int f = lane + 64 * i;
+      double g = dV * (double)wpre[i][AT];
+#pragma unroll
+      for (int a = 0; a < AT; ++a) g = fma(dza[a], (double)wpre[i][a], g);
+      if (f < p.F) {
+        if (p.legacy && !(hv32[i] > 0.f)) g = 0.0;
+        dhn[f] = (float)g;
+      }
+    }
+  } else if constexpr (FCH > 0) {
+#pragma unroll
+    for (int i = 0; i < FCH; ++i)
+      if (lane + 64 * i < p.F) dh_one(lane + 64 * i);
+  } else {
+    for (int f = lane; f < p.F; f += 64) dh_one(f);
+  }
+}
 
 // One wave per sample; after the dot products lane a < A owns action a, so the softmax /
 // log / gradient run once per lane (one exp and one log per lane instead of MAXA of each,
@@ -133,7 +195,8 @@ __device__ __forceinline__ void heads_sample(const HeadsArgsOf<LOSS>& p, int n, 
   float bpre[PRE ? AT + 1 : 1];                  // pi biases, v bias
   float blg[PRE ? FCH : 1];                      // legacy FC bias of the lane's features
   float Rpre = 0.f;
-  constexpr bool ROWS = LOSS != LOSS_A3C;            // LOSS_PPO: the sample's row replaces R
+  constexpr bool ROWS = LOSS == LOSS_PPO;            // LOSS_PPO: the sample's row replaces R
+  constexpr bool SEED = LOSS == LOSS_SEED;           // LOSS_SEED: no R at all
   float4 rowpre = make_float4(0.f, 0.f, 0.f, 0.f);   // one 16-byte load
   int apre = 0;
   float hv32[FCH > 0 ? FCH : 1];
@@ -161,7 +224,7 @@ __device__ __forceinline__ void heads_sample(const HeadsArgsOf<LOSS>& p, int n, 
     for (int a = 0; a < AT; ++a) bpre[a] = p.pib[a];
     bpre[AT] = p.vb[0];
     if constexpr (ROWS) rowpre = p.rows[n];
-    else Rpre = *(p.train ? p.R + n : p.pib);
+    else if constexpr (!SEED) Rpre = *(p.train ? p.R + n : p.pib);
     // the action's low word (actions are small and non-negative)
     apre = *(p.train ? reinterpret_cast<const int*>(p.action + n) : reinterpret_cast<const int*>(p.pib));
 #pragma unroll
@@ -281,6 +344,14 @@ __device__ __forceinline__ void heads_sample(const HeadsArgsOf<LOSS>& p, int n, 
   if (p.value && lane == 0) p.value[n] = (float)V;
   if (!p.train) return;
 
+  if constexpr (SEED) {
+    // dz, dV from the sample's seeds; dh through the same code as the losses' (below)
+    const float2 sd = p.seeds[n];
+    const int act = (int)(PRE ? apre : p.action[n]);
+    const double dz = mine ? (double)sd.x * ((lane == act ? 1.0 : 0.0) - pr) : 0.0;
+    heads_dh<FCH, AT, PRE>(p, n, lane, A, dz, (double)sd.y, hn, wpre, hv32);
+    return;
+  }
   if constexpr (ROWS && !PRE) rowpre = p.rows[n];
   const double Rn = ROWS ? (double)rowpre.x : PRE ? (double)Rpre : (double)p.R[n];
   const int act = (int)(PRE ? apre : p.action[n]);
@@ -316,48 +387,7 @@ __device__ __forceinline__ void heads_sample(const HeadsArgsOf<LOSS>& p, int n, 
     use_clipped = ve > 0.0 && fabs(d) > ve && csq > (V - Rn) * (V - Rn);
   }
   const double dV = LOSS == LOSS_PPO && use_clipped ? 0.0 : (V - Rn) * invB;
-  // [dz | dV | 0...] row for the head weight-gradient product
-  if (lane < MAXA) p.dzv[(size_t)n * MAXA + lane] = (float)(lane == A ? dV : dz);
-  double dza[NA];
-#pragma unroll
-  for (int a = 0; a < NA; ++a) {
-    dza[a] = 0.0;
-    if (AT || a < A) {                               // uniform branch: A broadcasts only
-      const unsigned long long u = __double_as_longlong(dz);
-      const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)u, a), hi = __builtin_amdgcn_readlane((uint32_t)(u >> 32), a);
-      dza[a] = __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-    }
-  }
-  float* dhn = p.dh + (size_t)n * p.F;
-  auto dh_one = [&](int f) {
-    const float* wr = p.piW + (size_t)f * A;
-    double g = dV * (double)p.vW[f];
-#pragma unroll
-    for (int a = 0; a < NA; ++a)
-      if (AT || a < A) g = fma(dza[a], (double)wr[a], g);
-    if (p.legacy && !(hn[f] > 0.f)) g = 0.0;
-    dhn[f] = (float)g;
-  };
-  if constexpr (PRE) {
-    // the preloaded weights; the legacy ReLU mask from the h values this lane stored
-#pragma unroll
-    for (int i = 0; i < FCH; ++i) {
-      const int f = lane + 64 * i;
-      double g = dV * (double)wpre[i][AT];
-#pragma unroll
-      for (int a = 0; a < AT; ++a) g = fma(dza[a], (double)wpre[i][a], g);
-      if (f < p.F) {
-        if (p.legacy && !(hv32[i] > 0.f)) g = 0.0;
-        dhn[f] = (float)g;
-      }
-    }
-  } else if constexpr (FCH > 0) {
-#pragma unroll
-    for (int i = 0; i < FCH; ++i)
-      if (lane + 64 * i < p.F) dh_one(lane + 64 * i);
-  } else {
-    for (int f = lane; f < p.F; f += 64) dh_one(f);
-  }
+  heads_dh<FCH, AT, PRE>(p, n, lane, A, dz, dV, hn, wpre, hv32);
   if (lane < NTERMS) {
     double t = 0.0;
     t = lane == 0 ? t0 : t;

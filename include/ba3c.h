@@ -197,6 +197,30 @@ int ba3c_train_grads_ppo(ba3c_handle* h, void* stream, const float* params, cons
                          const int64_t* action, const float* rows, int32_t batch,
                          float entropy_beta, float clip_eps, void* workspace, float* grads,
                          double* scalars, float* ratio, int32_t phase);
+/* Input-gradient saliency (no reference counterpart; ba3c_amd/saliency.py states the rules and is
+ * the oracle).  ba3c_conv0_input_grad runs conv0's input gradient alone, on the dP0 and the
+ * argmax codes c0 that the TRAINING workspace of a `batch`-sized call holds (ba3c_workspace_tensor):
+ * with dY[y, x, o] = dP0[y>>1, x>>1, o] where c0[y>>1, x>>1, o] == 2 (y&1) + (x&1), else 0,
+ *   dstate[b, y, x, c] = sum_{ky, kx in 0..4, o} dY[b, y-ky, x-kx, o] conv0/W[ky, kx, c, o]
+ * for 0 <= y, x < 84, c < 4 (fp32 [B,84,84,4]): the gradient with respect to the float input the
+ * network sees, state / 255.  Only the 4 real input channels of conv0/W are read.  map (fp32
+ * [B,84,84], may be NULL) receives sum_c |dstate|.  Two launches (weight / maxima prep, the
+ * kernel); an image's result does not depend on its slot or its batch, and an all-zero dP0 image
+ * gives exact zeros.
+ * ba3c_input_grads runs the training-mode forward of `state`, differentiates per sample
+ *   J_n = s_pi log pi(a_n | x_n) + s_v V(x_n),   seeds[n] = {s_pi, s_v} (fp32 [B][2])
+ * (dlogits = s_pi (onehot(a_n) - p), dV = s_v: no 1/B, no loss) through the ordinary backward
+ * pass, whose weight gradients land in grads_scratch (a flat gradient buffer of the caller's,
+ * fully overwritten), and then ba3c_conv0_input_grad's kernel: dstate = dJ_n / d(state_n / 255).
+ * Both refuse, before any GPU call and in this order (BA3C_ERR_INVALID): a null handle or a null
+ * or not 16-byte aligned pointer (map only when given; action only when null); a batch outside
+ * [1, max_batch]; channels != 4 ("saliency needs channels == 4"). */
+int ba3c_conv0_input_grad(ba3c_handle* h, void* stream, const float* params, void* workspace,
+                          int32_t batch, float* dstate, float* map);
+int ba3c_input_grads(ba3c_handle* h, void* stream, const float* params, const uint8_t* state,
+                     const int64_t* action, const float* seeds, int32_t batch, void* workspace,
+                     float* grads_scratch, float* dstate, float* map);
+
 /* Per-minibatch advantage normalisation, in place on the n rows {R, V_old, l_old, .} of a PPO
  * step (fp32 [n][4], device): with Adv_i = (double)R_i - (double)V_old_i, mean = sum Adv / n and
  * the population std = sqrt(sum (Adv - mean)^2 / n) (two passes, fp64),

@@ -1,0 +1,61 @@
+"""conv0's input gradient: ms per ba3c_conv0_input_grad call (prep launch +
+kernel) on the dp0 a training pass left at B = 1, 32 and 2048 — HIP events around batches of
+calls after warm-up, five rounds, without and with the map output — its fraction of the fp16x3
+path peak priced on the algorithmic 45.16 MFLOP per image, and conv1's input gradient at the same
+batch (the BA3C_K_CONV1_DGRAD probe inside train_grads; at small batches that kernel shares a
+launch the probe does not bracket: 0 launches).  One JSON line per batch.
+    python scripts/saliency_time.py"""
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "distributed-ba3c_amd")]
+from ba3c_amd.engine import Ba3cEngine
+from oracle import ba3c_oracle as O
+
+PEAK = 838.9e12                      # fp16x3 path, fp32-equivalent
+FLOP = 2 * 7056 * 4 * 800            # algorithmic, per image
+out = {}
+for B, F, S in ((1, 128, 4), (32, 128, 4), (2048, 512, 1)):
+    rs = np.random.RandomState(B)
+    eng = Ba3cEngine(num_actions=4, fc_neurons=F, fc_splits=S, max_batch=B)
+    eng.load_params(O.init_params(F, S, 4, seed=7, dtype=np.float32))
+    st = torch.from_numpy(rs.randint(0, 256, size=(B, 84, 84, 4)).astype(np.uint8)).cuda()
+    ac = torch.from_numpy(rs.randint(0, 4, size=B).astype(np.int64)).cuda()
+    R = torch.from_numpy(rs.normal(size=B).astype(np.float32)).cuda()
+    eng.probe_enable("conv1_dgrad")
+    for _ in range(30):
+        eng.train_grads(st, ac, R)
+    torch.cuda.synchronize()
+    eng.probe_read()
+    for _ in range(50):
+        eng.train_grads(st, ac, R)
+    ms1, n1 = eng.probe_read()
+    merged = eng.kernel_merged("conv1_dgrad")
+    eng.probe_enable(None)
+    dx = torch.empty(B, 84, 84, 4, device="cuda")
+    mp = torch.empty(B, 84, 84, device="cuda")
+    reps = 200 if B < 2048 else 40
+    res = {}
+    for name, m in (("dx", None), ("dx+map", mp)):
+        for _ in range(20):
+            eng.conv0_input_grad(B, out=dx, map=m)
+        rounds = []
+        for _ in range(5):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                eng.conv0_input_grad(B, out=dx, map=m)
+            e1.record()
+            torch.cuda.synchronize()
+            rounds.append(e0.elapsed_time(e1) / reps)
+        res[name] = sorted(rounds)
+    med = res["dx"][2]
+    out[B] = dict(conv0d_ms=res, frac_fp16x3_peak=B * FLOP / (med * 1e-3) / PEAK,
+                  conv1_dgrad_ms=ms1 / max(n1, 1), conv1_dgrad_launches=n1, conv1_dgrad_merged=merged)
+    print(B, json.dumps(out[B]), flush=True)
+    del eng
