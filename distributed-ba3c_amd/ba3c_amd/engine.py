@@ -253,6 +253,38 @@ class Ba3cEngine(object):
                                              _ptr(self._sal_grads), _ptr(out), _ptr(map)))
         return out, map
 
+    # -- perturbation saliency (ba3c_amd.perturb) -------------------------------------------
+    _perturbed = None   # perturb_maps' scratch: one forward batch of perturbed states, on first use
+
+    def perturb_maps(self, state, which, newest=False, grid=None):
+        """The perturbation-saliency map of each state [B,84,84,4] (uint8, device): `which` is
+        "v" (S_v) or "pi" (S_pi) of ba3c_amd.perturb; newest: blur only the newest frame.  The
+        B * 289 perturbed states are made (ba3c_perturb_states) and forwarded in chunks of at most
+        max_batch rows into one outputs buffer, which ba3c_perturb_scores turns into the maps; the
+        host reads nothing on the way, and the map does not depend on max_batch.  grid: an
+        optional float64 [B,17,17] device tensor for the raw scores.  -> float32 [B,84,84]."""
+        from .perturb import GRID, NC, WHICH
+        if self.channels != 4:
+            raise ValueError("perturb_maps needs channels == 4 (an engine of %d)" % self.channels)
+        B, A, N = self._check_state(state), self.num_actions, state.shape[0] * NC
+        assert grid is None or (grid.dtype == torch.float64 and tuple(grid.shape) == (B, GRID, GRID)
+                                and grid.is_cuda and grid.is_contiguous())
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.device)
+        probs0, _, value0 = self.forward(state)
+        rows = min(self.max_batch, N)
+        if self._perturbed is None or self._perturbed.shape[0] < rows:
+            self._perturbed = torch.empty(rows, 84, 84, 4, dtype=torch.uint8, device=self.device)
+        probs, probsT, value, out = new(N, A), new(rows, A), new(N), new(B, 84, 84)
+        for first in range(0, N, rows):
+            count = min(rows, N - first)
+            _lib.check(self.lib.ba3c_perturb_states(_stream(), _ptr(state), B, first, count,
+                                                    1 if newest else 0, _ptr(self._perturbed)))
+            self.forward(self._perturbed[:count], out=(probs[first:first + count], probsT[:count],
+                                                       value[first:first + count]))
+        _lib.check(self.lib.ba3c_perturb_scores(_stream(), _ptr(probs0), _ptr(value0), _ptr(probs),
+                                                _ptr(value), B, A, WHICH[which], _ptr(out), _ptr(grid)))
+        return out
+
     def occupy_cus(self, stream, n_cus, usec):
         """Diagnostic: hold `n_cus` CUs for `usec` microseconds on torch stream `stream`."""
         _lib.check(self.lib.ba3c_occupy_cus(ctypes.c_void_p(stream.cuda_stream), int(n_cus),

@@ -14,13 +14,14 @@ rows[frame_steps[j]], with that decision's output in the HUD.
 
     python -m ba3c_amd.record --load CKPT -e GridBoxing-v0 --num_actions 18 --fc_neurons 128 \\
         --fc_splits 4 --episodes 3 --scale 3 --out DIR [--frame_skip 2-4 --sticky 0.25]
-        [--saliency v]
+        [--saliency v | pi | pv | ppi]
     python -m ba3c_amd.record --random -e GridBreakout-v0 --episodes 3 --out DIR
 
 `--saliency v` (or `pi`) adds a `saliency` array [T, 84, 84] to each trace: per decision, the
 newest frame's channel of |dV / dx| (or |d log pi(action) / dx|) of the state the policy saw
-(ba3c_amd.saliency), and tints the GIF's frames with it.  Without the flag a recording is what it
-was.
+(ba3c_amd.saliency), and tints the GIF's frames with it.  `pv` / `ppi` store the perturbation map
+of the value / of the policy instead (ba3c_amd.perturb, blurring the newest frame: 289 forwards per
+decision, in chunks of the engine's max_batch).  Without the flag a recording is what it was.
 
 Matches of two-player GridBoxing (ba3c_amd.duel) are recorded by `record_match`, along
 `duel.match`'s own decision path, as `MatchEpisode`s: the same trace with both sides' actions and
@@ -37,6 +38,7 @@ from .breakout import DEFAULT_LIMIT
 from .flags import GAMES, GRID_BOXING, GRID_BREAKOUT, build_parser, resolve
 
 MODULES = {GRID_BREAKOUT: breakout, GRID_BOXING: boxing}
+SALIENCY = ("v", "pi", "pv", "ppi")      # --saliency
 ARRAYS = ("row0", "aux0", "actions", "rewards", "probs", "values", "frames", "frame_steps")
 
 
@@ -153,8 +155,9 @@ def record_episodes(engine, game, n_episodes, n_envs=None, seed=0, limit=DEFAULT
     n_episodes-th included, as eval_with_envs counts them).  policy(state) -> probs [E, A]
     replaces the engine's forward (values are then recorded as 0).  Every `every`-th decision's
     frame is kept, at most `max_frames` per episode; hud: draw the policy's output under it.
-    saliency: None, "v" or "pi" — every decision's map of the newest frame (ba3c_amd.saliency:
-    value_map, or policy_map of the action handed to the env) on the engine's own network."""
+    saliency: None, "v", "pi", "pv" or "ppi" — every decision's map of the newest frame
+    (ba3c_amd.saliency: value_map, policy_map of the action handed to the env, perturb_value_map
+    or perturb_policy_map) on the engine's own network."""
     import torch
 
     from .evaluate import EvalPlayers
@@ -162,7 +165,7 @@ def record_episodes(engine, game, n_episodes, n_envs=None, seed=0, limit=DEFAULT
     from .view import ACTIONS, HUD_H, W, check_scale, hud_from_policy
     n_envs = int(n_envs) if n_envs else max(1, min(int(n_episodes), 20, engine.max_batch))
     assert n_episodes >= 1 and 1 <= n_envs <= engine.max_batch and every >= 1 and max_frames >= 0
-    assert saliency in (None, "v", "pi")
+    assert saliency in (None,) + SALIENCY
     scale = check_scale(scale)
     dev = engine.device
     env = GAMES[game][0](n_envs, seed=seed, limit=limit, device=dev, frame_skip=frame_skip,
@@ -192,8 +195,11 @@ def record_episodes(engine, game, n_episodes, n_envs=None, seed=0, limit=DEFAULT
                 live[e].frames.append(frames[j])
         if saliency:
             from . import saliency as sal
-            maps = (sal.value_map(engine, hist.state, newest=True) if saliency == "v"
-                    else sal.policy_map(engine, hist.state, act, newest=True)).cpu().numpy()
+            maps = {"v": lambda: sal.value_map(engine, hist.state, newest=True),
+                    "pi": lambda: sal.policy_map(engine, hist.state, act, newest=True),
+                    "pv": lambda: sal.perturb_value_map(engine, hist.state, newest=True),
+                    "ppi": lambda: sal.perturb_policy_map(engine, hist.state, newest=True),
+                    }[saliency]().cpu().numpy()
             for e in range(n_envs):
                 live[e].saliency.append(maps[e])
         for e in range(n_envs):
@@ -383,7 +389,8 @@ def record_match(side_a, side_b, n_episodes, n_games, seed=0, limit=DEFAULT_LIMI
     return watch.done
 
 
-def main(argv=None):
+def record_parser():
+    """train's parser with the recorder's own flags."""
     p = build_parser()
     p.description = "record episodes of an on-device game as replayable traces (and GIFs)"
     p.add_argument("--episodes", type=int, default=3)
@@ -393,9 +400,14 @@ def main(argv=None):
     p.add_argument("--limit", type=int, default=DEFAULT_LIMIT, help="LimitLengthPlayer's game steps")
     p.add_argument("--every", type=int, default=1, help="keep every N-th decision's frame")
     p.add_argument("--max_frames", type=int, default=2000)
-    p.add_argument("--saliency", choices=("v", "pi"), default=None,
-                   help="store each decision's input-gradient saliency map (value / chosen action)")
-    args = resolve(p.parse_args(argv))
+    p.add_argument("--saliency", choices=SALIENCY, default=None,
+                   help="store each decision's saliency map: the input gradient of the value / of the "
+                        "chosen action (v, pi), or the perturbation map of the value / policy (pv, ppi)")
+    return p
+
+
+def main(argv=None):
+    args = resolve(record_parser().parse_args(argv))
     if args.environment not in GAMES:
         raise SystemExit("recording needs an on-device game: pass -e %s" % " or -e ".join(sorted(GAMES)))
     if not args.random and not args.load:

@@ -13,6 +13,9 @@ The rule.  dP0 [B,40,40,32] is the gradient of the pooled conv0 output, c0 its a
     dY[b, y, x, o] = dP0[b, y>>1, x>>1, o]  where c0[b, y>>1, x>>1, o] == 2 (y&1) + (x&1), else 0
     dX[b, y, x, c] = sum_{ky, kx in 0..4, o} dY[b, y-ky, x-kx, o] W0[ky, kx, c, o]
 for 0 <= y, x < 84 and the C = 4 real input channels (dY is 0 outside [0, 80)^2).
+
+`perturb_value_map` / `perturb_policy_map` are the perturbation maps of ba3c_amd.perturb, which
+need no gradient: the smoother picture the Atari literature shows.
 """
 import numpy as np
 
@@ -101,3 +104,15 @@ def value_map(engine, state, newest=False):
 def policy_map(engine, state, action, newest=False):
     """|d log pi(action) / dx|: seeds (1, 0)."""
     return _seeded(engine, state, action, 1.0, 0.0, newest)
+
+
+def perturb_value_map(engine, state, newest=False):
+    """The perturbation saliency of the value (ba3c_amd.perturb: S_v = 1/2 (V - V')^2 under a
+    blurred patch at each of 17 x 17 centres, interpolated to the frame): Ba3cEngine.perturb_maps.
+    -> float32 [B,84,84]; newest: only the newest frame is blurred."""
+    return engine.perturb_maps(state, "v", newest=newest)
+
+
+def perturb_policy_map(engine, state, newest=False):
+    """The same of the policy: S_pi = 1/2 sum_a (p_a - p'_a)^2."""
+    return engine.perturb_maps(state, "pi", newest=newest)

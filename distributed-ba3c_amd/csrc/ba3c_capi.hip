@@ -31,6 +31,7 @@
 #include "ba3c_gemm6.h"
 #include "ba3c_launch.h"
 #include "ba3c_multi.h"
+#include "ba3c_perturb.h"
 #include "ba3c_plan.h"
 #include "ba3c_problems.h"
 #include "ba3c_rollout.h"
@@ -1614,6 +1615,32 @@ int ba3c_input_grads(ba3c_handle* h, void* stream, const float* params, const ui
                   false, nullptr, seeds));
   CHECK(BackwardPass<4>(h, s, pl, w, params, state, grads_scratch, batch, 0).run());
   return run_conv0d(h, s, params, w, batch, dstate, map);
+}
+
+int ba3c_perturb_states(void* stream, const uint8_t* state, int32_t n, int64_t first, int64_t count,
+                        int32_t newest, uint8_t* out) {
+  if (!state || !out) return fail(BA3C_ERR_INVALID, "null pointer");
+  if (n < 1) return fail(BA3C_ERR_INVALID, "bad count: n must be >= 1");
+  if (first < 0 || count < 1 || first > (int64_t)n * Perturb::NC - count)
+    return fail(BA3C_ERR_INVALID, "chunk outside the n * 289 perturbed states");
+  if (!check_ptr(state) || !check_ptr(out)) return fail(BA3C_ERR_INVALID, "state and out must be 16-byte aligned");
+  HIP_TRY(launch_perturb_states(static_cast<hipStream_t>(stream),
+                                PerturbStatesArgs{reinterpret_cast<const uint4*>(state), reinterpret_cast<uint4*>(out),
+                                                  first, count, (int)(first / Perturb::GRID)},
+                                newest != 0));
+  return BA3C_OK;
+}
+
+int ba3c_perturb_scores(void* stream, const float* probs0, const float* value0, const float* probs,
+                        const float* value, int32_t n, int32_t num_actions, int32_t which, float* map,
+                        double* grid) {
+  if (!probs0 || !value0 || !probs || !value || !map) return fail(BA3C_ERR_INVALID, "null pointer");
+  if (n < 1) return fail(BA3C_ERR_INVALID, "bad count: n must be >= 1");
+  if (which != 0 && which != 1) return fail(BA3C_ERR_INVALID, "which must be 0 (value) or 1 (policy)");
+  if (num_actions < 1 || num_actions > 31) return fail(BA3C_ERR_INVALID, "num_actions must be in [1, 31]");
+  HIP_TRY(launch_perturb_scores(static_cast<hipStream_t>(stream),
+                                PerturbScoresArgs{probs0, value0, probs, value, map, grid, num_actions, which}, n));
+  return BA3C_OK;
 }
 
 int ba3c_ppo_norm_adv(void* stream, float* rows, int32_t n, double* stats) {

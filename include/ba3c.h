@@ -221,6 +221,28 @@ int ba3c_input_grads(ba3c_handle* h, void* stream, const float* params, const ui
                      const int64_t* action, const float* seeds, int32_t batch, void* workspace,
                      float* grads_scratch, float* dstate, float* map);
 
+/* Perturbation saliency (no reference counterpart; ba3c_amd/perturb.py states the rule and is the
+ * oracle of both).  A state has 17 x 17 = 289 perturbed copies: copy n * 289 + 17 i + j of source
+ * state n has a Gaussian-blurred patch blended in around pixel (5i, 5j) (blur sigma 3 / radius 9
+ * with reflected edges, mask sigma 5 / radius 15, all fixed-point; newest != 0 perturbs only the
+ * newest history plane, byte 3 of a pixel).  ba3c_perturb_states writes copies first ..
+ * first + count of the n * 289 of state (u8 [n,84,84,4]) to out (u8 [count,84,84,4]), so that a
+ * caller can make them in chunks that fit its forward batch: one launch, bit-equal to
+ * perturb.perturb_numpy.
+ * ba3c_perturb_scores takes the network's outputs on the n source states (probs0 [n][A], value0
+ * [n]) and on all n * 289 copies (probs [n*289][A], value [n*289]; fp32), forms per copy, in fp64,
+ *   which == 0:  S_v = 1/2 (V - V')^2      which == 1:  S_pi = 1/2 sum_a (p_a - p'_a)^2
+ * and writes the 17 x 17 grid interpolated bilinearly to map (fp32 [n,84,84]: pixel (y, x) at grid
+ * coordinate (y/5, x/5) clamped to 16) and, where grid is given, the raw scores (fp64 [n,17,17]).
+ * Both refuse, before any GPU call and in this order (BA3C_ERR_INVALID): a null pointer (grid
+ * excepted); n < 1; a chunk outside [0, n * 289] or empty; state or out not 16-byte aligned;
+ * which not 0 or 1; num_actions outside [1, 31]. */
+int ba3c_perturb_states(void* stream, const uint8_t* state, int32_t n, int64_t first, int64_t count,
+                        int32_t newest, uint8_t* out);
+int ba3c_perturb_scores(void* stream, const float* probs0, const float* value0, const float* probs,
+                        const float* value, int32_t n, int32_t num_actions, int32_t which, float* map,
+                        double* grid);
+
 /* Per-minibatch advantage normalisation, in place on the n rows {R, V_old, l_old, .} of a PPO
  * step (fp32 [n][4], device): with Adv_i = (double)R_i - (double)V_old_i, mean = sum Adv / n and
  * the population std = sqrt(sum (Adv - mean)^2 / n) (two passes, fp64),

@@ -4,7 +4,13 @@ calls after warm-up, five rounds, without and with the map output — its fracti
 path peak priced on the algorithmic 45.16 MFLOP per image, and conv1's input gradient at the same
 batch (the BA3C_K_CONV1_DGRAD probe inside train_grads; at small batches that kernel shares a
 launch the probe does not bracket: 0 launches).  One JSON line per batch.
-    python scripts/saliency_time.py"""
+    python scripts/saliency_time.py
+--perturb times perturbation saliency instead at B = 1 and 32: ms per
+Ba3cEngine.perturb_maps call (289 B forwards in chunks of max_batch = 2048) and per launch of
+ba3c_perturb_states (all 289 B states at once, with its store rate) and of ba3c_perturb_scores, the
+same way: HIP events around batches of calls after warm-up, five rounds, sorted.
+    python scripts/saliency_time.py --perturb"""
+import ctypes
 import json
 import os
 import sys
@@ -16,6 +22,53 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "distributed-ba3c_amd")]
 from ba3c_amd.engine import Ba3cEngine
 from oracle import ba3c_oracle as O
+
+
+
+def rounds_ms(fn, reps, warm=10):
+    """Sorted ms per call of five rounds of `reps` calls between HIP events, after `warm` calls."""
+    for _ in range(warm):
+        fn()
+    rounds = []
+    for _ in range(5):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        rounds.append(e0.elapsed_time(e1) / reps)
+    return sorted(rounds)
+
+
+def perturb_times():
+    from ba3c_amd import _lib as L
+    from ba3c_amd.perturb import NC
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+    for B in (1, 32):
+        eng = Ba3cEngine(num_actions=18, fc_neurons=128, fc_splits=4, max_batch=2048)
+        eng.load_params(O.init_params(128, 4, 18, seed=7, dtype=np.float32))
+        st = torch.from_numpy(np.random.RandomState(B).randint(0, 256, size=(B, 84, 84, 4)).astype(np.uint8)).cuda()
+        N = B * NC
+        out = torch.empty(N, 84, 84, 4, dtype=torch.uint8, device="cuda")
+        p0, v0, p, v = (torch.rand(*s, device="cuda") for s in ((B, 18), (B,), (N, 18), (N,)))
+        mp = torch.empty(B, 84, 84, device="cuda")
+        res = {"perturb_maps_v_ms": rounds_ms(lambda: eng.perturb_maps(st, "v"), 20, 3),
+               "perturb_maps_pi_newest_ms": rounds_ms(lambda: eng.perturb_maps(st, "pi", newest=True), 20, 3)}
+        for newest in (0, 1):
+            res["states_newest%d_ms" % newest] = rounds_ms(lambda: L.check(eng.lib.ba3c_perturb_states(
+                None, ptr(st), B, 0, N, newest, ptr(out))), 50)
+        for which in (0, 1):
+            res["scores_which%d_ms" % which] = rounds_ms(lambda: L.check(eng.lib.ba3c_perturb_scores(
+                None, ptr(p0), ptr(v0), ptr(p), ptr(v), B, 18, which, ptr(mp), None)), 200)
+        res["states_store_GBps"] = N * 28224 / (res["states_newest0_ms"][2] * 1e-3) / 1e9
+        print(B, json.dumps(res), flush=True)
+        del eng
+
+
+if "--perturb" in sys.argv[1:]:
+    perturb_times()
+    sys.exit(0)
 
 PEAK = 838.9e12                      # fp16x3 path, fp32-equivalent (DESIGN.md section 3.1)
 FLOP = 2 * 7056 * 4 * 800            # algorithmic, per image
