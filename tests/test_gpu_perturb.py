@@ -32,21 +32,53 @@ def deal(kind, n, newest):
     return s, P.perturb_numpy(s, newest)
 
 
+def held_bit_for_bit(kind, n, newest, chunks):
+    """Each chunk (first, count) of the n * 289 perturbed states equals the rule's, and the guard
+    row after it keeps its 0xAB.  -> the chunks' outputs, concatenated."""
+    from ba3c_amd import _lib as L
+    lib = L.load()
+    s, ref = deal(kind, n, newest)
+    src = dev(s)
+    got = []
+    for first, count in chunks or ((0, n * P.NC),):
+        out = torch.full((count + 1, 84, 84, 4), 0xAB, dtype=torch.uint8, device="cuda")
+        L.check(lib.ba3c_perturb_states(None, ptr(src), n, first, count, int(newest), ptr(out)))
+        out = out.cpu().numpy()
+        assert np.array_equal(out[:count], ref[first:first + count]), (first, count)
+        assert np.all(out[count] == 0xAB), (first, count)      # nothing past the chunk
+        got.append(out[:count])
+    return np.concatenate(got), ref
+
+
 @pytest.mark.parametrize("chunks", [None, ((0, 100), (100, 189))], ids=["whole", "chunks"])
 @pytest.mark.parametrize("newest", [False, True])
 @pytest.mark.parametrize("n", [1, 3])
 @pytest.mark.parametrize("kind", ["random", "atari", "black", "white", "pixels"])
 def test_perturbed_states_are_the_rule_bit_for_bit(kind, n, newest, chunks):
-    from ba3c_amd import _lib as L
-    lib = L.load()
-    s, ref = deal(kind, n, newest)
-    src = dev(s)
-    for first, count in chunks or ((0, n * P.NC),):
-        out = torch.full((count + 1, 84, 84, 4), 0xAB, dtype=torch.uint8, device="cuda")
-        L.check(lib.ba3c_perturb_states(None, ptr(src), n, first, count, int(newest), ptr(out)))
-        out = out.cpu().numpy()
-        assert np.array_equal(out[:count], ref[first:first + count])
-        assert np.all(out[count] == 0xAB)                      # nothing past the chunk
+    held_bit_for_bit(kind, n, newest, chunks)
+
+
+# Chunk seams at n = 3 (867 perturbed states; a state is 289 = 17 centre rows of 17; the kernel's
+# first workgroup is (first // 17) // 17, first // 17 % 17).  Ba3cEngine.perturb_maps makes all of
+# these whenever max_batch does not divide 289.
+SEAMS = {
+    "crosses_state_0_to_1": ((280, 20),),
+    "single_states_at_a_state_boundary_and_the_end": ((288, 1), (289, 1), (866, 1)),
+    "one_centre_row": ((306, 17),),
+    "one_centre_row_and_a_state_either_side": ((305, 19),),
+    "inside_state_1_to_the_end": ((577, 290),),
+}
+SWEEP = tuple((first, min(64, 867 - first)) for first in range(0, 867, 64))   # the recorder's max_batch
+
+
+@pytest.mark.parametrize("name", sorted(SEAMS) + ["sweep_of_64"])
+@pytest.mark.parametrize("newest", [False, True])
+@pytest.mark.parametrize("kind", ["random", "pixels"])
+def test_chunk_seams_are_the_rule_bit_for_bit(kind, newest, name):
+    got, ref = held_bit_for_bit(kind, 3, newest, SWEEP if name == "sweep_of_64" else SEAMS[name])
+    if name == "sweep_of_64":
+        assert SWEEP[-1] == (832, 35) and len(SWEEP) == 14     # a ragged last chunk
+        assert np.array_equal(got, ref)                        # the sweep, concatenated, is the whole
 
 
 def within_rounding(got, grid):

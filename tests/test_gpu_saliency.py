@@ -5,32 +5,11 @@ import pytest
 import torch
 
 from ba3c_amd import saliency as S
+from conv0d_walk import BINADES, deal
 from test_gpu_parity import GRAD_TOL, case, dev, engine, gpu_decisions, rel
 from test_gpu_ppo import HEADS
 
 pytestmark = pytest.mark.gpu
-
-SPOTS = [(y, x) for y in (0, 19, 39) for x in (0, 19, 39)]    # corners, edges, centre (pooled)
-BINADES = (1e-6, 1.0, 1e4, 0.0)
-
-
-def deal(kind, B, seed=0):
-    """(dP0 float32 [B,40,40,32], codes): single-K: one element per spot (disjoint footprints) under
-    code K; dense: N(0,1), ~30 % dead windows; binades: dense, image i scaled by BINADES[i]."""
-    rs = np.random.RandomState(seed + B)
-    c0 = rs.randint(0, 4, size=(B, 40, 40, 32)).astype(np.uint8)
-    if kind.startswith("single"):
-        dp0 = np.zeros((B, 40, 40, 32), np.float32)
-        c0[:] = int(kind[-1])
-        for b in range(B):
-            for y, x in SPOTS:
-                dp0[b, y, x, rs.randint(32)] = rs.normal()
-        return dp0, c0
-    c0[rs.random_sample(c0.shape) < 0.3] = 255
-    dp0 = rs.normal(size=c0.shape)
-    if kind == "binades":
-        dp0 *= np.asarray(BINADES)[:B, None, None, None]
-    return dp0.astype(np.float32), c0
 
 
 def run_kernel(eng, dp0, c0):
@@ -41,6 +20,21 @@ def run_kernel(eng, dp0, c0):
     return dx.cpu().numpy(), m.cpu().numpy()
 
 
+def held_normwise(dp0, c0, w0, dx, m, tag):
+    """The per-image normwise bound on dX against the float64 rule (an all-zero image: exact zeros)
+    and `map` within 4 spacings of the float64 channel sum of the kernel's own dX."""
+    ref = S.conv0_input_grad_numpy(dp0, c0, w0)
+    f32 = S.conv0_input_grad_numpy(dp0, c0, w0, np.float32)
+    for b in range(len(dp0)):
+        if not dp0[b].any():
+            assert not dx[b].any() and not m[b].any()           # exact zeros
+            continue
+        print("%s image %d: kernel %.3e, float32 numpy %.3e" % (tag, b, rel(dx[b], ref[b]), rel(f32[b], ref[b])))
+        assert rel(dx[b], ref[b]) < GRAD_TOL
+    want = np.abs(dx).sum(axis=3, dtype=np.float64)
+    assert np.all(np.abs(m - want) <= 4 * np.spacing(want.astype(np.float32)))
+
+
 def check(kind, B, pad=0.0):
     params = case(3, 1)[0]
     params["conv0/W"][:, :, 4:] = pad
@@ -48,16 +42,7 @@ def check(kind, B, pad=0.0):
     eng.load_params(params)
     dp0, c0 = deal(kind, B)
     dx, m = run_kernel(eng, dp0, c0)
-    ref = S.conv0_input_grad_numpy(dp0, c0, params["conv0/W"])
-    f32 = S.conv0_input_grad_numpy(dp0, c0, params["conv0/W"], np.float32)
-    for b in range(B):
-        if not dp0[b].any():
-            assert not dx[b].any() and not m[b].any()           # exact zeros
-            continue
-        print("%s B=%d image %d: kernel %.3e, float32 numpy %.3e" % (kind, B, b, rel(dx[b], ref[b]), rel(f32[b], ref[b])))
-        assert rel(dx[b], ref[b]) < GRAD_TOL
-    want = np.abs(dx).sum(axis=3, dtype=np.float64)
-    assert np.all(np.abs(m - want) <= 4 * np.spacing(want.astype(np.float32)))
+    held_normwise(dp0, c0, params["conv0/W"], dx, m, "%s B=%d" % (kind, B))
     return dx, m
 
 
@@ -124,21 +109,37 @@ def autograd_reference(params, state, action, seeds, forced):
     return torch.autograd.grad(J, x)[0].permute(0, 2, 3, 1).numpy()
 
 
-@pytest.mark.parametrize("seed", [(0.0, 1.0), (1.0, 0.0)], ids=["v", "pi"])
-def test_input_grads_end_to_end(seed):
-    B = 2
+@pytest.mark.parametrize("seed,B", [((0.0, 1.0), 2), ((1.0, 0.0), 2), (None, 129)], ids=["v", "pi", "mix129"])
+def test_input_grads_end_to_end(seed, B):
+    """B = 129 is one above OVERLAP_B: ba3c_input_grads then runs the seed heads under the
+    large-batch launch plan (mj_fc on big tiles, whole-map conv2, no multi-job conv launches) and
+    conv0d_kernel walks (2709 bands); mixed per-sample seeds.  All 129 images are compared, the
+    float64 autograd evaluated in chunks of at most 32 (the objective is a per-sample sum)."""
     params, state, action, _, _ = case(60, B, wscale=2.0)
-    eng = engine()
+    eng = engine(max_batch=max(B, 64))
     eng.load_params(params)
-    seeds = np.tile(np.float32(seed), (B, 1))
+    if seed is None:
+        seeds = np.random.RandomState(6).normal(size=(B, 2)).astype(np.float32)
+    else:
+        seeds = np.tile(np.float32(seed), (B, 1))
     before = eng.grads.clone()
+    for n in ("c0", "c1", "c2"):                               # no code, no finite a3: the decisions
+        eng.workspace_tensor(n, B).fill_(7)                    # read back below are this call's
+    eng.workspace_tensor("a3", B).fill_(float("nan"))
     dx, m = eng.input_grads(dev(state), dev(action), dev(seeds), map=True)
     assert torch.equal(eng.grads, before)                      # the weight gradients go to scratch
-    ref = autograd_reference(params, state, action, seeds, gpu_decisions(eng, B)[0])
-    for b in range(B):
-        print("seed %s image %d: rel %.3e" % (seed, b, rel(dx[b].cpu().numpy(), ref[b])))
-        assert rel(dx[b].cpu().numpy(), ref[b]) < GRAD_TOL
-    assert torch.equal(S.value_map(eng, dev(state)) if seed[1] else S.policy_map(eng, dev(state), dev(action)), m)
+    forced, codes = gpu_decisions(eng, B)
+    assert all(np.isin(c, (0, 1, 2, 3, 255)).all() for c in codes)
+    assert np.isfinite(eng.workspace_tensor("a3", B).cpu().numpy()).all()
+    dx = dx.cpu().numpy()
+    for i in range(0, B, 32):
+        ref = autograd_reference(params, state[i:i + 32], action[i:i + 32], seeds[i:i + 32],
+                                 {k: v[i:i + 32] for k, v in forced.items()})
+        for b in range(len(ref)):
+            print("seed %s image %d: rel %.3e" % (seed, i + b, rel(dx[i + b], ref[b])))
+            assert rel(dx[i + b], ref[b]) < GRAD_TOL
+    if seed is not None:
+        assert torch.equal(S.value_map(eng, dev(state)) if seed[1] else S.policy_map(eng, dev(state), dev(action)), m)
 
 
 def test_recorder_stores_the_value_map_of_each_decision(tmp_path):
