@@ -39,13 +39,14 @@ class Ba3cOptParams(ctypes.Structure):
 
 _lib = None
 # roofline-accounting queries, the PPO entry points, the episode log, the global-norm clip and the
-# saliency and perturbation entry points an
+# saliency, perturbation and integrated-gradients entry points an
 # alternative A/B build (BA3C_LIB) may predate.  Every PPO step of the engine is one
 # ba3c_train_grads_ppo_ext call: a build older than that entry point runs none.
 AB_OPTIONAL = {"ba3c_kernel_merged", "ba3c_probe_every", "ba3c_train_grads_ppo", "ba3c_sample_logp",
                "ba3c_train_grads_ppo_ext", "ba3c_ppo_norm_adv", "ba3c_episode_stats",
                "ba3c_global_clip_scratch", "ba3c_clip_grads_global", "ba3c_conv0_input_grad",
-               "ba3c_input_grads", "ba3c_perturb_states", "ba3c_perturb_scores"}
+               "ba3c_input_grads", "ba3c_perturb_states", "ba3c_perturb_scores", "ba3c_ig_states",
+               "ba3c_ig_accumulate"}
 PPO_ADV_FROM_ROW = 1       # BA3C_PPO_ADV_FROM_ROW
 
 
@@ -90,6 +91,8 @@ def load():
         "ba3c_input_grads": (i32, [P, P, P, P, P, P, i32, P, P, P, P]),
         "ba3c_perturb_states": (i32, [P, P, i32, i64, i64, i32, P]),
         "ba3c_perturb_scores": (i32, [P, P, P, P, P, i32, i32, i32, P, P]),
+        "ba3c_ig_states": (i32, [P, P, i32, i32, i32, i64, i64, P]),
+        "ba3c_ig_accumulate": (i32, [P, P, i32, i32, i32, i64, i64, P, P, P]),
         "ba3c_sample_logp": (i32, [P, P, P, P, i32, i32, P, P, P]),
         "ba3c_bucket_tensor": (i32, [P]),
         "ba3c_set_phase2_event": (i32, [P, P]),

@@ -285,6 +285,41 @@ class Ba3cEngine(object):
                                                 _ptr(value), B, A, WHICH[which], _ptr(out), _ptr(grid)))
         return out
 
+    # -- integrated gradients (ba3c_amd.intgrad) -----------------------------------------------
+    _ig_path = None     # integrated_grads' scratch: one batch of path states and of their
+    _ig_grads = None    # input gradients, on first use
+
+    def integrated_grads(self, state, action, seeds, steps=32, baseline="blur"):
+        """The integrated-gradients attribution of J = s_pi log pi(action) + s_v V per unit of
+        state / 255 (ba3c_amd.intgrad): `steps` uint8 path states per state from the "zero" or the
+        "blur" baseline, their input gradients summed in float64 and scaled by (x - x0) / 255.  The
+        B * steps path states are made (ba3c_ig_states), differentiated (input_grads; each carries
+        the action and the seeds of its state) and summed (ba3c_ig_accumulate) in chunks of at
+        most max_batch rows; the host reads nothing on the way, and the result does not depend on
+        max_batch.  -> float32 [B,84,84,4]."""
+        from .intgrad import BASELINES, MAX_STEPS
+        if self.channels != 4:
+            raise ValueError("integrated_grads needs channels == 4 (an engine of %d)" % self.channels)
+        B, action, _, _ = self._check_train(state, action, None)
+        assert seeds.dtype == torch.float32 and seeds.shape == (B, 2) and seeds.is_cuda
+        steps, base = int(steps), BASELINES[baseline]
+        assert 1 <= steps <= MAX_STEPS, "steps %d outside [1, %d]" % (steps, MAX_STEPS)
+        N = B * steps
+        rows = min(self.max_batch, N)
+        if self._ig_path is None or self._ig_path.shape[0] < rows:
+            self._ig_path = torch.empty(rows, 84, 84, 4, dtype=torch.uint8, device=self.device)
+            self._ig_grads = torch.empty(rows, 84, 84, 4, dtype=torch.float32, device=self.device)
+        acc = torch.zeros(B, 84, 84, 4, dtype=torch.float64, device=self.device)
+        attr = torch.empty(B, 84, 84, 4, dtype=torch.float32, device=self.device)
+        for first in range(0, N, rows):
+            count = min(rows, N - first)
+            chunk = (_stream(), _ptr(state), B, steps, base, first, count)
+            _lib.check(self.lib.ba3c_ig_states(*chunk, _ptr(self._ig_path)))
+            src = torch.arange(first, first + count, device=self.device) // steps
+            self.input_grads(self._ig_path[:count], action[src], seeds[src], out=self._ig_grads[:count])
+            _lib.check(self.lib.ba3c_ig_accumulate(*chunk, _ptr(self._ig_grads), _ptr(acc), _ptr(attr)))
+        return attr
+
     def occupy_cus(self, stream, n_cus, usec):
         """Diagnostic: hold `n_cus` CUs for `usec` microseconds on torch stream `stream`."""
         _lib.check(self.lib.ba3c_occupy_cus(ctypes.c_void_p(stream.cuda_stream), int(n_cus),

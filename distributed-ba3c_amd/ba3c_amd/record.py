@@ -14,14 +14,16 @@ rows[frame_steps[j]], with that decision's output in the HUD.
 
     python -m ba3c_amd.record --load CKPT -e GridBoxing-v0 --num_actions 18 --fc_neurons 128 \\
         --fc_splits 4 --episodes 3 --scale 3 --out DIR [--frame_skip 2-4 --sticky 0.25]
-        [--saliency v | pi | pv | ppi]
+        [--saliency v | pi | pv | ppi | iv | ipi]
     python -m ba3c_amd.record --random -e GridBreakout-v0 --episodes 3 --out DIR
 
 `--saliency v` (or `pi`) adds a `saliency` array [T, 84, 84] to each trace: per decision, the
 newest frame's channel of |dV / dx| (or |d log pi(action) / dx|) of the state the policy saw
 (ba3c_amd.saliency), and tints the GIF's frames with it.  `pv` / `ppi` store the perturbation map
 of the value / of the policy instead (ba3c_amd.perturb, blurring the newest frame: 289 forwards per
-decision, in chunks of the engine's max_batch).  Without the flag a recording is what it was.
+decision, in chunks of the engine's max_batch); `iv` / `ipi` the integrated-gradients map
+(ba3c_amd.intgrad: 32 path states from the blurred state, the newest frame's channel).  Without
+the flag a recording is what it was.
 
 Matches of two-player GridBoxing (ba3c_amd.duel) are recorded by `record_match`, along
 `duel.match`'s own decision path, as `MatchEpisode`s: the same trace with both sides' actions and
@@ -38,7 +40,7 @@ from .breakout import DEFAULT_LIMIT
 from .flags import GAMES, GRID_BOXING, GRID_BREAKOUT, build_parser, resolve
 
 MODULES = {GRID_BREAKOUT: breakout, GRID_BOXING: boxing}
-SALIENCY = ("v", "pi", "pv", "ppi")      # --saliency
+SALIENCY = ("v", "pi", "pv", "ppi", "iv", "ipi")      # --saliency
 ARRAYS = ("row0", "aux0", "actions", "rewards", "probs", "values", "frames", "frame_steps")
 
 
@@ -155,9 +157,9 @@ def record_episodes(engine, game, n_episodes, n_envs=None, seed=0, limit=DEFAULT
     n_episodes-th included, as eval_with_envs counts them).  policy(state) -> probs [E, A]
     replaces the engine's forward (values are then recorded as 0).  Every `every`-th decision's
     frame is kept, at most `max_frames` per episode; hud: draw the policy's output under it.
-    saliency: None, "v", "pi", "pv" or "ppi" — every decision's map of the newest frame
-    (ba3c_amd.saliency: value_map, policy_map of the action handed to the env, perturb_value_map
-    or perturb_policy_map) on the engine's own network."""
+    saliency: None, "v", "pi", "pv", "ppi", "iv" or "ipi" — every decision's map of the newest frame
+    (ba3c_amd.saliency: value_map, policy_map of the action handed to the env, perturb_value_map,
+    perturb_policy_map, ig_value_map or ig_policy_map) on the engine's own network."""
     import torch
 
     from .evaluate import EvalPlayers
@@ -199,6 +201,8 @@ def record_episodes(engine, game, n_episodes, n_envs=None, seed=0, limit=DEFAULT
                     "pi": lambda: sal.policy_map(engine, hist.state, act, newest=True),
                     "pv": lambda: sal.perturb_value_map(engine, hist.state, newest=True),
                     "ppi": lambda: sal.perturb_policy_map(engine, hist.state, newest=True),
+                    "iv": lambda: sal.ig_value_map(engine, hist.state, newest=True),
+                    "ipi": lambda: sal.ig_policy_map(engine, hist.state, act, newest=True),
                     }[saliency]().cpu().numpy()
             for e in range(n_envs):
                 live[e].saliency.append(maps[e])
@@ -402,7 +406,8 @@ def record_parser():
     p.add_argument("--max_frames", type=int, default=2000)
     p.add_argument("--saliency", choices=SALIENCY, default=None,
                    help="store each decision's saliency map: the input gradient of the value / of the "
-                        "chosen action (v, pi), or the perturbation map of the value / policy (pv, ppi)")
+                        "chosen action (v, pi), the perturbation map of the value / policy (pv, ppi), or "
+                        "their integrated gradients (iv, ipi)")
     return p
 
 

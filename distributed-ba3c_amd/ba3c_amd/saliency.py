@@ -15,7 +15,9 @@ The rule.  dP0 [B,40,40,32] is the gradient of the pooled conv0 output, c0 its a
 for 0 <= y, x < 84 and the C = 4 real input channels (dY is 0 outside [0, 80)^2).
 
 `perturb_value_map` / `perturb_policy_map` are the perturbation maps of ba3c_amd.perturb, which
-need no gradient: the smoother picture the Atari literature shows.
+need no gradient: the smoother picture the Atari literature shows.  `ig_value_map` /
+`ig_policy_map` are the integrated-gradients maps of ba3c_amd.intgrad: this module's gradient
+averaged over a path from a baseline and scaled by the distance from it, in the same units.
 """
 import numpy as np
 
@@ -116,3 +118,25 @@ def perturb_value_map(engine, state, newest=False):
 def perturb_policy_map(engine, state, newest=False):
     """The same of the policy: S_pi = 1/2 sum_a (p_a - p'_a)^2."""
     return engine.perturb_maps(state, "pi", newest=newest)
+
+
+def _integrated(engine, state, action, s_pi, s_v, newest, steps, baseline):
+    import torch
+    B = state.shape[0]
+    if action is None:
+        action = torch.zeros(B, dtype=torch.int64, device=state.device)
+    seeds = torch.tensor([s_pi, s_v], dtype=torch.float32, device=state.device).repeat(B, 1)
+    attr = engine.integrated_grads(state, action, seeds, steps=steps, baseline=baseline).abs()
+    return attr[..., -1] if newest else attr.sum(dim=-1)
+
+
+def ig_value_map(engine, state, newest=False, steps=32, baseline="blur"):
+    """|integrated gradients of V| (ba3c_amd.intgrad, Ba3cEngine.integrated_grads with seeds
+    (0, 1)) of each state.  -> float32 [B,84,84], summed over the four frames, or the newest
+    frame's channel alone, as value_map."""
+    return _integrated(engine, state, None, 0.0, 1.0, newest, steps, baseline)
+
+
+def ig_policy_map(engine, state, action, newest=False, steps=32, baseline="blur"):
+    """The same of log pi(action): seeds (1, 0)."""
+    return _integrated(engine, state, action, 1.0, 0.0, newest, steps, baseline)

@@ -29,6 +29,7 @@
 #include "ba3c_envview.h"
 #include "ba3c_episodes.h"
 #include "ba3c_gemm6.h"
+#include "ba3c_intgrad.h"
 #include "ba3c_launch.h"
 #include "ba3c_multi.h"
 #include "ba3c_perturb.h"
@@ -1640,6 +1641,45 @@ int ba3c_perturb_scores(void* stream, const float* probs0, const float* value0, 
   if (num_actions < 1 || num_actions > 31) return fail(BA3C_ERR_INVALID, "num_actions must be in [1, 31]");
   HIP_TRY(launch_perturb_scores(static_cast<hipStream_t>(stream),
                                 PerturbScoresArgs{probs0, value0, probs, value, map, grid, num_actions, which}, n));
+  return BA3C_OK;
+}
+
+// The checks that ba3c_ig_states and ba3c_ig_accumulate share, in the header's order
+static int ig_chunk(const uint8_t* state, int32_t n, int32_t steps, int32_t baseline, int64_t first,
+                    int64_t count, IgChunk* c) {
+  if (!state) return fail(BA3C_ERR_INVALID, "null pointer");
+  if (n < 1) return fail(BA3C_ERR_INVALID, "bad count: n must be >= 1");
+  if (steps < 1 || steps > IntGrad::MAX_STEPS) return fail(BA3C_ERR_INVALID, "steps must be in [1, 256]");
+  if (baseline != 0 && baseline != 1) return fail(BA3C_ERR_INVALID, "baseline must be 0 (zero) or 1 (blur)");
+  if (first < 0 || count < 1 || first > (int64_t)n * steps - count)
+    return fail(BA3C_ERR_INVALID, "chunk outside the n * steps path states");
+  *c = IgChunk{reinterpret_cast<const uint4*>(state), first, count, steps, (int)(first / steps)};
+  return BA3C_OK;
+}
+
+int ba3c_ig_states(void* stream, const uint8_t* state, int32_t n, int32_t steps, int32_t baseline,
+                   int64_t first, int64_t count, uint8_t* out) {
+  IgChunk c;
+  if (!out) return fail(BA3C_ERR_INVALID, "null pointer");
+  CHECK(ig_chunk(state, n, steps, baseline, first, count, &c));
+  if (!check_ptr(state) || !check_ptr(out)) return fail(BA3C_ERR_INVALID, "state and out must be 16-byte aligned");
+  const unsigned magic = (unsigned)((1ull << 32) / (2u * (unsigned)steps)) + 1u;
+  HIP_TRY(launch_ig_states(static_cast<hipStream_t>(stream),
+                           IgStatesArgs{c, reinterpret_cast<uint4*>(out), magic}, baseline != 0));
+  return BA3C_OK;
+}
+
+int ba3c_ig_accumulate(void* stream, const uint8_t* state, int32_t n, int32_t steps, int32_t baseline,
+                       int64_t first, int64_t count, const float* grads, double* acc, float* attr) {
+  IgChunk c;
+  if (!grads || !acc) return fail(BA3C_ERR_INVALID, "null pointer");
+  CHECK(ig_chunk(state, n, steps, baseline, first, count, &c));
+  if (!check_ptr(state) || !check_ptr(grads) || !check_ptr(acc) || (attr && !check_ptr(attr)))
+    return fail(BA3C_ERR_INVALID, "state, grads, acc and attr must be 16-byte aligned");
+  HIP_TRY(launch_ig_accumulate(static_cast<hipStream_t>(stream),
+                               IgAccumulateArgs{c, reinterpret_cast<const float4*>(grads),
+                                                reinterpret_cast<double2*>(acc), reinterpret_cast<float4*>(attr)},
+                               baseline != 0));
   return BA3C_OK;
 }
 

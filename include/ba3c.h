@@ -243,6 +243,31 @@ int ba3c_perturb_scores(void* stream, const float* probs0, const float* value0, 
                         const float* value, int32_t n, int32_t num_actions, int32_t which, float* map,
                         double* grid);
 
+/* Integrated-gradients saliency (no reference counterpart; ba3c_amd/intgrad.py states the rule and
+ * is the oracle of both).  A state x (u8 [84,84,4]) has `steps` = K path states between a baseline
+ * x0 and itself, path state n * K + j of source state n being, per byte and in integers,
+ *   p_j = x0 + floor(((2j+1) (x - x0) + K) / (2K))          (the midpoint rule, rounded half up)
+ * with x0 = 0 (baseline 0) or the whole-frame Gaussian blur of ba3c_perturb_states, sigma 3 /
+ * radius 9 with reflected edges, rounded half up to a byte (baseline 1).  ba3c_ig_states writes
+ * path states first .. first + count of the n * K of state (u8 [n,84,84,4]) to out (u8
+ * [count,84,84,4]), so that a caller can make them in chunks that fit its batch: one launch,
+ * bit-equal to intgrad.path_states.
+ * ba3c_ig_accumulate takes grads (fp32 [count,84,84,4]), ba3c_input_grads' dstate on that chunk,
+ * and adds each state's gradients into acc (fp64 [n,84,84,4], zeroed by the caller before the
+ * first chunk) in ascending j: one thread per four elements, no atomics, so acc does not depend
+ * on where the chunks' seams fall.  For every state whose last path state is in the chunk it
+ * writes, where attr (fp32 [n,84,84,4]) is given,
+ *   attr = (float)(((x - x0) / 255) (acc / K))
+ * with x - x0 recomputed from state: the attribution per unit of state / 255, whose sum over a
+ * state approaches J(x) - J(x0).  Chunks must be passed in ascending order, each once.
+ * Both refuse, before any GPU call and in this order (BA3C_ERR_INVALID): a null pointer (attr
+ * excepted); n < 1; steps outside [1, 256]; baseline not 0 or 1; a chunk outside [0, n * steps]
+ * or empty; a pointer that is not 16-byte aligned. */
+int ba3c_ig_states(void* stream, const uint8_t* state, int32_t n, int32_t steps, int32_t baseline,
+                   int64_t first, int64_t count, uint8_t* out);
+int ba3c_ig_accumulate(void* stream, const uint8_t* state, int32_t n, int32_t steps, int32_t baseline,
+                       int64_t first, int64_t count, const float* grads, double* acc, float* attr);
+
 /* Per-minibatch advantage normalisation, in place on the n rows {R, V_old, l_old, .} of a PPO
  * step (fp32 [n][4], device): with Adv_i = (double)R_i - (double)V_old_i, mean = sum Adv / n and
  * the population std = sqrt(sum (Adv - mean)^2 / n) (two passes, fp64),

@@ -9,7 +9,15 @@ launch the probe does not bracket: 0 launches).  One JSON line per batch.
 Ba3cEngine.perturb_maps call (289 B forwards in chunks of max_batch = 2048) and per launch of
 ba3c_perturb_states (all 289 B states at once, with its store rate) and of ba3c_perturb_scores, the
 same way: HIP events around batches of calls after warm-up, five rounds, sorted.
-    python scripts/saliency_time.py --perturb"""
+    python scripts/saliency_time.py --perturb
+--intgrad times integrated gradients at B = 1 and 32, max_batch = 2048: ms per
+Ba3cEngine.integrated_grads call at K = 8, 32 and 128 ("blur"), beside one input_grads call and one
+perturb_maps call on the same states, ms per launch of ba3c_ig_states (all B K path states at once,
+with its store rate) and of ba3c_ig_accumulate at K = 32, and the completeness gap
+|sum(attr) - (V(x) - V(x0))| of the value at each K, as [median, largest] over the states of its
+ratio to |V(x) - V(x0)| and to sum |attr|: on the timed states (uniform noise) and, at B = 32, on
+tests/atari_frames.py's drawn Breakout frames.
+    python scripts/saliency_time.py --intgrad"""
 import ctypes
 import json
 import os
@@ -65,6 +73,53 @@ def perturb_times():
         print(B, json.dumps(res), flush=True)
         del eng
 
+
+def intgrad_times():
+    from ba3c_amd import _lib as L
+    from ba3c_amd import intgrad as IG
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+    for B in (1, 32):
+        eng = Ba3cEngine(num_actions=18, fc_neurons=128, fc_splits=4, max_batch=2048)
+        eng.load_params(O.init_params(128, 4, 18, seed=7, dtype=np.float32))
+        host = np.random.RandomState(B).randint(0, 256, size=(B, 84, 84, 4)).astype(np.uint8)
+        st = torch.from_numpy(host).cuda()
+        ac = torch.zeros(B, dtype=torch.int64, device="cuda")
+        seeds = torch.tensor([0.0, 1.0], device="cuda").repeat(B, 1)
+
+        def gaps(frames, K):
+            x, x0 = (torch.from_numpy(a).cuda() for a in (frames, IG.baseline_numpy(frames, "blur")))
+            v = eng.forward(x)[2].double() - eng.forward(x0)[2].double()
+            attr = eng.integrated_grads(x, ac, seeds, steps=K).double()
+            gap = (attr.sum(dim=(1, 2, 3)) - v).abs()
+            return [[float(r.median()), float(r.max())] for r in (gap / v.abs(), gap / attr.abs().sum(dim=(1, 2, 3)))]
+        res = {"input_grads_ms": rounds_ms(lambda: eng.input_grads(st, ac, seeds), 50),
+               "perturb_maps_v_ms": rounds_ms(lambda: eng.perturb_maps(st, "v"), 20, 3)}
+        for K in (8, 32, 128):
+            res["integrated_grads_K%d_ms" % K] = rounds_ms(lambda: eng.integrated_grads(st, ac, seeds, steps=K), 20, 3)
+            res["gap_noise_K%d" % K] = gaps(host, K)
+            if B == 32:
+                sys.path.insert(0, os.path.join(ROOT, "tests"))
+                from atari_frames import atari_frames
+                res["gap_drawn_K%d" % K] = gaps(atari_frames(B, 5), K)
+        N = B * 32
+        out = torch.empty(N, 84, 84, 4, dtype=torch.uint8, device="cuda")
+        g = torch.rand(N, 84, 84, 4, device="cuda")
+        acc = torch.zeros(B, 84, 84, 4, dtype=torch.float64, device="cuda")
+        attr = torch.empty(B, 84, 84, 4, device="cuda")
+        for base in (0, 1):
+            res["states_baseline%d_ms" % base] = rounds_ms(lambda: L.check(eng.lib.ba3c_ig_states(
+                None, ptr(st), B, 32, base, 0, N, ptr(out))), 50)
+            res["accumulate_baseline%d_ms" % base] = rounds_ms(lambda: L.check(eng.lib.ba3c_ig_accumulate(
+                None, ptr(st), B, 32, base, 0, N, ptr(g), ptr(acc), ptr(attr))), 50)
+        res["states_store_GBps"] = N * 28224 / (res["states_baseline1_ms"][2] * 1e-3) / 1e9
+        res["accumulate_read_GBps"] = N * 28224 * 4 / (res["accumulate_baseline1_ms"][2] * 1e-3) / 1e9
+        print(B, json.dumps(res), flush=True)
+        del eng
+
+
+if "--intgrad" in sys.argv[1:]:
+    intgrad_times()
+    sys.exit(0)
 
 if "--perturb" in sys.argv[1:]:
     perturb_times()
