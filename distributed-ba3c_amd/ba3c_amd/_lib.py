@@ -39,14 +39,15 @@ class Ba3cOptParams(ctypes.Structure):
 
 _lib = None
 # roofline-accounting queries, the PPO entry points, the episode log, the global-norm clip and the
-# saliency, perturbation and integrated-gradients entry points an
+# saliency, perturbation, integrated-gradients and t-SNE entry points an
 # alternative A/B build (BA3C_LIB) may predate.  Every PPO step of the engine is one
 # ba3c_train_grads_ppo_ext call: a build older than that entry point runs none.
 AB_OPTIONAL = {"ba3c_kernel_merged", "ba3c_probe_every", "ba3c_train_grads_ppo", "ba3c_sample_logp",
                "ba3c_train_grads_ppo_ext", "ba3c_ppo_norm_adv", "ba3c_episode_stats",
                "ba3c_global_clip_scratch", "ba3c_clip_grads_global", "ba3c_conv0_input_grad",
                "ba3c_input_grads", "ba3c_perturb_states", "ba3c_perturb_scores", "ba3c_ig_states",
-               "ba3c_ig_accumulate"}
+               "ba3c_ig_accumulate", "ba3c_tsne_workspace_size", "ba3c_tsne_sqdist",
+               "ba3c_tsne_affinities", "ba3c_tsne_step"}
 PPO_ADV_FROM_ROW = 1       # BA3C_PPO_ADV_FROM_ROW
 
 
@@ -64,6 +65,7 @@ def load():
     except OSError as e:
         raise Ba3cLibraryError("failed to load %s: %s" % (LIB_PATH, e))
     P, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
+    f64 = ctypes.c_double
     sig = {
         "ba3c_version": (i32, []),
         "ba3c_last_error": (ctypes.c_char_p, []),
@@ -93,6 +95,10 @@ def load():
         "ba3c_perturb_scores": (i32, [P, P, P, P, P, i32, i32, i32, P, P]),
         "ba3c_ig_states": (i32, [P, P, i32, i32, i32, i64, i64, P]),
         "ba3c_ig_accumulate": (i32, [P, P, i32, i32, i32, i64, i64, P, P, P]),
+        "ba3c_tsne_workspace_size": (ctypes.c_size_t, [i32, i32]),
+        "ba3c_tsne_sqdist": (i32, [P, P, i32, i32, P, P]),
+        "ba3c_tsne_affinities": (i32, [P, P, i32, f64, P, P, P]),
+        "ba3c_tsne_step": (i32, [P, P, i32, P, P, P, f64, f64, f64, P, P]),
         "ba3c_sample_logp": (i32, [P, P, P, P, i32, i32, P, P, P]),
         "ba3c_bucket_tensor": (i32, [P]),
         "ba3c_set_phase2_event": (i32, [P, P]),

@@ -160,6 +160,22 @@ class Ba3cEngine(object):
                                          _ptr(out[0]), _ptr(out[1]), _ptr(out[2])))
         return out
 
+    def features(self, state, out=None):
+        """The predictor forward's last hidden layer h (fc1 after its PReLU) of every state, as
+        float32 [B, fc_neurons]: what ba3c_amd.tsne embeds.  B is not bounded by max_batch: the
+        states run in chunks of it, and each chunk's h is copied on the device out of the forward
+        workspace (`workspace_tensor("h", b, train=False)`)."""
+        assert state.dim() == 4 and state.shape[0] >= 1, state.shape
+        B, F = state.shape[0], self.cfg["fc_neurons"]
+        if out is None:
+            out = torch.empty(B, F, dtype=torch.float32, device=self.device)
+        assert out.shape == (B, F) and out.dtype == torch.float32 and out.is_contiguous()
+        for first in range(0, B, self.max_batch):
+            b = min(self.max_batch, B - first)
+            self.forward(state[first:first + b])
+            out[first:first + b].view(-1).copy_(self.workspace_tensor("h", b, train=False))
+        return out
+
     def train_grads(self, state, action, futurereward, entropy_beta=0.01, grads=None, phase=0):
         """Forward + loss + backward; raw gradients into `grads` (default self.grads).
         Returns the device float64 scalars tensor (order: _lib.SCALAR_NAMES).  phase 1 / 2

@@ -150,6 +150,20 @@ class _Open(object):
         self.frames, self.frame_steps, self.saliency = [], [], []
 
 
+def open_players(engine, game, n_envs, seed=0, limit=DEFAULT_LIMIT, frame_skip=1, sticky=0.0, policy=None):
+    """The evaluation's decision path over `n_envs` simulators of `game`, drawn from
+    RandomState(seed): -> (env, hist, players).  `players.step(env, hist, before_step)` plays one
+    decision of every simulator; hist.state is what the policy sees."""
+    from .evaluate import EvalPlayers
+    from .rollout import FrameHistory
+    env = GAMES[game][0](n_envs, seed=seed, limit=limit, device=engine.device, frame_skip=frame_skip,
+                         sticky=sticky)
+    assert env.A <= engine.num_actions
+    hist = FrameHistory(n_envs, hist_len=4, channels=1, device=engine.device)
+    env.reset_history(hist)
+    return env, hist, EvalPlayers(engine, n_envs, np.random.RandomState(seed), policy)
+
+
 def record_episodes(engine, game, n_episodes, n_envs=None, seed=0, limit=DEFAULT_LIMIT, frame_skip=1,
                     sticky=0.0, policy=None, scale=3, hud=True, every=1, max_frames=2000, saliency=None):
     """Play `n_envs` evaluation players of `game` until `n_episodes` episodes have finished and
@@ -162,20 +176,13 @@ def record_episodes(engine, game, n_episodes, n_envs=None, seed=0, limit=DEFAULT
     perturb_policy_map, ig_value_map or ig_policy_map) on the engine's own network."""
     import torch
 
-    from .evaluate import EvalPlayers
-    from .rollout import FrameHistory
     from .view import ACTIONS, HUD_H, W, check_scale, hud_from_policy
     n_envs = int(n_envs) if n_envs else max(1, min(int(n_episodes), 20, engine.max_batch))
     assert n_episodes >= 1 and 1 <= n_envs <= engine.max_batch and every >= 1 and max_frames >= 0
     assert saliency in (None,) + SALIENCY
     scale = check_scale(scale)
     dev = engine.device
-    env = GAMES[game][0](n_envs, seed=seed, limit=limit, device=dev, frame_skip=frame_skip,
-                         sticky=sticky)
-    assert env.A <= engine.num_actions
-    hist = FrameHistory(n_envs, hist_len=4, channels=1, device=dev)
-    env.reset_history(hist)
-    players = EvalPlayers(engine, n_envs, np.random.RandomState(seed), policy)
+    env, hist, players = open_players(engine, game, n_envs, seed, limit, frame_skip, sticky, policy)
 
     def start(which):
         rows = env.game.cpu().numpy()

@@ -38,6 +38,7 @@
 #include "ba3c_rollout.h"
 #include "ba3c_small.h"
 #include "ba3c_split.h"
+#include "ba3c_tsne.h"
 #include "ba3c_wgrad6.h"
 
 using namespace ba3c;
@@ -1680,6 +1681,57 @@ int ba3c_ig_accumulate(void* stream, const uint8_t* state, int32_t n, int32_t st
                                IgAccumulateArgs{c, reinterpret_cast<const float4*>(grads),
                                                 reinterpret_cast<double2*>(acc), reinterpret_cast<float4*>(attr)},
                                baseline != 0));
+  return BA3C_OK;
+}
+
+// ---- t-SNE (ba3c_tsne.h): the refusals in the header's order ------------------------------------
+static int tsne_range(int32_t n, int32_t d) {
+  if (n < Tsne::MIN_N || n > Tsne::MAX_N) return fail(BA3C_ERR_INVALID, "n must be in [8, 8192]");
+  if (d < 1 || d > Tsne::MAX_D) return fail(BA3C_ERR_INVALID, "d must be in [1, 2048]");
+  return BA3C_OK;
+}
+
+size_t ba3c_tsne_workspace_size(int32_t n, int32_t d) {
+  if (tsne_range(n, d) != BA3C_OK) return 0;
+  return tsne_work_layout(n, d, nullptr, nullptr);
+}
+
+int ba3c_tsne_sqdist(void* stream, const float* x, int32_t n, int32_t d, void* work, float* dist) {
+  if (!x || !work || !dist) return fail(BA3C_ERR_INVALID, "null pointer");
+  CHECK(tsne_range(n, d));
+  if (!check_ptr(x) || !check_ptr(work) || !check_ptr(dist))
+    return fail(BA3C_ERR_INVALID, "x, work and dist must be 16-byte aligned");
+  HIP_TRY(launch_tsne_sqdist(static_cast<hipStream_t>(stream), x, n, d, work, dist));
+  return BA3C_OK;
+}
+
+int ba3c_tsne_affinities(void* stream, const float* dist, int32_t n, double perplexity, void* work,
+                         double* beta, float* p) {
+  if (!dist || !work || !beta || !p) return fail(BA3C_ERR_INVALID, "null pointer");
+  CHECK(tsne_range(n, 1));
+  if (!std::isfinite(perplexity) || perplexity < 1.0 || perplexity > (n - 1) / 3.0)
+    return fail(BA3C_ERR_INVALID, "perplexity must be finite and in [1, (n - 1) / 3]");
+  if (!check_ptr(dist) || !check_ptr(work) || !check_ptr(beta) || !check_ptr(p))
+    return fail(BA3C_ERR_INVALID, "dist, work, beta and p must be 16-byte aligned");
+  HIP_TRY(launch_tsne_affinities(static_cast<hipStream_t>(stream), dist, n, std::log(perplexity), beta, p));
+  return BA3C_OK;
+}
+
+int ba3c_tsne_step(void* stream, const float* p, int32_t n, float* y, float* vel, float* gains, double exag,
+                   double momentum, double lr, void* work, double* kl_out) {
+  if (!p || !y || !vel || !gains || !work) return fail(BA3C_ERR_INVALID, "null pointer");
+  CHECK(tsne_range(n, 1));
+  if (!std::isfinite(lr) || lr <= 0.0) return fail(BA3C_ERR_INVALID, "lr must be finite and > 0");
+  if (!(momentum >= 0.0 && momentum < 1.0)) return fail(BA3C_ERR_INVALID, "momentum must be in [0, 1)");
+  if (!check_ptr(p) || !check_ptr(y) || !check_ptr(vel) || !check_ptr(gains) || !check_ptr(work) ||
+      (reinterpret_cast<uintptr_t>(kl_out) & 7))
+    return fail(BA3C_ERR_INVALID, "p, y, vel, gains and work must be 16-byte and kl_out 8-byte aligned");
+  TsneWork w;
+  tsne_work_layout(n, 1, work, &w);
+  HIP_TRY(launch_tsne_step(static_cast<hipStream_t>(stream),
+                           TsneStepArgs{p, reinterpret_cast<float2*>(y), reinterpret_cast<float2*>(vel),
+                                        reinterpret_cast<float2*>(gains), w.part, kl_out, n, tsne_rows_per_wave(n),
+                                        exag, momentum, lr}));
   return BA3C_OK;
 }
 

@@ -668,6 +668,34 @@ int ba3c_boxing_view(void* stream, const int32_t* game, int32_t n_envs, const in
                      int32_t n_sel, const uint8_t* palette, const uint8_t* hud, int32_t scale,
                      uint8_t* out);
 
+/* ---- Exact t-SNE of a set of feature vectors ------------------------------------------------ */
+
+/* The embedding of ba3c_amd/tsne.py, which states the rule and is the oracle (DESIGN.md section
+ * 23).  Handle-free; 8 <= n <= 8192, 1 <= d <= 2048.  `work` is ba3c_tsne_workspace_size(n, d)
+ * bytes (0 for an n or d out of range); the size for d = 1 serves ba3c_tsne_affinities and
+ * ba3c_tsne_step, and a larger workspace serves every call.
+ *
+ * ba3c_tsne_sqdist: x float32 [n][d] -> dist float32 [n][n], the squared distances of the rows of
+ * x centred by its column means; dist is symmetric bit for bit and zero on the diagonal.  Three
+ * launches.
+ * ba3c_tsne_affinities: dist -> beta float64 [n] and the joint affinities p float32 [n][n] at
+ * `perplexity` in [1, (n - 1) / 3].  Two launches: the conditional rows go into p, which is then
+ * symmetrised in place.
+ * ba3c_tsne_step: one iteration in place on y, vel, gains (float32 [n][2]) from p, with
+ * exaggeration `exag`, `momentum` in [0, 1) and `lr` > 0; where kl_out is not null it receives the
+ * iteration's KL divergence (of the y the iteration started from).  Two launches.
+ *
+ * Each refuses, on the host before any launch and in this order: (1) a null pointer (kl_out may be
+ * null); (2) n, then d, out of range; (3) a perplexity that is not finite or out of range; (4) an
+ * lr that is not finite or <= 0, then a momentum outside [0, 1); (5) a pointer that is not 16-byte
+ * aligned (kl_out: 8-byte).  They never synchronise and never allocate. */
+size_t ba3c_tsne_workspace_size(int32_t n, int32_t d);
+int ba3c_tsne_sqdist(void* stream, const float* x, int32_t n, int32_t d, void* work, float* dist);
+int ba3c_tsne_affinities(void* stream, const float* dist, int32_t n, double perplexity, void* work,
+                         double* beta, float* p);
+int ba3c_tsne_step(void* stream, const float* p, int32_t n, float* y, float* vel, float* gains,
+                   double exag, double momentum, double lr, void* work, double* kl_out);
+
 #ifdef __cplusplus
 }
 #endif
