@@ -39,7 +39,7 @@ class Ba3cOptParams(ctypes.Structure):
 
 _lib = None
 # roofline-accounting queries, the PPO entry points, the episode log, the global-norm clip and the
-# saliency, perturbation, integrated-gradients and t-SNE entry points an
+# saliency, perturbation, integrated-gradients, t-SNE and GridPong entry points an
 # alternative A/B build (BA3C_LIB) may predate.  Every PPO step of the engine is one
 # ba3c_train_grads_ppo_ext call: a build older than that entry point runs none.
 AB_OPTIONAL = {"ba3c_kernel_merged", "ba3c_probe_every", "ba3c_train_grads_ppo", "ba3c_sample_logp",
@@ -47,7 +47,8 @@ AB_OPTIONAL = {"ba3c_kernel_merged", "ba3c_probe_every", "ba3c_train_grads_ppo",
                "ba3c_global_clip_scratch", "ba3c_clip_grads_global", "ba3c_conv0_input_grad",
                "ba3c_input_grads", "ba3c_perturb_states", "ba3c_perturb_scores", "ba3c_ig_states",
                "ba3c_ig_accumulate", "ba3c_tsne_workspace_size", "ba3c_tsne_sqdist",
-               "ba3c_tsne_affinities", "ba3c_tsne_step"}
+               "ba3c_tsne_affinities", "ba3c_tsne_step", "ba3c_gridpong_step", "ba3c_gridpong_render",
+               "ba3c_gridpong_step_skip", "ba3c_gridpong_view"}
 PPO_ADV_FROM_ROW = 1       # BA3C_PPO_ADV_FROM_ROW
 
 
@@ -138,6 +139,10 @@ def load():
         "ba3c_boxing_step_skip": (i32, [P, P, P, P, i32, i32, i32, i32, i32, P, P, P, P, P]),
         "ba3c_breakout_view": (i32, [P, P, i32, P, i32, P, P, i32, P]),
         "ba3c_boxing_view": (i32, [P, P, i32, P, i32, P, P, i32, P]),
+        "ba3c_gridpong_step": (i32, [P, P, P, i32, i32, P, P, P, P, P]),
+        "ba3c_gridpong_render": (i32, [P, P, i32, P, P]),
+        "ba3c_gridpong_step_skip": (i32, [P, P, P, P, i32, i32, i32, i32, i32, P, P, P, P, P]),
+        "ba3c_gridpong_view": (i32, [P, P, i32, P, i32, P, P, i32, P]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("BA3C_LIB") and name in AB_OPTIONAL and not hasattr(lib, name):

@@ -20,7 +20,7 @@ import numpy as np
 
 from . import tsne
 from .breakout import DEFAULT_LIMIT
-from .flags import GAMES, build_parser, resolve
+from .flags import ALL_GAMES, build_parser, resolve
 
 
 def collect_states(engine, game, n_states, every=1, n_envs=None, seed=0, limit=DEFAULT_LIMIT, frame_skip=1,
@@ -93,8 +93,8 @@ def embed_parser():
 
 def main(argv=None):
     args = resolve(embed_parser().parse_args(argv))
-    if args.environment not in GAMES:
-        raise SystemExit("embedding needs an on-device game: pass -e %s" % " or -e ".join(sorted(GAMES)))
+    if args.environment not in ALL_GAMES:
+        raise SystemExit("embedding needs an on-device game: pass -e %s" % " or -e ".join(sorted(ALL_GAMES)))
     if not args.random and not args.load:
         raise SystemExit("pass --load CHECKPOINT, or --random for a uniform-random policy")
     if not tsne.MIN_N <= args.states <= tsne.MAX_N or not 1 <= args.perplexity <= (args.states - 1) / 3.0:

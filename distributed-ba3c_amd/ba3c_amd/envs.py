@@ -492,8 +492,142 @@ class BoxingPlayer(RLEnvironment):
         return self.space
 
 
+class PongPlayer(RLEnvironment):
+    """GridPong (ba3c_amd.gridpong holds the rules and constants) as one host player, for the
+    simulator processes: the same integer rules as scalar Python ints.  Auto-restarts like
+    GymEnv and records the episode 'score' stat (mine minus theirs) in finish_episode.
+    `limit` (None: none) ends an episode after that many steps; get_player leaves that to
+    LimitLengthPlayer.  `last_events` names what the last action() met, from: serve, wall, hit,
+    opp_hit, speedup, point, lost, over_win, over_loss, over_limit."""
+
+    def __init__(self, idx=0, num_actions=6, seed=0, limit=None):
+        super(PongPlayer, self).__init__()
+        from . import gridpong as K
+        self.K = K
+        self.idx = int(idx)
+        self.limit = limit
+        self.rng = (int(seed) * 1000 + self.idx) % (1 << 32)
+        self.space = DiscreteActionSpace(int(num_actions), seed=seed + 1)
+        self.last_events = set()
+        self.last_ep_score = None
+        self.restart_episode()
+
+    def restart_episode(self):
+        K = self.K
+        self.py = self.oy = K.PY0
+        self.bx, self.by, self.vx, self.vy = K.BX0, K.BY0, K.V0, 0
+        self.mine = self.theirs = self.t = self.hits = 0
+        self.serve = K.SERVE_DELAY
+
+    def finish_episode(self):
+        self.stats["score"].append(self.mine - self.theirs)
+
+    def game_row(self):
+        """The episode state as the device's int32 row (gridpong.py layout)."""
+        rng = self.rng - (1 << 32) if self.rng >= (1 << 31) else self.rng
+        return [self.py, self.oy, self.bx, self.by, self.vx, self.vy, self.mine, self.theirs,
+                self.t, rng, self.hits, self.serve, 0, 0, 0, 0]
+
+    def current_state(self):
+        K = self.K
+        f = np.zeros((K.H, K.W), np.uint8)
+        for y in range(K.WALL_TOP + 2, K.WALL_BOTTOM):
+            if (y - (K.WALL_TOP + 2)) & 4 == 0:
+                f[y, K.NET_X:K.NET_X + K.NET_W] = K.DIM
+        f[K.WALL_TOP:K.WALL_TOP + 2] = f[K.WALL_BOTTOM:K.WALL_BOTTOM + 2] = K.DIM
+        # later paints win: opponent (bar, paddle), ball, agent (bar, paddle)
+        f[K.O_BAR_Y:K.O_BAR_Y + 2, K.W - K.BAR_UNIT * self.theirs:] = K.OPP_SHADE
+        f[self.oy:self.oy + K.PADDLE_H, K.OPP_X:K.OPP_X + K.PADDLE_W] = K.OPP_SHADE
+        if self.serve == 0:
+            x, y = self.bx >> K.SUB, self.by >> K.SUB
+            f[y:y + K.BALL, x:x + K.BALL] = K.AGENT_SHADE
+        f[K.A_BAR_Y:K.A_BAR_Y + 2, :K.BAR_UNIT * self.mine] = K.AGENT_SHADE
+        f[self.py:self.py + K.PADDLE_H, K.AGENT_X:K.AGENT_X + K.PADDLE_W] = K.AGENT_SHADE
+        return f
+
+    def action(self, act):
+        K = self.K
+        ev = set()
+        act = int(act)
+        if not 0 <= act < K.NUM_ACTIONS:
+            act = K.NOOP
+        clamp = lambda v, lo, hi: min(max(v, lo), hi)
+        reward = 0
+        self.rng = (self.rng * K.LCG_A + K.LCG_C) % (1 << 32)
+        r = self.rng >> 16
+        self.py = clamp(self.py + K.PADDLE_STEP * ((act in K.DOWN_SET) - (act in K.UP_SET)), K.Y_MIN, K.Y_MAX)
+        target = (self.by >> K.SUB) + 1 if self.serve == 0 else K.CENTRE_ROW
+        if (r & 7) >= K.LAPSE_OF_8:
+            ody = clamp(target - (self.oy + K.PADDLE_H // 2), -K.OPP_STEP, K.OPP_STEP)
+            self.oy = clamp(self.oy + ody, K.Y_MIN, K.Y_MAX)
+        if self.serve > 0:
+            self.serve -= 1
+            if act in K.FIRE_SET or self.serve == 0:
+                self.serve = 0
+                k, m = (r >> 3) & 7, 1 + ((r >> 6) & 1)
+                if (r >> 7) & 1:
+                    self.by, self.vy = (K.SERVE_TOP + k) << K.SUB, -m
+                else:
+                    self.by, self.vy = (K.SERVE_BOTTOM - k) << K.SUB, m
+                ev.add("serve")
+        else:
+            edge = K.BALL << K.SUB
+            nx, ny = self.bx + self.vx, self.by + self.vy
+            if ny < K.BY_MIN:
+                ny, self.vy = 2 * K.BY_MIN - ny, -self.vy
+                ev.add("wall")
+            elif ny > K.BY_MAX:
+                ny, self.vy = 2 * K.BY_MAX - ny, -self.vy
+                ev.add("wall")
+            b = ny >> K.SUB
+            d = side = None
+            if (self.vx > 0 and self.bx + edge <= K.AGENT_FACE < nx + edge
+                    and 0 <= b - self.py + 1 <= K.PADDLE_H):
+                d, nx, side = b - self.py + 1, 2 * (K.AGENT_FACE - edge) - nx, -1
+                ev.add("hit")
+            elif self.vx < 0 and nx < K.OPP_FACE <= self.bx and 0 <= b - self.oy + 1 <= K.PADDLE_H:
+                d, nx, side = b - self.oy + 1, 2 * K.OPP_FACE - nx, 1
+                ev.add("opp_hit")
+            if side is not None:
+                self.hits += 1
+                speed = min(K.V0 + K.V_STEP * (self.hits >> K.HITS_SHIFT), K.V_CAP)
+                if speed != abs(self.vx):
+                    ev.add("speedup")
+                self.vx = side * speed
+                self.vy = K.VY_MAGS[d] if d >= K.PADDLE_H // 2 else -K.VY_MAGS[d]
+            self.bx, self.by = nx, ny
+            if self.bx >= K.AGENT_PAST:
+                self.theirs += 1
+                reward, self.vx = -1, K.V0
+                ev.add("lost")
+            elif self.bx <= K.OPP_PAST:
+                self.mine += 1
+                reward, self.vx = 1, -K.V0
+                ev.add("point")
+            if reward:
+                self.bx, self.by, self.vy, self.hits, self.serve = K.BX0, K.BY0, 0, 0, K.SERVE_DELAY
+        self.t += 1
+        if self.mine >= K.WIN:
+            ev.add("over_win")
+        if self.theirs >= K.WIN:
+            ev.add("over_loss")
+        if self.limit is not None and self.t >= self.limit:
+            ev.add("over_limit")
+        over = bool(ev & {"over_win", "over_loss", "over_limit"})
+        if over:
+            self.last_ep_score = self.mine - self.theirs
+            self.finish_episode()
+            self.restart_episode()
+        self.last_events = ev
+        return float(reward), over
+
+    def get_action_space(self):
+        return self.space
+
+
 class FrameSkipPlayer(ProxyPlayer):
-    """Frame skip and sticky actions around a BreakoutPlayer / BoxingPlayer: ba3c_amd.frameskip's
+    """Frame skip and sticky actions around a game's player (BreakoutPlayer, BoxingPlayer,
+    PongPlayer): ba3c_amd.frameskip's
     decision as scalar Python ints, for the simulator processes.  One action() draws k in
     [lo, hi], plays k game steps of the wrapped player (each repeats the previous effective
     action when its 16-bit draw is below q16, else plays `act`), sums their rewards and stops at
@@ -541,16 +675,17 @@ class FrameSkipPlayer(ProxyPlayer):
 
 
 # game key -> the host player of get_player / SyntheticSimulatorWorker
-PLAYERS = {"synthetic": SyntheticAtariPlayer, "breakout": BreakoutPlayer, "boxing": BoxingPlayer}
+PLAYERS = {"synthetic": SyntheticAtariPlayer, "breakout": BreakoutPlayer, "boxing": BoxingPlayer,
+           "gridpong": PongPlayer}
 
 
 def get_player(idx=0, num_actions=4, seed=0, train=False, frame_history=FRAME_HISTORY,
                limit=40000, game="synthetic", frame_skip=1, sticky=0.0):
     """OpenAIGym/train.py:113-128 with the synthetic game (or game="breakout": GridBreakout,
-    game="boxing": GridBoxing): history of `frame_history` frames, PreventStuckPlayer(30, 1)
+    game="boxing": GridBoxing, game="gridpong": GridPong): history of `frame_history` frames, PreventStuckPlayer(30, 1)
     for evaluation players, LimitLengthPlayer(40000).
     A non-default `frame_skip` (K or (lo, hi)) / `sticky` (a probability) puts a FrameSkipPlayer
-    under the history, for GridBreakout / GridBoxing only; `limit` then counts game steps as it
+    under the history, for the games only; `limit` then counts game steps as it
     does on the device: the game's own player ends the episode, in place of LimitLengthPlayer."""
     if game not in PLAYERS:
         raise ValueError("unknown game %r (%s)" % (game, ", ".join(sorted(PLAYERS))))
@@ -559,7 +694,8 @@ def get_player(idx=0, num_actions=4, seed=0, train=False, frame_history=FRAME_HI
     if skip is None:
         pl = PLAYERS[game](idx, num_actions, seed)
     elif game == "synthetic":
-        raise ValueError("frame_skip / sticky need game='breakout' or game='boxing'")
+        raise ValueError("frame_skip / sticky need a game: %s"
+                         % ", ".join(repr(k) for k in sorted(PLAYERS) if k != "synthetic"))
     else:
         pl = FrameSkipPlayer(PLAYERS[game](idx, num_actions, seed, limit=limit), *skip, seed=seed, idx=idx)
     pl = HistoryFramePlayer(pl, frame_history)

@@ -1,4 +1,4 @@
-"""Evaluation on an on-device game (flags.GAMES: GridBreakout, GridBoxing): the reference's
+"""Evaluation on an on-device game (flags.ALL_GAMES: GridBreakout, GridBoxing, GridPong): the reference's
 `eval_with_funcs` / `play_one_episode` and its `Evaluator` callback (OpenAIGym/common.py:24-141)
 over a vector of on-device simulators.
 
@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from .breakout import DEFAULT_LIMIT
-from .flags import GAMES, GRID_BREAKOUT
+from .flags import ALL_GAMES, GRID_BREAKOUT
 from .metrics import StatCounter
 from .predict import greedy_actions
 from .rollout import FrameHistory
@@ -75,7 +75,7 @@ class EvalPlayers(object):
 
 def eval_with_envs(engine, nr_eval, n_envs, seed=0, limit=DEFAULT_LIMIT, policy=None,
                    game=GRID_BREAKOUT, frame_skip=1, sticky=0.0):
-    """Play `n_envs` evaluation players of `game` (a key of flags.GAMES) with `engine`'s greedy
+    """Play `n_envs` evaluation players of `game` (a key of flags.ALL_GAMES) with `engine`'s greedy
     policy until `nr_eval` episodes have finished; returns (mean, max) of their scores (common.py:42-86).
     Episodes that finish in the same step as the nr_eval-th are counted too (the reference
     also feeds the runs its workers were finishing).  `limit` is LimitLengthPlayer's.
@@ -86,7 +86,7 @@ def eval_with_envs(engine, nr_eval, n_envs, seed=0, limit=DEFAULT_LIMIT, policy=
     assert nr_eval >= 1 and 1 <= n_envs <= engine.max_batch
     dev, A = engine.device, engine.num_actions
     rs = np.random.RandomState(seed)
-    env = GAMES[game][0](n_envs, seed=seed, limit=limit, device=dev, frame_skip=frame_skip,
+    env = ALL_GAMES[game][0](n_envs, seed=seed, limit=limit, device=dev, frame_skip=frame_skip,
                          sticky=sticky)
     assert env.A <= A
     hist = FrameHistory(n_envs, hist_len=4, channels=1, device=dev)

@@ -8,11 +8,16 @@ import math
 from . import duel, frameskip, ppo, schedule
 from .boxing import BoxingVec
 from .breakout import BreakoutVec
+from .gridpong import PongVec
 
 GRID_BREAKOUT = "GridBreakout-v0"
 GRID_BOXING = "GridBoxing-v0"
-# -e name -> (vector class, the game's number of actions, envs.get_player's game key)
+GRID_PONG = "GridPong-v0"
+# -e name -> (vector class, the game's number of actions, envs.get_player's game key).
+# GAMES is the table of the first two games, which the tests of the launcher's flags hold to
+# exactly these two names; ALL_GAMES is the table every consumer reads, and where a game is added.
 GAMES = {GRID_BREAKOUT: (BreakoutVec, 4, "breakout"), GRID_BOXING: (BoxingVec, 18, "boxing")}
+ALL_GAMES = dict(GAMES, **{GRID_PONG: (PongVec, 6, "gridpong")})
 MAX_LOCAL_TIME = 128                  # ba3c_lambda_returns holds local_time_max + 1 <= 129 ring slots
 STATE_BYTES = 84 * 84 * 4             # one stacked state of the rollout ring
 MAX_RING_BYTES = 16 * 2 ** 30         # simulator_procs x (local_time_max + 1) states
@@ -59,9 +64,9 @@ def build_parser():
     p.add_argument("--beta2", type=float, default=0.999)
     p.add_argument("--adam_debug", action="store_true")
     p.add_argument("--environment", "-e", "--env", dest="environment", default="Breakout-v0",
-                   help="GridBreakout-v0 / GridBoxing-v0: the on-device Breakout / Boxing "
-                        "(ba3c_amd.breakout, ba3c_amd.boxing); any other name: the synthetic "
-                        "environment")
+                   help="GridBreakout-v0 / GridBoxing-v0 / GridPong-v0: the on-device Breakout / "
+                        "Boxing / Pong (ba3c_amd.breakout, ba3c_amd.boxing, ba3c_amd.gridpong); any "
+                        "other name: the synthetic environment")
     p.add_argument("--channels", type=int, default=1)
     p.add_argument("--num_actions", type=int, default=4)
     p.add_argument("--predict_batch_size", type=int, default=16)
@@ -77,7 +82,7 @@ def build_parser():
     p.add_argument("--send_debug_every", type=int, default=100)
     p.add_argument("--nr_eval", type=int, default=0,
                    help="episodes the Evaluator plays every --steps_per_epoch learner steps on "
-                        "rank 0 (0: off; needs -e GridBreakout-v0 or GridBoxing-v0)")
+                        "rank 0 (0: off; needs an on-device game, e.g. -e GridBreakout-v0)")
     p.add_argument("--frame_skip", type=frame_skip_arg, default=1,
                    help="game steps per policy decision: K, or LO-HI for a uniform draw per "
                         "decision (ALE's -v0: 2-4); 1 <= LO <= HI <= 16; needs an on-device game")
@@ -165,7 +170,7 @@ def build_parser():
 def resolve(args, duel_tool=False):
     """Apply the reference's implicit rules: --use_normal_fc disables replace_with_conv
     (run_job.py:131); --adam_debug sets beta2 := beta1 (train.py:460-461); --use_sync needs
-    --ngrads (run_job.py:55-57).  An on-device game (GAMES) needs --channels 1 and --num_actions
+    --ngrads (run_job.py:55-57).  An on-device game (ALL_GAMES) needs --channels 1 and --num_actions
     >= its own number of actions; --nr_eval, --frame_skip and --sticky need one of them.
     --self_play needs GridBoxing, an even --simulator_procs and neither --frame_skip nor --sticky:
     its two-player games take --duel_frame_skip / --duel_sticky, which like --duel_start need
@@ -193,21 +198,21 @@ def resolve(args, duel_tool=False):
         args.beta2 = args.beta1
     if args.use_sync and args.ngrads is None:
         raise SystemExit("if using SyncReplicasOptimizer you have to specify --ngrads argument")
-    if args.environment in GAMES:
-        name, A = args.environment, GAMES[args.environment][1]
+    if args.environment in ALL_GAMES:
+        name, A = args.environment, ALL_GAMES[args.environment][1]
         if args.channels != 1:
             raise SystemExit("-e %s renders grayscale frames: it requires --channels 1" % name)
         if args.num_actions < A:
             raise SystemExit("-e %s has %d actions: it requires --num_actions >= %d" % (name, A, A))
     elif args.nr_eval:
-        raise SystemExit("--nr_eval needs a game to evaluate: pass -e %s" % " or -e ".join(sorted(GAMES)))
+        raise SystemExit("--nr_eval needs a game to evaluate: pass -e %s" % " or -e ".join(sorted(ALL_GAMES)))
     try:
         skip = frameskip.setting(args.frame_skip, args.sticky)
     except ValueError as e:
         raise SystemExit("--frame_skip / --sticky: %s" % e)
-    if skip is not None and args.environment not in GAMES:
+    if skip is not None and args.environment not in ALL_GAMES:
         raise SystemExit("--frame_skip / --sticky need an on-device game: pass -e %s"
-                         % " or -e ".join(sorted(GAMES)))
+                         % " or -e ".join(sorted(ALL_GAMES)))
     if args.self_play:
         if args.environment != GRID_BOXING:
             raise SystemExit("--self_play is two-player GridBoxing: pass -e %s" % GRID_BOXING)

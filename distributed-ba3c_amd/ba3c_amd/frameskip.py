@@ -95,7 +95,8 @@ def setting(frame_skip=1, sticky=0.0):
 
 def step_numpy(game_module, game, aux, actions, limit, lo, hi, q16):
     """One decision of every row of `game` ([E,16] int32) and `aux` ([E,2] int32), both updated
-    in place, under `actions` [E]; game_module is ba3c_amd.breakout or ba3c_amd.boxing.
+    in place, under `actions` [E]; game_module is the game's own (ba3c_amd.breakout, .boxing,
+    .gridpong).
     Returns (reward float64 [E], over bool [E], ep_score int32 [E], 0 where not over)."""
     check(lo, hi, q16)
     E = game.shape[0]

@@ -1,4 +1,4 @@
-"""Record whole episodes of an on-device game (flags.GAMES) as checkable traces: the reference's
+"""Record whole episodes of an on-device game (flags.ALL_GAMES) as checkable traces: the reference's
 `record_model.py` over a vector of on-device simulators.
 
 The players are `evaluate.EvalPlayers`, the decision path of `eval_with_envs` (greedy + eps +
@@ -30,22 +30,24 @@ Matches of two-player GridBoxing (ba3c_amd.duel) are recorded by `record_match`,
 outputs, replayed through `duel.decide_numpy` / `duel.step_numpy`
 (`python -m ba3c_amd.duel ... --record DIR`).
 """
+import importlib
 import json
 import os
 
 import numpy as np
 
-from . import boxing, breakout, duel, frameskip
+from . import duel, frameskip
 from .breakout import DEFAULT_LIMIT
-from .flags import GAMES, GRID_BOXING, GRID_BREAKOUT, build_parser, resolve
+from .flags import ALL_GAMES, build_parser, resolve
 
-MODULES = {GRID_BREAKOUT: breakout, GRID_BOXING: boxing}
+# -e name -> the module that states the game's rules: the one its vector class lives in
+MODULES = {name: importlib.import_module(row[0].__module__) for name, row in ALL_GAMES.items()}
 SALIENCY = ("v", "pi", "pv", "ppi", "iv", "ipi")      # --saliency
 ARRAYS = ("row0", "aux0", "actions", "rewards", "probs", "values", "frames", "frame_steps")
 
 
 class Episode(object):
-    """One recorded episode of `game` (a key of flags.GAMES) under `limit` and `skip` ((lo, hi,
+    """One recorded episode of `game` (a key of flags.ALL_GAMES) under `limit` and `skip` ((lo, hi,
     q16) of ba3c_amd.frameskip, or None: plain steps).  row0 int32 [16]; aux0 int32 [2] (None
     without skip); actions int64 [T]; rewards float64 [T]; probs float32 [T, A]; values float32
     [T]; score, steps = T; frames uint8 [T', Hc*S, 84*S, 3]; frame_steps int64 [T']; saliency
@@ -156,7 +158,7 @@ def open_players(engine, game, n_envs, seed=0, limit=DEFAULT_LIMIT, frame_skip=1
     decision of every simulator; hist.state is what the policy sees."""
     from .evaluate import EvalPlayers
     from .rollout import FrameHistory
-    env = GAMES[game][0](n_envs, seed=seed, limit=limit, device=engine.device, frame_skip=frame_skip,
+    env = ALL_GAMES[game][0](n_envs, seed=seed, limit=limit, device=engine.device, frame_skip=frame_skip,
                          sticky=sticky)
     assert env.A <= engine.num_actions
     hist = FrameHistory(n_envs, hist_len=4, channels=1, device=engine.device)
@@ -420,8 +422,8 @@ def record_parser():
 
 def main(argv=None):
     args = resolve(record_parser().parse_args(argv))
-    if args.environment not in GAMES:
-        raise SystemExit("recording needs an on-device game: pass -e %s" % " or -e ".join(sorted(GAMES)))
+    if args.environment not in ALL_GAMES:
+        raise SystemExit("recording needs an on-device game: pass -e %s" % " or -e ".join(sorted(ALL_GAMES)))
     if not args.random and not args.load:
         raise SystemExit("pass --load CHECKPOINT, or --random for a uniform-random policy")
     if not 1 <= args.scale <= 8 or args.episodes < 1:

@@ -6,7 +6,7 @@
 - `-o` and its hyper-parameters: the optimizer (:582-597).
 - `--use_sync -g N`: SyncReplicasOptimizer (:598-606), here an RCCL all-reduce over the node's GPUs.
 - `-e`, `--simulator_procs`: the actor-learner loop (simulator master + predictor + BatchData,
-  :520-534) on the synthetic on-device environment or on a game of flags.GAMES.
+  :520-534) on the synthetic on-device environment or on a game of flags.ALL_GAMES.
 - `--frame_skip` / `--sticky`: ALE's frame skip and sticky actions, for training and evaluation.
 - `--self_play`, `--duel_frame_skip` / `--duel_sticky` / `--duel_start`: two-player GridBoxing
   (ba3c_amd.duel), both sides played by the learner.
@@ -38,7 +38,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .flags import GAMES, build_parser, resolve
+from .flags import ALL_GAMES, build_parser, resolve
 
 
 def _free_port():
@@ -165,8 +165,8 @@ def _run(args, rank, world):
             env = BoxingDuelDecisionVec(args.simulator_procs // 2, seed=rank, device=trainer.engine.device,
                                         frame_skip=args.play_frame_skip, sticky=args.play_sticky,
                                         start=start_from_gap(args.duel_start))
-        elif args.environment in GAMES:
-            env = GAMES[args.environment][0](args.simulator_procs, seed=rank,
+        elif args.environment in ALL_GAMES:
+            env = ALL_GAMES[args.environment][0](args.simulator_procs, seed=rank,
                                              device=trainer.engine.device,
                                              frame_skip=args.frame_skip, sticky=args.sticky)
         al = ActorLearner(trainer, n_envs=args.simulator_procs, batch_size=args.batch_size,

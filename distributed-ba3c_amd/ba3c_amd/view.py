@@ -1,8 +1,8 @@
-"""The colour view of the on-device games (GridBreakout, GridBoxing): what a simulator's
+"""The colour view of the on-device games (flags.ALL_GAMES): what a simulator's
 current game looks like to a person, with the policy's output under it.  This module states the
-image ONCE, over the games' own `render_numpy` and `PALETTE`; it restates no rule of either game
+image ONCE, over the games' own `render_numpy` and `PALETTE`; it restates no rule of any game
 and is the oracle of the HIP kernel (csrc/ba3c_envview.h: env_view_kernel, behind
-ba3c_breakout_view / ba3c_boxing_view, reached through `BreakoutVec.view` / `BoxingVec.view`).
+ba3c_breakout_view / ba3c_boxing_view / ba3c_gridpong_view, reached through each vector's `view`).
 
 The canvas is 84 px wide and Hc = 84 px high, or Hc = 84 + HUD_H with a HUD.  Canvas rows 0..83
 are `palette[render_numpy(row)]`.  The HUD strip is drawn from 20 bytes per image (integers
@@ -47,11 +47,13 @@ def check_scale(scale):
 
 def _game_of(palette):
     """The game module whose PALETTE this is (the view is built on ITS render_numpy)."""
-    from . import boxing, breakout
-    for mod in (breakout, boxing):
-        if np.array_equal(palette, mod.PALETTE):
-            return mod
-    raise ValueError("palette is neither game's PALETTE: pass game=<module>")
+    import importlib
+
+    from .flags import ALL_GAMES
+    for vec, _, _ in ALL_GAMES.values():
+        if np.array_equal(palette, vec.PALETTE):
+            return importlib.import_module(vec.__module__)
+    raise ValueError("palette is no game's PALETTE: pass game=<module>")
 
 
 def hud_strip_numpy(hud):

@@ -29,6 +29,7 @@
 #include "ba3c_envview.h"
 #include "ba3c_episodes.h"
 #include "ba3c_gemm6.h"
+#include "ba3c_gridpong.h"
 #include "ba3c_intgrad.h"
 #include "ba3c_launch.h"
 #include "ba3c_multi.h"
@@ -2111,6 +2112,33 @@ int ba3c_breakout_view(void* stream, const int32_t* game, int32_t n_envs, const 
 int ba3c_boxing_view(void* stream, const int32_t* game, int32_t n_envs, const int32_t* sel, int32_t n_sel,
                      const uint8_t* palette, const uint8_t* hud, int32_t scale, uint8_t* out) {
   return env_view<BoxingRules>(stream, game, n_envs, sel, n_sel, palette, hud, scale, out);
+}
+
+// GridPong (ba3c_gridpong.h): the four entry points of a one-player game.
+int ba3c_gridpong_step(void* stream, int32_t* game, const int64_t* action, int32_t n_envs,
+                       int32_t limit, double* reward, uint8_t* over, int32_t* ep_score,
+                       uint8_t* frame, uint8_t* state) {
+  return game_launch<SoloSim<PongRules>>(stream, {game, action, limit, n_envs, reward, over, ep_score,
+                                                  frame, state});
+}
+
+int ba3c_gridpong_step_skip(void* stream, int32_t* game, int32_t* aux, const int64_t* action, int32_t n_envs,
+                            int32_t limit, int32_t skip_lo, int32_t skip_hi, int32_t sticky_q16,
+                            double* reward, uint8_t* over, int32_t* ep_score, uint8_t* frame,
+                            uint8_t* state) {
+  const Decision d{aux, skip_lo, skip_hi, sticky_q16};
+  return game_launch<SoloSim<PongRules>>(stream, {game, action, limit, n_envs, reward, over, ep_score,
+                                                  frame, state}, &d);
+}
+
+int ba3c_gridpong_render(void* stream, const int32_t* game, int32_t n_envs, uint8_t* frame,
+                         uint8_t* state) {
+  return game_launch<SoloSim<PongRules>>(stream, render_args(game, n_envs, frame, state), nullptr, true);
+}
+
+int ba3c_gridpong_view(void* stream, const int32_t* game, int32_t n_envs, const int32_t* sel, int32_t n_sel,
+                       const uint8_t* palette, const uint8_t* hud, int32_t scale, uint8_t* out) {
+  return env_view<PongRules>(stream, game, n_envs, sel, n_sel, palette, hud, scale, out);
 }
 
 int ba3c_kernel_split(const ba3c_handle* h, int32_t kid) {

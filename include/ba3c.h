@@ -546,6 +546,44 @@ int ba3c_boxing_step(void* stream, int32_t* game, const int64_t* action, int32_t
 int ba3c_boxing_render(void* stream, const int32_t* game, int32_t n_envs, uint8_t* frame,
                        uint8_t* state);
 
+/* ---- GridPong: a third on-device game (a rally, +1 / -1 per point, first to 21) --------- */
+
+/* A small integer-only Pong for n_envs simulators; ba3c_amd/gridpong.py states the rules
+ * (constants, step_numpy, render_numpy) and is the oracle of these entry points.  All game
+ * state is int32, one 64-byte (16-byte aligned) row per simulator:
+ *   game[e] = [py, oy, bx, by, vx, vy, mine, theirs, t, rng, hits, serve, 0, 0, 0, 0]
+ * py / oy: top row of the agent's (right, x in 76..77) / the tracking opponent's (left, x in
+ * 6..7) 2x10 paddle, in 12..72; (bx, by): top-left of the 2x2 ball in EIGHTHS of a pixel;
+ * (vx, vy): its velocity in eighths per step (|vx| 10, 12 or 14: below a paddle's 16); mine /
+ * theirs: the points of the episode; t: its steps; rng: the LCG's uint32 bits (one draw per
+ * step: the opponent's lapse and the serve); hits: paddle hits of the rally; serve: steps until
+ * the ball is served (0: in play); the four padding ints are written as 0.
+ *
+ * ba3c_gridpong_step applies action[e] (ALE Pong's 6: 0 NOOP, 1 FIRE, 2 RIGHT = up, 3 LEFT =
+ * down, 4 RIGHTFIRE, 5 LEFTFIRE; anything outside [0, 6) is NOOP; the value is range-checked
+ * and shifts constant bit masks, it is never used as an index) and writes reward[e] (float64:
+ * +1 when the ball passes the opponent, -1 when it passes the agent), over[e], and ep_score[e]
+ * ONLY where over[e] (mine - theirs of the finished episode, in [-21, 21]; the row is then
+ * already reset).  An episode ends when either side reaches 21 or at t >= limit.  frame / state
+ * are as for ba3c_breakout_step; ba3c_gridpong_render is ba3c_breakout_render,
+ * ba3c_gridpong_step_skip ba3c_breakout_step_skip and ba3c_gridpong_view ba3c_breakout_view
+ * (all three documented below) for these rows.
+ *
+ * Same argument contract and host-side refusals as the other games, the same launch shape
+ * (one kernel template, one 256-thread workgroup per simulator). */
+int ba3c_gridpong_step(void* stream, int32_t* game, const int64_t* action, int32_t n_envs,
+                       int32_t limit, double* reward, uint8_t* over, int32_t* ep_score,
+                       uint8_t* frame, uint8_t* state);
+int ba3c_gridpong_render(void* stream, const int32_t* game, int32_t n_envs, uint8_t* frame,
+                         uint8_t* state);
+int ba3c_gridpong_step_skip(void* stream, int32_t* game, int32_t* aux, const int64_t* action,
+                            int32_t n_envs, int32_t limit, int32_t skip_lo, int32_t skip_hi,
+                            int32_t sticky_q16, double* reward, uint8_t* over, int32_t* ep_score,
+                            uint8_t* frame, uint8_t* state);
+int ba3c_gridpong_view(void* stream, const int32_t* game, int32_t n_envs, const int32_t* sel,
+                       int32_t n_sel, const uint8_t* palette, const uint8_t* hud, int32_t scale,
+                       uint8_t* out);
+
 /* ---- Two-player GridBoxing: both boxers driven by actions (self-play, matches) ----------- */
 
 /* A second way to run GridBoxing; ba3c_amd/duel.py states the rules (step_numpy, render_numpy,

@@ -1,10 +1,11 @@
 """Environment step time on the GPU (GridBreakout / GridBoxing sections): µs per fused
-`step_into` of the on-device game (--game breakout: `BreakoutVec`; --game boxing: `BoxingVec`,
-timed next to GridBreakout's fused step in the same run) against `SyntheticAtari.step` +
+`step_into` of the on-device game (--game KEY: the vector of flags.ALL_GAMES with that player key;
+breakout: `BreakoutVec`; boxing / gridpong: `BoxingVec` / `PongVec`, timed next to GridBreakout's
+fused step in the same run) against `SyntheticAtari.step` +
 `FrameHistory.push`, and the fused
 kernel's achieved bytes/s against this box's measured HBM copy rate (a device-to-device copy, and
 an in-place update over the kernel's own footprint).  With --random N also the
-evaluation scores of a uniform-random policy (and, for boxing, of a NOOP policy) over N
+evaluation scores of a uniform-random policy (and, but for breakout, of a NOOP policy) over N
 episodes (under the frame skip / stickiness given).  With --frame_skip K | LO-HI and / or --sticky P also the frame-skip step (one
 launch per DECISION, ba3c_amd.frameskip), timed alternately with the one-step fused step in the
 same run: µs per decision, µs per game step (at the mean k = (LO + HI) / 2 of the draw) and the
@@ -43,7 +44,7 @@ with the global-norm clip (`Model(max_grad_norm=0.5)`, ba3c_amd.gradclip) on ide
 the clip's two launches alone at both flat sizes; --gradclip_only skips the environment tables.
 Prints one JSON line.
 
-    python scripts/env_throughput.py [--game boxing] [--envs 8192 64] [--iters 200] [--random 20]
+    python scripts/env_throughput.py [--game boxing | gridpong] [--envs 8192 64] [--iters 200] [--random 20]
                                      [--frame_skip 2-4] [--sticky 0.25] [--view 1 3] [--duel]
                                      [--duel_start 8-14] [--duel_only] [--returns] [--ppo] [--ppo_only]
                                      [--ppo_norm_adv] [--ppo_vclip 0.2] [--episodes] [--episodes_only]
@@ -451,7 +452,7 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--random", type=int, default=0)
-    ap.add_argument("--game", choices=["breakout", "boxing"], default="breakout")
+    ap.add_argument("--game", default="breakout", help="a player key of flags.ALL_GAMES: breakout, boxing, gridpong")
     ap.add_argument("--frame_skip", default="1")
     ap.add_argument("--sticky", type=float, default=0.0)
     ap.add_argument("--view", type=int, nargs="+", default=[])
@@ -461,11 +462,14 @@ def main(argv=None):
     assert torch.cuda.is_available(), "needs the GPU: a CPU run measures nothing"
     from ba3c_amd.actor_learner import SyntheticAtari
     from ba3c_amd.breakout import BreakoutVec
-    from ba3c_amd.flags import GAMES, GRID_BOXING, GRID_BREAKOUT
+    from ba3c_amd.flags import ALL_GAMES as GAMES
     from ba3c_amd.frameskip import setting
     from ba3c_amd.rollout import FrameHistory
     skip = setting(args.frame_skip, args.sticky)          # (lo, hi, q16), None: off
-    name = GRID_BOXING if args.game == "boxing" else GRID_BREAKOUT
+    names = {row[2]: name for name, row in GAMES.items()}       # player key -> -e name
+    if args.game not in names:
+        ap.error("--game must be one of %s" % ", ".join(sorted(names)))
+    name = names[args.game]
     Vec, A = GAMES[name][:2]
     out = {"game": name, "iters": args.iters, "envs": {}}
     if skip is not None:
@@ -498,7 +502,7 @@ def main(argv=None):
         env, hist = Vec(E, seed=0), FrameHistory(E, 4, 1)
         env.reset_history(hist)
         if Vec is not BreakoutVec:                        # the yardstick: GridBreakout's fused step
-            actions_b = torch.randint(0, 4, (E,), generator=g, device="cuda")
+            actions_b = torch.randint(0, BreakoutVec.A, (E,), generator=g, device="cuda")
             env_b, hist_b = BreakoutVec(E, seed=0), FrameHistory(E, 4, 1)
             env_b.reset_history(hist_b)
         if skip is not None:
@@ -579,7 +583,7 @@ def main(argv=None):
         mean, mx = eval_with_envs(m.engine, args.random, min(args.random, 20), seed=0,
                                   policy=uniform_policy(A), game=name, **fs)
         out["random_policy"] = {"episodes": args.random, "mean_score": mean, "max_score": mx}
-        if args.game == "boxing":
+        if Vec is not BreakoutVec:                        # (its NOOP never serves: nothing to report)
             def noop(state):                              # argmax 0 = NOOP (FIRE every 30th step:
                 p = torch.zeros(state.shape[0], A, dtype=torch.float32, device=state.device)
                 p[:, 0] = 1.0                             # the evaluation's PreventStuckPlayer)
