@@ -69,6 +69,27 @@ def row_entropy(dm, beta):
     return np.log(s) + beta * (dm * e).sum() / s, e, s
 
 
+def conditional_row_numpy(row, i, target):
+    """One row of the bisection: row float64 [N] = d_i., target = log u.  -> (beta_i, the
+    conditional row p_.|i float64 [N], zero at i)."""
+    others = np.arange(row.shape[0]) != i
+    dm = row[others] - row[others].min()
+    b, lo, hi = 1.0, -np.inf, np.inf
+    for it in range(MAX_BISECT + 1):
+        h, e, s = row_entropy(dm, b)
+        if abs(h - target) <= ENTROPY_TOL or it == MAX_BISECT:
+            break
+        if h > target:
+            lo = b
+            b = b * 2.0 if hi == np.inf else 0.5 * (b + hi)
+        else:
+            hi = b
+            b = b * 0.5 if lo == -np.inf else 0.5 * (b + lo)
+    out = np.zeros(row.shape[0])
+    out[others] = e / s
+    return b, out
+
+
 def conditional_numpy(dist, perplexity):
     """dist [N, N] -> (beta float64 [N], P_c float64 [N, N])."""
     dist = np.asarray(dist, np.float64)
@@ -76,20 +97,7 @@ def conditional_numpy(dist, perplexity):
     target = np.log(check_perplexity(n, perplexity))
     beta, pc = np.ones(n), np.zeros((n, n))
     for i in range(n):
-        others = np.arange(n) != i
-        dm = dist[i, others] - dist[i, others].min()
-        b, lo, hi = 1.0, -np.inf, np.inf
-        for it in range(MAX_BISECT + 1):
-            h, e, s = row_entropy(dm, b)
-            if abs(h - target) <= ENTROPY_TOL or it == MAX_BISECT:
-                break
-            if h > target:
-                lo = b
-                b = b * 2.0 if hi == np.inf else 0.5 * (b + hi)
-            else:
-                hi = b
-                b = b * 0.5 if lo == -np.inf else 0.5 * (b + lo)
-        beta[i], pc[i, others] = b, e / s
+        beta[i], pc[i] = conditional_row_numpy(dist[i], i, target)
     return beta, pc
 
 
