@@ -39,7 +39,7 @@ class Ba3cOptParams(ctypes.Structure):
 
 _lib = None
 # roofline-accounting queries, the PPO entry points, the episode log, the global-norm clip and the
-# saliency, perturbation, integrated-gradients, t-SNE and GridPong entry points an
+# saliency, perturbation, integrated-gradients, t-SNE, GridPong and PCA entry points an
 # alternative A/B build (BA3C_LIB) may predate.  Every PPO step of the engine is one
 # ba3c_train_grads_ppo_ext call: a build older than that entry point runs none.
 AB_OPTIONAL = {"ba3c_kernel_merged", "ba3c_probe_every", "ba3c_train_grads_ppo", "ba3c_sample_logp",
@@ -48,7 +48,8 @@ AB_OPTIONAL = {"ba3c_kernel_merged", "ba3c_probe_every", "ba3c_train_grads_ppo",
                "ba3c_input_grads", "ba3c_perturb_states", "ba3c_perturb_scores", "ba3c_ig_states",
                "ba3c_ig_accumulate", "ba3c_tsne_workspace_size", "ba3c_tsne_sqdist",
                "ba3c_tsne_affinities", "ba3c_tsne_step", "ba3c_gridpong_step", "ba3c_gridpong_render",
-               "ba3c_gridpong_step_skip", "ba3c_gridpong_view"}
+               "ba3c_gridpong_step_skip", "ba3c_gridpong_view", "ba3c_pca_workspace_size", "ba3c_pca_scatter",
+               "ba3c_pca_components", "ba3c_pca_project"}
 PPO_ADV_FROM_ROW = 1       # BA3C_PPO_ADV_FROM_ROW
 
 
@@ -100,6 +101,10 @@ def load():
         "ba3c_tsne_sqdist": (i32, [P, P, i32, i32, P, P]),
         "ba3c_tsne_affinities": (i32, [P, P, i32, f64, P, P, P]),
         "ba3c_tsne_step": (i32, [P, P, i32, P, P, P, f64, f64, f64, P, P]),
+        "ba3c_pca_workspace_size": (ctypes.c_size_t, [i32, i32]),
+        "ba3c_pca_scatter": (i32, [P, P, i32, i32, P, P]),
+        "ba3c_pca_components": (i32, [P, P, i32, P, P, i32, i32, P, P, P, P, P]),
+        "ba3c_pca_project": (i32, [P, P, i32, i32, P, i32, P, P, P, P]),
         "ba3c_sample_logp": (i32, [P, P, P, P, i32, i32, P, P, P]),
         "ba3c_bucket_tensor": (i32, [P]),
         "ba3c_set_phase2_event": (i32, [P, P]),

@@ -7,10 +7,15 @@ fc1 activations and `tsne.embed` the map, all on the device.
     python -m ba3c_amd.embed --load CKPT -e GridBoxing-v0 --num_actions 18 --fc_neurons 128 \\
         --fc_splits 4 --states 2048 --every 4 --perplexity 30 --iters 1000 --out boxing_tsne.npz
     python -m ba3c_amd.embed --random -e GridBreakout-v0 --states 512 --out random_tsne.npz
+    python -m ba3c_amd.embed --random -e GridBreakout-v0 --states 512 --method pca --out random_pca.npz
+
+--init pca starts the map from the first two principal-component scores (ba3c_amd/pca.py) instead
+of the seed's draw; --method pca writes those two scores as y and runs no t-SNE.
 
 The .npz holds y float32 [N, 2], value float32 [N], action int64 [N], episode and step int64 [N]
 (the simulator's running episode count and the decision within it) and kl float64 (tsne.embed's
-trace).  With PIL a scatter of y coloured by value (blue low, red high) is written next to it as
+trace); where PCA ran also explained float64 [2] (the explained-variance ratios) and pca_resid.
+With PIL a scatter of y coloured by value (blue low, red high) is written next to it as
 .png; without PIL only the .npz.
 """
 import json
@@ -18,7 +23,7 @@ import os
 
 import numpy as np
 
-from . import tsne
+from . import pca, tsne
 from .breakout import DEFAULT_LIMIT
 from .flags import ALL_GAMES, build_parser, resolve
 
@@ -51,14 +56,27 @@ def collect_states(engine, game, n_states, every=1, n_envs=None, seed=0, limit=D
     return torch.cat(states)[:n_states].contiguous(), meta[:, 0], meta[:, 1], meta[:, 2]
 
 
-def embed_states(engine, state, perplexity=30, iters=1000, seed=0):
-    """-> dict of y, value and kl for `state` (uint8 device [N,84,84,4])."""
+def embed_states(engine, state, perplexity=30, iters=1000, seed=0, init="random", method="tsne"):
+    """-> dict of y, value and kl for `state` (uint8 device [N,84,84,4]); where PCA ran (init
+    "pca" or method "pca": y is then the two scores and no t-SNE runs) also explained (the two
+    explained-variance ratios) and pca_resid."""
     import torch
     feats = engine.features(state)
     value = torch.cat([engine.forward(state[i:i + engine.max_batch])[2].clone()
                        for i in range(0, state.shape[0], engine.max_batch)])
-    y, kl = tsne.embed(feats, perplexity=perplexity, iters=iters, seed=seed)
-    return {"y": y.cpu().numpy(), "value": value.cpu().numpy(), "kl": kl}
+    fit = {}
+    if method == "pca":
+        fit = pca.fit(feats.contiguous(), min(2, feats.shape[1]), seed=seed)
+        y, kl = torch.nn.functional.pad(fit["scores"], (0, 2 - fit["scores"].shape[1])), np.zeros(0)
+    else:
+        y, kl = tsne.embed(feats, perplexity=perplexity, iters=iters, seed=seed, init=init, pca_out=fit)
+    out = {"y": y.cpu().numpy(), "value": value.cpu().numpy(), "kl": kl}
+    if fit:
+        out.update(explained=fit["ratio"].cpu().numpy(), pca_resid=fit["resid"].cpu().numpy())
+        if out["pca_resid"].max() > pca.RESID_WARN:
+            print("warning: PCA residual %.3g exceeds %g: more sweeps are needed" %
+                  (out["pca_resid"].max(), pca.RESID_WARN), flush=True)
+    return out
 
 
 def scatter_png(path, y, value, size=512, dot=2):
@@ -88,6 +106,10 @@ def embed_parser():
     p.add_argument("--out", default="tsne.npz")
     p.add_argument("--random", action="store_true", help="a uniform-random policy: no --load needed")
     p.add_argument("--limit", type=int, default=DEFAULT_LIMIT, help="LimitLengthPlayer's game steps")
+    p.add_argument("--init", choices=("random", "pca"), default="random",
+                   help="t-SNE's start: the seed's draw, or the first two principal-component scores")
+    p.add_argument("--method", choices=("tsne", "pca"), default="tsne",
+                   help="pca: y is the two leading principal-component scores and no t-SNE runs")
     return p
 
 
@@ -107,7 +129,7 @@ def main(argv=None):
     state, action, episode, step = collect_states(model.engine, args.environment, args.states, args.every,
                                                   seed=seed, limit=args.limit, frame_skip=args.frame_skip,
                                                   sticky=args.sticky, policy=policy)
-    out = embed_states(model.engine, state, args.perplexity, args.iters, seed)
+    out = embed_states(model.engine, state, args.perplexity, args.iters, seed, args.init, args.method)
     out.update(action=action, episode=episode, step=step)
     d = os.path.dirname(args.out)
     if d:

@@ -28,7 +28,7 @@ KL and grad belong to the Y the iteration started from.
 
 Schedule (`run_numpy`, `embed`).  lr = 200; exag = 12 and momentum = 0.5 for iterations 0 .. 249,
 then 1 and 0.8; Y is never re-centred.  Y0 = float32(1e-4 RandomState(seed).standard_normal((N, 2))),
-U0 = 0, G0 = 1.  The KL trace holds iteration t's KL for every t with (t + 1) % kl_every == 0.
+U0 = 0, G0 = 1; with init="pca" Y0 is ba3c_amd/pca.py's start (`initial_pca_numpy`).  The KL trace holds iteration t's KL for every t with (t + 1) % kl_every == 0.
 """
 import ctypes
 
@@ -142,6 +142,15 @@ def initial_numpy(n, seed):
     return y, np.zeros((n, 2), np.float32), np.ones((n, 2), np.float32)
 
 
+def initial_pca_numpy(x, seed=0, sweeps=32):
+    """The PCA start of ba3c_amd/pca.py: Y0 from the first two principal-component scores of X, the
+    first at standard deviation 1e-4; `initial_numpy`'s draw where X has no variance."""
+    from . import pca
+    fit = pca.fit_numpy(x, min(2, x.shape[1]), sweeps, seed)
+    n = x.shape[0]
+    return pca.y0_numpy(fit["scores"], fit["eigvals"][0], seed), np.zeros((n, 2), np.float32), np.ones((n, 2), np.float32)
+
+
 def run_numpy(p, iters=1000, lr=200.0, seed=0, kl_every=50, state=None):
     """The schedule from Y0 (or from `state` = (Y, U, G, first iteration)) -> (Y, U, G, KL trace)."""
     y, vel, gains, t0 = state if state is not None else initial_numpy(p.shape[0], seed) + (0,)
@@ -210,17 +219,27 @@ def step(p, y, vel, gains, exag, momentum, lr, work, kl_out=None):
                                           float(exag), float(momentum), float(lr), _ptr(work), _ptr(kl_out)))
 
 
-def embed(x, perplexity=30, iters=1000, lr=200, seed=0, kl_every=50):
+def embed(x, perplexity=30, iters=1000, lr=200, seed=0, kl_every=50, init="random", pca_out=None):
     """x float32 device [N, D] -> (Y float32 device [N, 2], KL trace float64 numpy).  Three launches
     make P, then every iteration is two launches on the current stream; the host reads nothing
-    until the trace is copied back at the end."""
+    until the trace is copied back at the end.  init="pca": Y0 comes from `pca.fit` on the device
+    (over the seed's draw, which stays where X has no variance); a dict passed as pca_out receives
+    that fit."""
     import torch
     n, d = x.shape
     check_perplexity(n, perplexity)
-    assert iters >= 1 and kl_every >= 1
-    work = _workspace(n, d)
+    assert iters >= 1 and kl_every >= 1 and init in ("random", "pca"), init
+    if init == "pca":
+        from . import pca
+        work = pca._workspace(n, d)                  # one buffer serves both kernel families
+    else:
+        work = _workspace(n, d)
     p, _ = affinities(sqdist(x.contiguous(), work), perplexity, work)
     y, vel, gains = (torch.from_numpy(v).to(x.device) for v in initial_numpy(n, seed))
+    if init == "pca":
+        fit = pca.fit(x.contiguous(), min(2, d), seed=seed, y0=y, work=work)
+        if pca_out is not None:
+            pca_out.update(fit)
     trace = torch.zeros(max(1, iters // kl_every), dtype=torch.float64, device=x.device)
     for t in range(iters):
         slot = trace[(t + 1) // kl_every - 1:] if (t + 1) % kl_every == 0 else None

@@ -40,6 +40,7 @@
 #include "ba3c_small.h"
 #include "ba3c_split.h"
 #include "ba3c_tsne.h"
+#include "ba3c_pca.h"
 #include "ba3c_wgrad6.h"
 
 using namespace ba3c;
@@ -1733,6 +1734,55 @@ int ba3c_tsne_step(void* stream, const float* p, int32_t n, float* y, float* vel
                            TsneStepArgs{p, reinterpret_cast<float2*>(y), reinterpret_cast<float2*>(vel),
                                         reinterpret_cast<float2*>(gains), w.part, kl_out, n, tsne_rows_per_wave(n),
                                         exag, momentum, lr}));
+  return BA3C_OK;
+}
+
+// ---- PCA (ba3c_pca.h): the refusals in the header's order ------------------------------------------
+static int pca_width(int32_t d, int32_t k, int32_t sweeps, bool with_sweeps) {
+  if (k < 1 || k > (d < Pca::M ? d : Pca::M)) return fail(BA3C_ERR_INVALID, "k must be in [1, min(8, d)]");
+  if (with_sweeps && (sweeps < 1 || sweeps > Pca::MAX_SWEEPS)) return fail(BA3C_ERR_INVALID, "sweeps must be in [1, 256]");
+  return BA3C_OK;
+}
+
+size_t ba3c_pca_workspace_size(int32_t n, int32_t d) {
+  if (tsne_range(n, d) != BA3C_OK) return 0;
+  return pca_work_layout(n, d, nullptr, nullptr, nullptr);
+}
+
+int ba3c_pca_scatter(void* stream, const float* x, int32_t n, int32_t d, void* work, double* c) {
+  if (!x || !work || !c) return fail(BA3C_ERR_INVALID, "null pointer");
+  CHECK(tsne_range(n, d));
+  if (!check_ptr(x) || !check_ptr(work) || !check_ptr(c))
+    return fail(BA3C_ERR_INVALID, "x, work and c must be 16-byte aligned");
+  HIP_TRY(launch_pca_scatter(static_cast<hipStream_t>(stream), x, n, d, work, c));
+  return BA3C_OK;
+}
+
+int ba3c_pca_components(void* stream, const double* c, int32_t d, const double* trace, const double* q0, int32_t k,
+                        int32_t sweeps, void* work, float* components, double* eigvals, double* ratio,
+                        double* resid) {
+  if (!c || !q0 || !work || !components || !eigvals || !ratio || !resid) return fail(BA3C_ERR_INVALID, "null pointer");
+  CHECK(tsne_range(Tsne::MIN_N, d));
+  CHECK(pca_width(d, k, sweeps, true));
+  auto al8 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; };
+  if (!check_ptr(c) || !check_ptr(q0) || !check_ptr(work) || !check_ptr(components) || !al8(trace) ||
+      !al8(eigvals) || !al8(ratio) || !al8(resid))
+    return fail(BA3C_ERR_INVALID,
+                "c, q0, work and components must be 16-byte and trace, eigvals, ratio and resid 8-byte aligned");
+  HIP_TRY(launch_pca_components(static_cast<hipStream_t>(stream), c, d, trace, q0, k, sweeps, work, components,
+                                eigvals, ratio, resid));
+  return BA3C_OK;
+}
+
+int ba3c_pca_project(void* stream, const float* x, int32_t n, int32_t d, const float* components, int32_t k,
+                     const double* eigvals, void* work, float* scores, float* y0) {
+  if (!x || !components || !eigvals || !work || !scores) return fail(BA3C_ERR_INVALID, "null pointer");
+  CHECK(tsne_range(n, d));
+  CHECK(pca_width(d, k, 1, false));
+  if (!check_ptr(x) || !check_ptr(components) || !check_ptr(work) || !check_ptr(scores) || (y0 && !check_ptr(y0)) ||
+      (reinterpret_cast<uintptr_t>(eigvals) & 7))
+    return fail(BA3C_ERR_INVALID, "x, components, work, scores and y0 must be 16-byte and eigvals 8-byte aligned");
+  HIP_TRY(launch_pca_project(static_cast<hipStream_t>(stream), x, n, d, components, k, eigvals, work, scores, y0));
   return BA3C_OK;
 }
 

@@ -734,6 +734,36 @@ int ba3c_tsne_affinities(void* stream, const float* dist, int32_t n, double perp
 int ba3c_tsne_step(void* stream, const float* p, int32_t n, float* y, float* vel, float* gains,
                    double exag, double momentum, double lr, void* work, double* kl_out);
 
+/* ---- Principal components of a set of feature vectors ---------------------------------------- */
+
+/* The leading principal components of ba3c_amd/pca.py, which states the rule and is the oracle
+ * (DESIGN.md section 25).  Handle-free; n and d as for t-SNE, 1 <= k <= m = min(8, d),
+ * 1 <= sweeps <= 256.  `work` is ba3c_pca_workspace_size(n, d) bytes (0 for an n or d out of
+ * range); it is at least ba3c_tsne_workspace_size(n, d), so one buffer serves both families, and
+ * the size of any n serves ba3c_pca_components at the same d.
+ *
+ * ba3c_pca_scatter: x float32 [n][d] -> c float64 [d][d] = Xc^T Xc of x centred by its column
+ * means (the Xc of ba3c_tsne_sqdist), symmetric bit for bit.  Four launches.
+ * ba3c_pca_components: c and q0 float64 [d][m] (the start of the block iteration) ->
+ * components float32 [k][d], eigvals, ratio (eigvals / trace; `trace` is a float64 device element
+ * or null: the diagonal of c is then summed) and resid float64 [k].  It overwrites `work` from its
+ * base.  2 sweeps + 3 launches.
+ * ba3c_pca_project: scores float32 [n][k] = Xc components^T; where y0 is not null and
+ * eigvals[0] > 0, y0 float32 [n][2] receives 1e-4 scores[:, :2] / sqrt(eigvals[0] / n) (a second
+ * column of zeros for k = 1), and with eigvals[0] <= 0 it keeps what the caller put there.  Three
+ * launches.
+ *
+ * Each refuses, on the host before any launch and in this order: (1) a null pointer (trace and y0
+ * may be null); (2) n, then d, then k, then sweeps out of range; (3) a pointer that is not 16-byte
+ * aligned (trace, eigvals, ratio, resid: 8-byte).  They never synchronise and never allocate. */
+size_t ba3c_pca_workspace_size(int32_t n, int32_t d);
+int ba3c_pca_scatter(void* stream, const float* x, int32_t n, int32_t d, void* work, double* c);
+int ba3c_pca_components(void* stream, const double* c, int32_t d, const double* trace,
+                        const double* q0, int32_t k, int32_t sweeps, void* work, float* components,
+                        double* eigvals, double* ratio, double* resid);
+int ba3c_pca_project(void* stream, const float* x, int32_t n, int32_t d, const float* components,
+                     int32_t k, const double* eigvals, void* work, float* scores, float* y0);
+
 #ifdef __cplusplus
 }
 #endif
